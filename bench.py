@@ -14,9 +14,14 @@ The ONE JSON line of rank 0 carries, besides the contract keys:
   roofline          HBM view of the dominant kernel (algorithmic 28 B/cell over its HIP-event duration)
   roofline_compute  the bound that actually binds OI: VALU issue (FP64 and other VALU wave-instructions per launch from the
                     committed rocprofv3 PMC bundle, 4 and 2 issue cycles each, over the live kernel time and 1024 SIMDs)
+and, with --full only (measurements of their own after the timed steps, N = 1, case oi):
   host_inclusive    the same call from numpy buffers (PCIe both ways; never `value`)
-  other_configs     the other BASELINE.json configs with the same per-step fields (N = 1 only)
-  cpu_baseline      the oracle's OpenMP / cell-list build of the same loop on this box's host cores (1 thread and all threads)
+  other_configs     the other BASELINE.json configs with the same per-step fields (--no-other-configs drops them)
+  cpu_baseline      the oracle's OpenMP / cell-list build of the same loop on the host's cores (1 thread and all threads;
+                    --no-cpu-baseline drops it)
+
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs); the inputs are seeded, so two
+builds of the project compare output for output.
 
 `--case ensi` / `--case nbh` run config 5 / config 4 instead of OI with the same contract (row tiles; EnSI broadcasts the
 observation block, the neighbourhood filter exchanges halo rows between neighbouring ranks with RCCL send / recv).
@@ -105,6 +110,23 @@ def cpu_baseline(ny, nx, S, seed, h, max_points, target_s=12.0):
             "algorithm": "cell-list radius query + per-point double inverse, OpenMP dynamic schedule (oracle/gridpp_oracle.c:orc_oi_full_omp)"}
 
 
+DUMP_MAX_VALUES = 12_000_000    # float32 values per output (48 MB): what a dump writes stays within 64 MB
+
+
+def dump_outputs(outdir, arrays, suffix=""):
+    """Writes each array a caller of the timed path receives as <outdir>/<name><suffix>.npy in float32.  An array of more than
+    DUMP_MAX_VALUES values is written as a fixed sample instead, <name>_sample<suffix>.npy: the values at the sorted distinct flat
+    indices of np.random.default_rng(0).integers(0, size, DUMP_MAX_VALUES), the same cells in every run and build of one shape."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = torch.as_tensor(a)
+        if a.numel() > DUMP_MAX_VALUES:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), DUMP_MAX_VALUES))
+            a, name = a.reshape(-1)[torch.from_numpy(idx).to(a.device)], name + "_sample"
+        np.save(os.path.join(outdir, name + suffix + ".npy"), a.to(torch.float32).cpu().numpy())
+
+
 def pmc_profile(workload, world):
     """Counters of the dominant kernel per launch from the committed rocprofv3 PMC passes of this exact workload (profiles/)."""
     try:
@@ -130,10 +152,14 @@ def main():
     ap.add_argument("--h", type=float, default=10000.0)
     ap.add_argument("--equal-tiles", action="store_true", help="case oi, N > 1: keep the equal row tiles (no rebalancing by measured kernel time)")
     ap.add_argument("--sync-calls", action="store_true", help="case oi: one blocking call per step instead of one analysis ahead (A/B of the GPP_ASYNC path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true", help="N = 1, case oi: after the timed steps also host_inclusive, other_configs and cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: no other_configs")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: time budget of the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import gridpp_amd as gridpp
@@ -328,6 +354,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert bool(torch.isfinite(torch.as_tensor(out)).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"neighbourhood" if case == "nbh" else "analysis": out}, "_rank%d" % rank if world > 1 else "")
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
@@ -401,7 +429,7 @@ def main():
                                                "reference_formulation_TFLOPs_equivalent": f64["reference_formulation_TFLOPs_equivalent"],
                                                "note": "EXECUTED FP64 flops (vector ADD / MUL / FMA + MFMA-F64) per call from the committed PMC bundle over the live kernel time; "
                                                        "the reference's E x E count is kept only as a labelled equivalent"}
-        if world == 1 and case == "oi":
+        if world == 1 and args.full and case == "oi":
             # the same call from numpy buffers (GPP_MEM_HOST): PCIe both ways included -- reported, never `value`
             hl, hlo, hbg, hplat, hplon, hobs, hrat, hpbg = make_workload(ny, nx, S, seed, 0, ny)
             hs = []
@@ -412,7 +440,7 @@ def main():
                 hs.append(time.perf_counter() - t1)
             res["host_inclusive"] = {"ms_per_step": min(hs) * 1e3, "value": cells_total / min(hs), "unit": "cells/s",
                                      "note": "numpy float32 buffers in, numpy out: 64 MB over PCIe each way inside the call"}
-        if world == 1 and not args.no_other_configs and case == "oi":
+        if world == 1 and args.full and not args.no_other_configs and case == "oi":
             from tools import bench_cases as bc
             oc = []
             try:
@@ -439,7 +467,7 @@ def main():
                 except Exception as e:
                     oc.append({"case": "cpu_baseline error", "message": repr(e)[:300]})
             res["other_configs"] = oc
-        if world == 1 and not args.no_cpu_baseline and case == "oi":
+        if world == 1 and args.full and not args.no_cpu_baseline and case == "oi":
             res["cpu_baseline"] = cpu_baseline(ny, nx, S, seed, args.h, args.max_points, args.cpu_seconds)
             res["speedup_vs_cpu_baseline"] = value / res["cpu_baseline"]["value"]
         print(json.dumps(res), flush=True)

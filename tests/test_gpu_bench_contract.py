@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def _json_line(text):
 
 
 def test_single_gpu_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "1"],
                          capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _json_line(out.stdout)
@@ -39,6 +40,22 @@ def test_single_gpu_line():
     for c in r["other_configs"]:
         assert c["ms"] > 0 and c["Mcells/s"] > 0 and 0 < c["frac_hbm"] < 1, c
     assert abs(r["value"] - 16e6 / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-6
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line holds the timed steps only; --dump-outputs writes the last step's analysis, the same in two runs."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--ny", "512", "--nx", "384", "--obs", "1000"]
+    dumps = []
+    for k in range(2):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = _json_line(out.stdout)
+        assert KEYS <= set(r) and r["steps"] == 2 and r["ms_per_step"] > 0
+        assert not {"host_inclusive", "other_configs", "cpu_baseline"} & set(r)
+        assert os.listdir(tmp_path / str(k)) == ["analysis.npy"]
+        dumps.append(np.load(tmp_path / str(k) / "analysis.npy"))
+    assert dumps[0].shape == (512, 384) and dumps[0].dtype == np.float32 and np.isfinite(dumps[0]).all()
+    np.testing.assert_array_equal(dumps[0], dumps[1])
 
 
 def test_two_rank_logic_on_one_gpu():

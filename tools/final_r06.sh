@@ -3,7 +3,7 @@
 #   tools/final_r06.sh suite     the GPU suite, plain and poisoned
 #   tools/final_r06.sh hostile   tools/hostile/run_all.sh 20
 #   tools/final_r06.sh soaks     the randomised soaks against the oracle, the large-n and ill-conditioned EnSI tables
-#   tools/final_r06.sh bench     slice overheads, the reference's benchmark rows, the default bench line
+#   tools/final_r06.sh bench     slice overheads, the reference's benchmark rows, the full bench line
 cd "$(dirname "$0")/.."
 O=gpurun_out/r06; mkdir -p $O
 noids() { grep -v amdgpu.ids; }
@@ -33,6 +33,6 @@ bench)
   python tools/slice_overhead_other.py 2>&1 | noids > $O/r06_slice_overhead_other.txt
   python tools/reference_benchmark_rows.py 2>/dev/null > $O/r06_reference_benchmark_rows.jsonl
   python tools/oi_variants.py 2>/dev/null > $O/r06_oi_variants.jsonl
-  python bench.py > $O/r06_bench_n1_final.json 2> $O/bench.err
+  python bench.py --full > $O/r06_bench_n1_final.json 2> $O/bench.err
   cat $O/r06_slice_overhead.txt; cut -c1-600 $O/r06_bench_n1_final.json ;;
 esac

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 evidence for the headline OI bench line (run on the GPU box from the repo root):
-#   1. --kernel-trace --stats of `python bench.py --steps 5 --warmup 2 --no-cpu-baseline`
+#   1. --kernel-trace --stats of `python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline`
 #   2. separate --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ instruction mix) of the same command, as the MI355X guide prescribes
 # Outputs land in gpurun_out/prof_oi/ ; the summaries are copied to profiles/ by hand (see profiles/README in DESIGN.md 6).
 set -u
@@ -8,7 +8,7 @@ OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/prof_oi
 mkdir -p $OUT
 REPO=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+CMD="python $REPO/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline"
 rm -rf /tmp/kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- $CMD > $OUT/bench_under_rocprof.json 2>/dev/null
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 $CMD > $OUT/bench_plain.json 2>/dev/null

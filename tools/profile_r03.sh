@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-3 evidence (run on the GPU box from the repo root; outputs under gpurun_out/prof_r03/; copy them to profiles/ as r03_* and
 # hbm_traffic.json):
-#   1. python bench.py (default: the driver's N = 1 line with other_configs and the CPU baseline)
+#   1. python bench.py --full (the driver's N = 1 line with other_configs and the CPU baseline)
 #   2. rocprofv3 --kernel-trace --stats of the OI bench, of C5 (EnSI) and of C4 (neighbourhood Mean / quantile_fast)
 #   3. separate --pmc passes of the OI bench (FETCH_SIZE, WRITE_SIZE, SQ instruction mix), as the MI355X guide prescribes
 #   4. --pmc FETCH_SIZE / WRITE_SIZE of C4 (quantile_fast traffic) and SQ_INSTS_VALU / SQ_INSTS_LDS / SQ_INSTS_VALU_MFMA_F64? of C5
@@ -10,7 +10,7 @@ REPO=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$REPO/gpurun_out/prof_r03
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python $REPO/bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 stats() {   # name, command...
   local name=$1; shift
   rm -rf /tmp/kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- "$@" > /dev/null 2>&1
