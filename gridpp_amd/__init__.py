@@ -1103,6 +1103,111 @@ def bilinear(igrid, opoints, values):
     return out
 
 
+# ---- downscaling, simple_gradient, full_gradient (include/gridpp.h:132-135,844-871,1017-1098) ---------------------------
+Nearest, Bilinear = 0, 1   # include/gridpp.h:132-135
+
+
+def _downscale_setup(name, igrid, output, ivalues, fields=()):
+    """Checks shared by the downscalers -> (values, other fields, ndim, output shape, empty, f64).  Fields are float32 (float64 in a
+    GPP_HOST_F64 call) arrays or float32 device tensors; None stays None."""
+    if not isinstance(igrid, Grid):
+        raise TypeError("%s: the input must be a Grid" % name)
+    if not isinstance(output, (Grid, Points)):
+        raise TypeError("%s: the output must be a Grid or Points" % name)
+    f64 = _wants_f64(ivalues, *fields)
+
+    def conv(a):
+        if a is None:
+            return None
+        if _is_dev(a):
+            import torch
+            return a.contiguous().to(torch.float32)
+        return np.ascontiguousarray(np.asarray(a), dtype=np.float64 if f64 else np.float32)
+    values = conv(ivalues)
+    shp = _shape(values)
+    if len(shp) not in (2, 3):
+        raise RuntimeError("%s: values must be 2-D or 3-D" % name)
+    # src/api/util.cpp:427-432: no rows (2-D) / no time levels or no rows (3-D) passes the size check
+    empty = shp[0] == 0 or (len(shp) == 3 and shp[1] == 0)
+    lead = (shp[0],) if len(shp) == 3 else ()
+    return values, [conv(a) for a in fields], len(shp), lead + _out_shape(output), empty, f64
+
+
+def _downscaler(downscaler):
+    if downscaler not in (Nearest, Bilinear):   # src/api/downscaling.cpp:16-17
+        raise ValueError("Invalid downscaler")
+    return int(downscaler)
+
+
+def downscaling(igrid, output, ivalues, downscaler):
+    """src/api/downscaling.cpp:7-61: `nearest` or `bilinear` from a Grid to a Grid or Points, 2-D or 3-D (T, Y, X) values."""
+    values, _, _, _, empty, _ = _downscale_setup("downscaling", igrid, output, ivalues)
+    if not empty and _shape(values)[-2:] != tuple(igrid.size()):
+        raise ValueError("Grid size is not the same as values")
+    if _downscaler(downscaler) == Nearest:
+        return nearest(igrid, output, values)
+    return bilinear(igrid, output, values)
+
+
+def _gradient_call(entry, igrid, output, values, fields, oshape, empty, f64, downscaler, *args):
+    """runs gpp_simple_gradient / gpp_full_gradient once the overload's checks have passed; fields = the present gradients"""
+    downscaler = _downscaler(downscaler)
+    mem = _mem(values, *fields)
+    if int(np.prod(oshape)) == 0:
+        return _empty_like_field(oshape, values)
+    if igrid._n and empty:
+        raise ValueError("Grid size is not the same as values")   # nothing to read from (the reference would index past the end)
+    out = _empty_like_field(oshape, values)
+    _sync_if_dev(mem)
+    nt = oshape[0] if len(_shape(values)) == 3 else 1
+    check(entry(igrid._h, output._h, _ptr(values), nt, *args, downscaler, _ptr(out),
+                mem | (_capi.HOST_F64 if f64 and mem == _capi.MEM_HOST else 0)))
+    return out
+
+
+def simple_gradient(igrid, output, ivalues, elev_gradient, downscaler=Nearest):
+    """src/api/simple_gradient.cpp: d(values) + (output elevation - d(grid elevation)) * elev_gradient, d = the downscaler.
+    No validity test: a missing elevation or gradient gives NaN."""
+    values, _, _, oshape, empty, f64 = _downscale_setup("simple_gradient", igrid, output, ivalues)
+    if not empty and _shape(values)[-2:] != tuple(igrid.size()):
+        raise ValueError("Grid size is not the same as values")
+    return _gradient_call(lib().gpp_simple_gradient, igrid, output, values, (), oshape, empty, f64, downscaler, float(elev_gradient))
+
+
+_NO_LAF = object()
+
+
+def full_gradient(igrid, output, ivalues, elev_gradient, laf_gradient=_NO_LAF, downscaler=Nearest):
+    """src/api/gradient.cpp:5-274: d(values) + (laf_corr + elev_corr), elev_corr = d(elev_gradient) * (output elevation - d(grid
+    elevation)) where both elevations are valid (else 0), laf_corr likewise.  A gradient with no elements leaves its term out.
+    Gradients have the shape of the values; only the Grid -> Grid 2-D overload may leave out laf_gradient (include/gridpp.h:1065)."""
+    values, (egrad, lgrad), nd, oshape, empty, f64 = _downscale_setup(
+        "full_gradient", igrid, output, ivalues, (elev_gradient, None if laf_gradient is _NO_LAF else laf_gradient))
+    grid_vec2 = isinstance(output, Grid) and nd == 2
+    if laf_gradient is _NO_LAF:
+        if not grid_vec2:
+            raise TypeError("full_gradient: laf_gradient is required unless both grids are 2-D fields (include/gridpp.h:1065-1098)")
+        lgrad = np.zeros((0, 0), np.float32)
+    if grid_vec2:   # gradient.cpp:10-11
+        if _shape(values) != tuple(igrid.size()):
+            raise ValueError("Values is the wrong size")
+    elif not empty and _shape(values)[-2:] != tuple(igrid.size()):
+        raise ValueError("Grid size is not the same as values")   # downscaling.cpp:8-9
+    present = []
+    # gradient.cpp:13-20 (checked in this order); the other overloads only assert it and would read past the end
+    for g, what in ((lgrad, "Laf gradient is the wrong size"), (egrad, "Elevation gradient is the wrong size")):
+        n = g.numel() if _is_dev(g) else g.size
+        if n == 0:
+            present.append(None)
+        elif _shape(g) != _shape(values):
+            raise ValueError(what)
+        else:
+            present.append(g)
+    lgrad, egrad = present
+    return _gradient_call(lib().gpp_full_gradient, igrid, output, values, [g for g in (egrad, lgrad) if g is not None], oshape, empty,
+                          f64, downscaler, _ptr(egrad), _ptr(lgrad))
+
+
 def point_in_rectangle(A, B, C_, D, m):   # src/api/util.cpp:571-582
     corners = (C.c_float * 8)(A.lat, A.lon, B.lat, B.lon, C_.lat, C_.lon, D.lat, D.lon)
     inside = C.c_int(0)

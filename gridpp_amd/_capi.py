@@ -68,6 +68,8 @@ SIGNATURES = {
     "gpp_gridding_nearest": [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int],
     "gpp_grid_get_box": [vp, vp, vp, C.c_int, vp, vp],
     "gpp_point_in_rectangle": [vp, C.c_float, C.c_float, ip],
+    "gpp_simple_gradient": [vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int],
+    "gpp_full_gradient": [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int],
     "gpp_structure_min_rho": [C.c_int, C.c_float, C.c_float, fp],
     "gpp_structure_localization_distance": [C.POINTER(gpp_structure), C.c_float, C.c_float, fp],
     "gpp_structure_corr": [C.POINTER(gpp_structure), fp, fp, C.c_int, fp],

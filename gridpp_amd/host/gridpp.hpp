@@ -11,6 +11,7 @@
 //   neighbourhood*, get_neighbourhood_thresholds :588-716
 //   nearest (all eight overloads)              :860-900
 //   bilinear(Grid, Grid|Points, vec2|vec3)     :902-930
+//   Downscaler, downscaling, simple_gradient, full_gradient (all four overloads each)  :132-135,844-871,1017-1098
 //   count, gridding, gridding_nearest          :938-1010
 //   fill, fill_missing, doping_square/circle, neighbourhood_search, calc_gradient
 //   calc_statistic / calc_quantile             :1454-1482
@@ -37,6 +38,7 @@ static const double radius_earth = 6.378137e6;
 
 enum Statistic { Mean = 0, Min = 10, Median = 20, Max = 30, Quantile = 40, Std = 50, Variance = 60, Sum = 70, Count = 80, RandomChoice = 90, Unknown = -1 };
 enum CoordinateType { Geodetic = 0, Cartesian = 1 };
+enum Downscaler { Nearest = 0, Bilinear = 1 };   // include/gridpp.h:132-135
 
 namespace detail {
 inline void check(int rc) {
@@ -744,6 +746,134 @@ inline vec3 bilinear(const Grid& igrid, const Grid& ogrid, const vec3& ivalues) 
     vec v = detail::flatten(ivalues, T, Y, X);
     size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
     return detail::unflatten(detail::bilinear_flat(igrid, ogrid.handle(), oy * ox, v, T, Y, X, T == 0 || Y == 0), T, oy, ox);
+}
+
+// ---- downscaling, simple_gradient, full_gradient (include/gridpp.h:844-871,1017-1098) -------------------------------
+namespace detail {
+inline void check_downscaler(Downscaler d) { if(d != Nearest && d != Bilinear) throw std::invalid_argument("Invalid downscaler"); }   // downscaling.cpp:16-17
+// values [T][Y][X] flattened -> [T][nq]; eg / lg NULL = that term is absent (full_gradient) -- simple_gradient passes neither
+inline vec gradient_flat(bool full, const Grid& igrid, gpp_points* to, size_t nq, const vec& v, size_t T, bool empty, const vec* eg,
+                         const vec* lg, float elev_gradient, Downscaler downscaler) {
+    check_downscaler(downscaler);
+    vec out(T * nq, MV);
+    if(T * nq == 0) return out;
+    if(cells(igrid) && empty) throw std::invalid_argument(GRID_MISMATCH);
+    if(full) check(gpp_full_gradient(igrid.handle(), to, v.data(), (int)T, eg ? eg->data() : nullptr, lg ? lg->data() : nullptr, (int)downscaler,
+                                     out.data(), GPP_MEM_HOST));
+    else check(gpp_simple_gradient(igrid.handle(), to, v.data(), (int)T, elev_gradient, (int)downscaler, out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline bool compatible(const Grid& g, const vec2& v) { return v.size() == 0 || fits(g, v.size(), v[0].size()); }   // util.cpp:427-429
+inline bool compatible(const Grid& g, const vec3& v) { return v.size() == 0 || v[0].size() == 0 || fits(g, v[0].size(), v[0][0].size()); }   // :430-432
+// a gradient of the reference's size() == 0 is absent (NULL); any other must have the shape of the values (gradient.cpp:13-20;
+// the other overloads only assert it and would read past the end)
+inline const vec* gradient_field(const vec2& g, vec& flat, size_t Y, size_t X, const char* what) {
+    if(g.size() == 0) return nullptr;
+    size_t a, b;
+    flat = flatten(g, a, b);
+    if(a != Y || b != X) throw std::invalid_argument(what);
+    return &flat;
+}
+inline const vec* gradient_field(const vec3& g, vec& flat, size_t T, size_t Y, size_t X, const char* what) {
+    if(g.size() == 0) return nullptr;
+    size_t a, b, c;
+    flat = flatten(g, a, b, c);
+    if(a != T || b != Y || c != X) throw std::invalid_argument(what);
+    return &flat;
+}
+const char* const LAF_MISMATCH = "Laf gradient is the wrong size";
+const char* const ELEV_MISMATCH = "Elevation gradient is the wrong size";
+}   // namespace detail
+// src/api/downscaling.cpp:7-61
+inline vec downscaling(const Grid& igrid, const Points& opoints, const vec2& ivalues, Downscaler downscaler) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    detail::check_downscaler(downscaler);
+    return downscaler == Nearest ? nearest(igrid, opoints, ivalues) : bilinear(igrid, opoints, ivalues);
+}
+inline vec2 downscaling(const Grid& igrid, const Grid& ogrid, const vec2& ivalues, Downscaler downscaler) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    detail::check_downscaler(downscaler);
+    return downscaler == Nearest ? nearest(igrid, ogrid, ivalues) : bilinear(igrid, ogrid, ivalues);
+}
+inline vec2 downscaling(const Grid& igrid, const Points& opoints, const vec3& ivalues, Downscaler downscaler) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    detail::check_downscaler(downscaler);
+    return downscaler == Nearest ? nearest(igrid, opoints, ivalues) : bilinear(igrid, opoints, ivalues);
+}
+inline vec3 downscaling(const Grid& igrid, const Grid& ogrid, const vec3& ivalues, Downscaler downscaler) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    detail::check_downscaler(downscaler);
+    return downscaler == Nearest ? nearest(igrid, ogrid, ivalues) : bilinear(igrid, ogrid, ivalues);
+}
+// src/api/simple_gradient.cpp:5-100
+inline vec2 simple_gradient(const Grid& igrid, const Grid& ogrid, const vec2& ivalues, float elev_gradient, Downscaler downscaler = Nearest) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    size_t Y, X;
+    vec v = detail::flatten(ivalues, Y, X);
+    size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
+    return detail::unflatten(detail::gradient_flat(false, igrid, ogrid.handle(), oy * ox, v, 1, Y == 0, nullptr, nullptr, elev_gradient, downscaler), oy, ox);
+}
+inline vec3 simple_gradient(const Grid& igrid, const Grid& ogrid, const vec3& ivalues, float elev_gradient, Downscaler downscaler = Nearest) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    size_t T, Y, X;
+    vec v = detail::flatten(ivalues, T, Y, X);
+    size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
+    return detail::unflatten(detail::gradient_flat(false, igrid, ogrid.handle(), oy * ox, v, T, T == 0 || Y == 0, nullptr, nullptr, elev_gradient, downscaler),
+                             T, oy, ox);
+}
+inline vec simple_gradient(const Grid& igrid, const Points& opoints, const vec2& ivalues, float elev_gradient, Downscaler downscaler = Nearest) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    size_t Y, X;
+    vec v = detail::flatten(ivalues, Y, X);
+    return detail::gradient_flat(false, igrid, opoints.handle(), opoints.size(), v, 1, Y == 0, nullptr, nullptr, elev_gradient, downscaler);
+}
+inline vec2 simple_gradient(const Grid& igrid, const Points& opoints, const vec3& ivalues, float elev_gradient, Downscaler downscaler = Nearest) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    size_t T, Y, X;
+    vec v = detail::flatten(ivalues, T, Y, X);
+    return detail::unflatten(detail::gradient_flat(false, igrid, opoints.handle(), opoints.size(), v, T, T == 0 || Y == 0, nullptr, nullptr, elev_gradient,
+                                                   downscaler), T, opoints.size());
+}
+// src/api/gradient.cpp:5-274
+inline vec2 full_gradient(const Grid& igrid, const Grid& ogrid, const vec2& ivalues, const vec2& elev_gradient, const vec2& laf_gradient = vec2(),
+                          Downscaler downscaler = Nearest) {
+    if((int)ivalues.size() != igrid.size()[0] || (int)(ivalues.size() ? ivalues[0].size() : 0) != igrid.size()[1])   // gradient.cpp:10-11
+        throw std::invalid_argument("Values is the wrong size");
+    size_t Y, X;
+    vec v = detail::flatten(ivalues, Y, X), lf, ef;
+    const vec* lg = detail::gradient_field(laf_gradient, lf, Y, X, detail::LAF_MISMATCH);
+    const vec* eg = detail::gradient_field(elev_gradient, ef, Y, X, detail::ELEV_MISMATCH);
+    size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
+    return detail::unflatten(detail::gradient_flat(true, igrid, ogrid.handle(), oy * ox, v, 1, Y == 0, eg, lg, 0, downscaler), oy, ox);
+}
+inline vec3 full_gradient(const Grid& igrid, const Grid& ogrid, const vec3& ivalues, const vec3& elev_gradient, const vec3& laf_gradient,
+                          Downscaler downscaler = Nearest) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    size_t T, Y, X;
+    vec v = detail::flatten(ivalues, T, Y, X), lf, ef;
+    const vec* lg = detail::gradient_field(laf_gradient, lf, T, Y, X, detail::LAF_MISMATCH);
+    const vec* eg = detail::gradient_field(elev_gradient, ef, T, Y, X, detail::ELEV_MISMATCH);
+    size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
+    return detail::unflatten(detail::gradient_flat(true, igrid, ogrid.handle(), oy * ox, v, T, T == 0 || Y == 0, eg, lg, 0, downscaler), T, oy, ox);
+}
+inline vec full_gradient(const Grid& igrid, const Points& opoints, const vec2& ivalues, const vec2& elev_gradient, const vec2& laf_gradient,
+                         Downscaler downscaler = Nearest) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    size_t Y, X;
+    vec v = detail::flatten(ivalues, Y, X), lf, ef;
+    const vec* lg = detail::gradient_field(laf_gradient, lf, Y, X, detail::LAF_MISMATCH);
+    const vec* eg = detail::gradient_field(elev_gradient, ef, Y, X, detail::ELEV_MISMATCH);
+    return detail::gradient_flat(true, igrid, opoints.handle(), opoints.size(), v, 1, Y == 0, eg, lg, 0, downscaler);
+}
+inline vec2 full_gradient(const Grid& igrid, const Points& opoints, const vec3& ivalues, const vec3& elev_gradient, const vec3& laf_gradient,
+                          Downscaler downscaler = Nearest) {
+    if(!detail::compatible(igrid, ivalues)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    size_t T, Y, X;
+    vec v = detail::flatten(ivalues, T, Y, X), lf, ef;
+    const vec* lg = detail::gradient_field(laf_gradient, lf, T, Y, X, detail::LAF_MISMATCH);
+    const vec* eg = detail::gradient_field(elev_gradient, ef, T, Y, X, detail::ELEV_MISMATCH);
+    return detail::unflatten(detail::gradient_flat(true, igrid, opoints.handle(), opoints.size(), v, T, T == 0 || Y == 0, eg, lg, 0, downscaler),
+                             T, opoints.size());
 }
 
 // ---- util (include/gridpp.h:1454-1482) -----------------------------------------------------------------------------

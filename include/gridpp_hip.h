@@ -49,8 +49,8 @@ extern "C" {
 /* With GPP_MEM_HOST: the float INPUT fields of the call hold float64 values (numpy's default dtype); they are uploaded as
  * they are and cast to float32 on the device -- the rounding the reference's typemap applies on the host
  * (swig/vector.i:42-55).  Outputs stay float32.  Honoured by gpp_optimal_interpolation_full,
- * gpp_optimal_interpolation_ensi, gpp_neighbourhood, gpp_nearest(_levels), gpp_bilinear (every `const float*` argument of
- * these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
+ * gpp_optimal_interpolation_ensi, gpp_neighbourhood, gpp_nearest(_levels), gpp_bilinear, gpp_simple_gradient and
+ * gpp_full_gradient (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
  * (their float fields), and by gpp_neighbourhood_quantile_fast for `input` only. */
 #define GPP_HOST_F64 4
 
@@ -199,6 +199,26 @@ int gpp_bilinear(gpp_points* igrid, gpp_points* to, const float* values, int nt,
 int gpp_grid_get_box(gpp_points* grid, const float* qlats, const float* qlons, int nq, int* inside, int* boxes);
 /* gridpp::point_in_rectangle (src/api/util.cpp:571-582): corners A, B, C, D as (lat, lon) pairs. */
 int gpp_point_in_rectangle(const float corners_latlon[8], float lat, float lon, int* inside);
+
+/* ---- downscaling with elevation / laf gradients (include/gridpp.h:132-135,844-871,1017-1098) ---------------------------
+ * downscaler: GPP_NEAREST (what gpp_nearest_levels computes) or GPP_BILINEAR (what gpp_bilinear computes), applied to each
+ * field on its own; anything else is GPP_EINVAL "Invalid downscaler" (src/api/downscaling.cpp:7-61).  `igrid` is a grid;
+ * values are [nt][ny][nx] of igrid, out is [nt][size of `to`]; all NaN if igrid is empty.  GPP_ERUNTIME ("Problem with
+ * bilinear interpolation...") exactly where gpp_bilinear would raise on one of the fields the reference downscales.  The
+ * nearest index and, for GPP_BILINEAR, the box and the weights are found once per location for all fields and levels.
+ * values / gradients / out follow `mem` (GPP_HOST_F64 honoured for the input fields). */
+#define GPP_NEAREST 0
+#define GPP_BILINEAR 1
+/* gridpp::simple_gradient, all four overloads (src/api/simple_gradient.cpp:5-100): out = d(values) + (elev of `to` -
+ * d(elevs of igrid)) * elev_gradient, with no validity test (a missing elevation or gradient gives NaN). */
+int gpp_simple_gradient(gpp_points* igrid, gpp_points* to, const float* values, int nt, float elev_gradient, int downscaler,
+                        float* out, int mem);
+/* gridpp::full_gradient, all four overloads (src/api/gradient.cpp:5-274): out = d(values) + (laf_corr + elev_corr) with
+ * elev_corr = d(elev_gradient) * (elev of `to` - d(elevs of igrid)) where both elevations are valid, else 0, and laf_corr
+ * the same with lafs.  elev_gradient / laf_gradient are [nt][ny][nx] (level t of the values uses level t) or NULL: that
+ * term is absent (the reference's size() == 0). */
+int gpp_full_gradient(gpp_points* igrid, gpp_points* to, const float* values, int nt, const float* elev_gradient,
+                      const float* laf_gradient, int downscaler, float* out, int mem);
 
 /* ---- structure functions (src/api/structure.cpp) -----------------------------
  * Scalar forms of BarnesStructure, CressmanStructure, SoarStructure, ToarStructure,

@@ -54,6 +54,7 @@ rows.append(("doping_square 200^2, 100000 points, halfwidth 5", 0.12, lambda: gr
 rows.append(("doping_circle 200^2, 100000 points, radius 5000", 2.00, lambda: gridpp.doping_circle(G200, Z200, P100000, np.ones(100000), np.ones(100000) * 5000, False)))
 R2000a, R2000b = np.random.rand(2000, 2000) * 100, np.random.rand(2000, 2000)
 rows.append(("calc_gradient 2000^2 LinearRegression hw=10", 0.45, lambda: gridpp.calc_gradient(R2000a, I2000, gridpp.LinearRegression, 10, 0, 100, 0)))
+rows.append(("full_gradient 1000^2", 1.59, lambda: gridpp.full_gradient(G1000, G1000, I1000, I1000, I1000)))   # tests/benchmark.py:72
 A2000 = np.random.rand(2000, 2000) < 0.5
 rows.append(("neighbourhood_search 2000^2 7x7", 1.11, lambda: gridpp.neighbourhood_search(R2000b, R2000b, 3, 0.7, 1, 0.1, A2000)))
 G100, P1000 = grid(100), points(1000)
