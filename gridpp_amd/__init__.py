@@ -1208,6 +1208,109 @@ def full_gradient(igrid, output, ivalues, elev_gradient, laf_gradient=_NO_LAF, d
                           f64, downscaler, _ptr(egrad), _ptr(lgrad))
 
 
+# ---- ensemble downscalers and smart (include/gridpp.h:138-143,945-990,1112) ----------------------------------------------
+Lt, Leq, Gt, Geq = 0, 10, 20, 30   # include/gridpp.h:138-143
+
+
+def _ens_setup(name, igrid, ogrid, cubes, threshold, comparison_operator):
+    """The checks the ensemble downscalers share (the reference checks none: a wrong shape reads out of bounds there) ->
+    (cubes, threshold, ne, f64).  Cubes are (Y, X, E), the threshold (oY, oX)."""
+    if not isinstance(igrid, Grid) or not isinstance(ogrid, Grid):
+        raise TypeError("%s: igrid and ogrid must be Grids" % name)
+    f64 = _wants_f64(*cubes)
+
+    def conv(a, ndim, what):
+        if _is_dev(a):
+            return _vec(a, ndim, what)
+        return _vec(a, ndim, what, np.float64 if f64 else np.float32)
+    cubes = [conv(a, 3, "values") for a in cubes]
+    threshold = conv(threshold, 2, "threshold")
+    _mem(threshold, *cubes)
+    shp = _shape(cubes[0])
+    if any(_shape(c) != shp for c in cubes[1:]):
+        raise ValueError("%s: ivalues_true, ivalues_false and threshold_values must have the same shape" % name)
+    if igrid._n and shp[:2] != tuple(igrid.size()):
+        raise ValueError("Grid size is not the same as values")
+    if _shape(threshold) != tuple(ogrid.size()):
+        raise ValueError("Grid size is not the same as threshold")
+    if igrid.get_coordinate_type() != ogrid.get_coordinate_type():
+        raise ValueError("Coordinate types must be the same")
+    if comparison_operator not in (Lt, Leq, Gt, Geq):
+        raise ValueError("Invalid comparison operator")
+    return cubes, threshold, shp[2], f64
+
+
+def _ens_call(entry, igrid, ogrid, cubes, ne, threshold, f64, *args):
+    out = _empty_like_field(tuple(ogrid.size()), threshold)
+    if ogrid._n == 0:
+        return out
+    mem = _mem(threshold, *cubes)
+    _sync_if_dev(mem)
+    if f64 and mem == _capi.MEM_HOST:
+        mem |= _capi.HOST_F64
+    check(entry(igrid._h, ogrid._h, *[_ptr(c) for c in cubes], int(ne), _ptr(threshold), *args, _ptr(out), mem))
+    return out
+
+
+def downscale_probability(igrid, ogrid, ivalues, threshold, comparison_operator):
+    """src/api/downscale_probability.cpp:7-67: the share of the valid members of the nearest input cell with
+    member OP threshold[i][j]; NaN where no member is valid.  ivalues is (Y, X, E), threshold (oY, oX)."""
+    cubes, threshold, ne, f64 = _ens_setup("downscale_probability", igrid, ogrid, [ivalues], threshold, comparison_operator)
+    return _ens_call(lib().gpp_downscale_probability, igrid, ogrid, cubes, ne, threshold, f64, int(comparison_operator))
+
+
+def _mask_threshold_downscale(name, igrid, ogrid, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator,
+                              statistic, quantile):
+    cubes, threshold, ne, f64 = _ens_setup(name, igrid, ogrid, [ivalues_true, ivalues_false, threshold_values], threshold,
+                                           comparison_operator)
+    if statistic not in (Mean, Min, Median, Max, Quantile, Std, Variance, Sum, Count, RandomChoice):   # src/api/util.cpp:106-108
+        raise RuntimeError("Internal error. Cannot compute statistic")
+    if statistic == Quantile and (quantile < 0 or quantile > 1):   # util.cpp:112-113
+        raise ValueError("calc_quantile: Quantile must be between 0 and 1 inclusive")
+    return _ens_call(lib().gpp_mask_threshold_downscale, igrid, ogrid, cubes, ne, threshold, f64, int(comparison_operator), int(statistic),
+                     float(quantile))
+
+
+def mask_threshold_downscale_consensus(igrid, ogrid, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator, statistic):
+    """src/api/mask_threshold_downscale_consensus.cpp:12-14,19-82: per output cell, member k comes from ivalues_true where
+    threshold_values[I][J][k] OP threshold[i][j], from ivalues_false otherwise (NaN where threshold_values is not valid), at the
+    nearest input cell (I, J); the members are reduced with `statistic` (Quantile: quantile 0, as the reference passes it)."""
+    return _mask_threshold_downscale("mask_threshold_downscale_consensus", igrid, ogrid, ivalues_true, ivalues_false, threshold_values,
+                                     threshold, comparison_operator, statistic, 0.0)
+
+
+def mask_threshold_downscale_quantile(igrid, ogrid, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator, quantile):
+    """src/api/mask_threshold_downscale_consensus.cpp:15-17: the same masked members reduced with calc_quantile(quantile)."""
+    return _mask_threshold_downscale("mask_threshold_downscale_quantile", igrid, ogrid, ivalues_true, ivalues_false, threshold_values,
+                                     threshold, comparison_operator, Quantile, quantile)
+
+
+def smart(igrid, ogrid, ivalues, num, structure):
+    """src/api/smart.cpp:12-66: the mean of the `num` input cells most correlated (structure.corr) with the output cell among
+    those within the structure's localization distance; rho descending, ties -> lower index of the input grid.  No validity
+    test on the values.  NaN where there is no candidate or num <= 0."""
+    if not isinstance(igrid, Grid) or not isinstance(ogrid, Grid):
+        raise TypeError("smart: igrid and ogrid must be Grids")
+    st = _structure(structure)
+    if _is_dev(ivalues):
+        values = _vec(ivalues, 2, "values")
+    else:
+        values = _vec(ivalues, 2, "values", np.float64 if _wants_f64(ivalues) else np.float32)
+    if igrid._n and _shape(values) != tuple(igrid.size()):
+        raise ValueError("Grid size is not the same as values")
+    if igrid.get_coordinate_type() != ogrid.get_coordinate_type():
+        raise ValueError("Coordinate types must be the same")
+    out = _empty_like_field(tuple(ogrid.size()), values)
+    if ogrid._n == 0:
+        return out
+    mem = _mem(values)
+    _sync_if_dev(mem)
+    if not _is_dev(values) and values.dtype == np.float64:
+        mem |= _capi.HOST_F64
+    check(lib().gpp_smart(igrid._h, ogrid._h, _ptr(values), int(num), st, _ptr(out), mem))
+    return out
+
+
 def point_in_rectangle(A, B, C_, D, m):   # src/api/util.cpp:571-582
     corners = (C.c_float * 8)(A.lat, A.lon, B.lat, B.lon, C_.lat, C_.lon, D.lat, D.lon)
     inside = C.c_int(0)

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("GPP_LIB") or os.path.join(_HERE, "lib", "libgridpp_hi
 
 GPP_OK, GPP_EINVAL, GPP_ERUNTIME, GPP_ENODEVICE = 0, -1, -2, -3
 MEM_HOST, MEM_DEVICE, ASYNC, HOST_F64, Q_HOST = 0, 1, 2, 4, 8
+ENSEMBLE_ROW_CAP = 1024   # GPP_ENSEMBLE_ROW_CAP of include/gridpp_hip.h
 
 
 class gpp_structure(C.Structure):
@@ -70,6 +71,9 @@ SIGNATURES = {
     "gpp_point_in_rectangle": [vp, C.c_float, C.c_float, ip],
     "gpp_simple_gradient": [vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int],
     "gpp_full_gradient": [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int],
+    "gpp_downscale_probability": [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_mask_threshold_downscale": [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int],
+    "gpp_smart": [vp, vp, vp, C.c_int, C.POINTER(gpp_structure), vp, C.c_int],
     "gpp_structure_min_rho": [C.c_int, C.c_float, C.c_float, fp],
     "gpp_structure_localization_distance": [C.POINTER(gpp_structure), C.c_float, C.c_float, fp],
     "gpp_structure_corr": [C.POINTER(gpp_structure), fp, fp, C.c_int, fp],

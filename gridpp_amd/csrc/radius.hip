@@ -757,3 +757,116 @@ extern "C" int gpp_staticcorr_points(gpp_points* points, gpp_points* knots, cons
     return GPP_OK;
     GPP_CATCH
 }
+
+// ---- smart (src/api/smart.cpp:12-66) ------------------------------------------------------------------------------------
+namespace {
+// the input cells inside an output cell's localization radius (KDTree::get_neighbours, match included) with corr(p1, p2) --
+// not corr_background, and cells with rho = 0 stay in (smart.cpp:36-47): counted (keys == NULL) or stored as the sortable
+// keys of k_staticcorr_candidates (rho, ~cell index) at the output cell's CSR offset
+__global__ __launch_bounds__(256) void k_smart_candidates(IxView ix, DevStructure st, const float* __restrict__ px, const float* __restrict__ py,
+                                                          const float* __restrict__ pz, const float* __restrict__ pe, const float* __restrict__ pl,
+                                                          int q0, int nq, int* __restrict__ cnt, const long long* __restrict__ offset, long long base,
+                                                          unsigned long long* __restrict__ keys) {
+    const int y = q0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if(y >= q0 + nq) return;
+    const float x1 = px[y], y1 = py[y], z1 = pz[y], e1 = pe[y], l1 = pl[y];
+    int c = 0;
+    long long w = keys ? offset[y] - base : 0;
+    visit_radius(ix, x1, y1, z1, st.R, true, [&](int j, int orig, float) {
+        if(keys) {
+            const float4 g = ix.sgeo[j];
+            const float rho = d_corr(st, x1, y1, z1, e1, l1, g.x, g.y, g.z, g.w, ix.smeta[j].x, false);   // corr(p1, p2)
+            keys[w++] = ((unsigned long long)f2ord(rho) << 32) | (unsigned)(~orig);
+        }
+        ++c;
+    });
+    if(!keys) cnt[y] = c;
+}
+// the m-th largest of n keys (n > m > 0), by bisection on the key value: the largest t with #(keys >= t) >= m -- the cut of
+// k_staticcorr_write, restated here: calling one function from both kernels reshaped k_staticcorr_write's loop nest
+__device__ __forceinline__ unsigned long long kth_largest_key(const unsigned long long* k, int n, int m) {
+    unsigned long long lo = 0ull, hi = ~0ull;
+    while(lo < hi) {
+        const unsigned long long mid = lo + ((hi - lo) >> 1) + 1ull;
+        int c = 0;
+        for(int i = 0; i < n; ++i) c += (k[i] >= mid) ? 1 : 0;
+        if(c >= m) lo = mid; else hi = mid - 1ull;
+    }
+    return lo;
+}
+// smart.cpp:48-63: the mean of the values of the min(num, n) cells of largest key (rho descending, ties -> lower index)
+__global__ __launch_bounds__(256) void k_smart_mean(const unsigned long long* __restrict__ keys, const long long* __restrict__ offset, long long base,
+                                                    const int* __restrict__ cnt, int q0, int nq, int num, const float* __restrict__ values,
+                                                    float* __restrict__ out) {
+    const int y = q0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if(y >= q0 + nq) return;
+    const unsigned long long* k = keys + (offset[y] - base);
+    const int n = cnt[y];
+    float r = NAN;
+    if(n > 0 && num > 0) {
+        const unsigned long long thr = n > num ? kth_largest_key(k, n, num) : 0ull;   // keys are distinct: exactly num of them are >= thr
+        float sum = 0;
+        int count = 0;
+        for(int i = 0; i < n; ++i) {
+            const unsigned long long key = k[i];
+            if(key >= thr) { sum += values[~(unsigned)(key & 0xffffffffull)]; ++count; }
+        }
+        r = sum / (float)count;
+    }
+    out[y] = r;
+}
+}   // namespace
+
+extern "C" int gpp_smart(gpp_points* igrid, gpp_points* ogrid, const float* values, int num, const gpp_structure* st, float* out, int mem) {
+    GPP_TRY
+    if(!igrid || !ogrid || !st) invalid("NULL argument");
+    if(igrid->n > 0 && igrid->nx <= 0) invalid("the input must be a Grid");
+    if(igrid->type != ogrid->type) invalid("Coordinate types must be the same");
+    const int nq = ogrid->n;
+    if(nq == 0) return GPP_OK;
+    if(!out) invalid("out is NULL");
+    ensure_device();
+    DevStructure d = gpp_resolve_structure(st);
+    if(d.fh) runtime("smart: spatially varying structure functions are not supported on the GPU path yet");
+    OutField o;
+    o.bind(out, nq, mem);
+    if(igrid->n == 0 || num <= 0) {   // no candidate / nothing kept: count == 0 (smart.cpp:59-61)
+        hipLaunchKernelGGL(k_fill_value, dim3((nq + 255) / 256), dim3(256), 0, stream(), o.d, (size_t)nq, NAN);
+        GPP_HIP(hipGetLastError());
+        o.finish();
+        GPP_HIP(hipStreamSynchronize(stream()));
+        return GPP_OK;
+    }
+    if(!values) invalid("values is NULL");
+    InField v;
+    v.bind(values, igrid->n, mem);
+    ogrid->to_device();
+    gpp_obs_index* ix = gpp_build_obs_index(igrid);
+    const IxView iv = view_of(ix);
+    DevBuf<int> cnt;
+    cnt.get(nq);
+    hipLaunchKernelGGL(k_smart_candidates, dim3((nq + 255) / 256), dim3(256), 0, stream(), iv, d, ogrid->d_x.p, ogrid->d_y.p, ogrid->d_z.p,
+                       ogrid->d_elev.p, ogrid->d_laf.p, 0, nq, cnt.p, (const long long*)nullptr, 0ll, (unsigned long long*)nullptr);
+    GPP_HIP(hipGetLastError());
+    DevBuf<long long> wide, offset;
+    const long long total = scan_counts(cnt.p, nq, wide, offset);
+    DevBuf<unsigned long long> keys;
+    for(auto ch : chunks_of(offset, nq, total)) {   // (one chunk unless the keys exceed CSR_CAP entries)
+        const int q0 = ch.first, n = ch.second - ch.first;
+        long long base = 0, end = total;
+        if(total > CSR_CAP) {
+            GPP_HIP(hipMemcpy(&base, offset.p + q0, sizeof(long long), hipMemcpyDeviceToHost));
+            GPP_HIP(hipMemcpy(&end, offset.p + ch.second, sizeof(long long), hipMemcpyDeviceToHost));
+        }
+        keys.get((size_t)std::max<long long>(end - base, 1));
+        hipLaunchKernelGGL(k_smart_candidates, dim3((n + 255) / 256), dim3(256), 0, stream(), iv, d, ogrid->d_x.p, ogrid->d_y.p, ogrid->d_z.p,
+                           ogrid->d_elev.p, ogrid->d_laf.p, q0, n, cnt.p, (const long long*)offset.p, base, keys.p);
+        hipLaunchKernelGGL(k_smart_mean, dim3((n + 255) / 256), dim3(256), 0, stream(), (const unsigned long long*)keys.p,
+                           (const long long*)offset.p, base, (const int*)cnt.p, q0, n, num, v.d, o.d);
+        GPP_HIP(hipGetLastError());
+    }
+    o.finish();
+    GPP_HIP(hipStreamSynchronize(stream()));
+    return GPP_OK;
+    GPP_CATCH
+}

@@ -12,6 +12,7 @@
 //   nearest (all eight overloads)              :860-900
 //   bilinear(Grid, Grid|Points, vec2|vec3)     :902-930
 //   Downscaler, downscaling, simple_gradient, full_gradient (all four overloads each)  :132-135,844-871,1017-1098
+//   ComparisonOperator, downscale_probability, mask_threshold_downscale_consensus / _quantile, smart  :138-143,945-990,1112
 //   count, gridding, gridding_nearest          :938-1010
 //   fill, fill_missing, doping_square/circle, neighbourhood_search, calc_gradient
 //   calc_statistic / calc_quantile             :1454-1482
@@ -39,6 +40,7 @@ static const double radius_earth = 6.378137e6;
 enum Statistic { Mean = 0, Min = 10, Median = 20, Max = 30, Quantile = 40, Std = 50, Variance = 60, Sum = 70, Count = 80, RandomChoice = 90, Unknown = -1 };
 enum CoordinateType { Geodetic = 0, Cartesian = 1 };
 enum Downscaler { Nearest = 0, Bilinear = 1 };   // include/gridpp.h:132-135
+enum ComparisonOperator { Lt = 0, Leq = 10, Gt = 20, Geq = 30 };   // include/gridpp.h:138-143
 
 namespace detail {
 inline void check(int rc) {
@@ -874,6 +876,67 @@ inline vec2 full_gradient(const Grid& igrid, const Points& opoints, const vec3& 
     const vec* eg = detail::gradient_field(elev_gradient, ef, T, Y, X, detail::ELEV_MISMATCH);
     return detail::unflatten(detail::gradient_flat(true, igrid, opoints.handle(), opoints.size(), v, T, T == 0 || Y == 0, eg, lg, 0, downscaler),
                              T, opoints.size());
+}
+
+// ---- ensemble downscalers and smart (include/gridpp.h:945-990,1112) ----------------------------------------------------
+namespace detail {
+// the checks the reference leaves out (a wrong shape reads out of bounds there); returns the flattened threshold
+inline vec ensemble_checks(const Grid& igrid, const Grid& ogrid, size_t Y, size_t X, const vec2& threshold, ComparisonOperator op) {
+    if(cells(igrid) && !fits(igrid, Y, X)) throw std::invalid_argument(GRID_MISMATCH);
+    size_t ty, tx;
+    vec t = flatten(threshold, ty, tx);
+    if(!((cells(ogrid) == 0 && t.empty()) || fits(ogrid, ty, tx))) throw std::invalid_argument("Grid size is not the same as threshold");
+    if(igrid.get_coordinate_type() != ogrid.get_coordinate_type()) throw std::invalid_argument("Coordinate types must be the same");
+    if(op != Lt && op != Leq && op != Gt && op != Geq) throw std::invalid_argument("Invalid comparison operator");
+    return t;
+}
+inline vec2 mask_threshold_downscale(const Grid& igrid, const Grid& ogrid, const vec3& ivalues_true, const vec3& ivalues_false,
+                                     const vec3& threshold_values, const vec2& threshold, ComparisonOperator op, Statistic statistic, float quantile) {
+    size_t Y, X, E, y2, x2, e2, y3, x3, e3;
+    vec vt = flatten(ivalues_true, Y, X, E), vf = flatten(ivalues_false, y2, x2, e2), tv = flatten(threshold_values, y3, x3, e3);
+    if(y2 != Y || x2 != X || e2 != E || y3 != Y || x3 != X || e3 != E)
+        throw std::invalid_argument("ivalues_true, ivalues_false and threshold_values must have the same shape");
+    vec t = ensemble_checks(igrid, ogrid, Y, X, threshold, op);
+    size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
+    vec out(oy * ox, MV);
+    check(gpp_mask_threshold_downscale(igrid.handle(), ogrid.handle(), vt.data(), vf.data(), tv.data(), (int)E, t.data(), (int)op, (int)statistic,
+                                       quantile, out.data(), GPP_MEM_HOST));
+    return unflatten(out, oy, ox);
+}
+}   // namespace detail
+// src/api/downscale_probability.cpp:7-67
+inline vec2 downscale_probability(const Grid& igrid, const Grid& ogrid, const vec3& ivalues, const vec2& threshold,
+                                  const ComparisonOperator& comparison_operator) {
+    size_t Y, X, E;
+    vec v = detail::flatten(ivalues, Y, X, E);
+    vec t = detail::ensemble_checks(igrid, ogrid, Y, X, threshold, comparison_operator);
+    size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
+    vec out(oy * ox, MV);
+    detail::check(gpp_downscale_probability(igrid.handle(), ogrid.handle(), v.data(), (int)E, t.data(), (int)comparison_operator, out.data(), GPP_MEM_HOST));
+    return detail::unflatten(out, oy, ox);
+}
+// src/api/mask_threshold_downscale_consensus.cpp:12-82
+inline vec2 mask_threshold_downscale_consensus(const Grid& igrid, const Grid& ogrid, const vec3& ivalues_true, const vec3& ivalues_false,
+                                               const vec3& threshold_values, const vec2& threshold, const ComparisonOperator& comparison_operator,
+                                               const Statistic& statistic) {
+    return detail::mask_threshold_downscale(igrid, ogrid, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator, statistic, 0);
+}
+inline vec2 mask_threshold_downscale_quantile(const Grid& igrid, const Grid& ogrid, const vec3& ivalues_true, const vec3& ivalues_false,
+                                              const vec3& threshold_values, const vec2& threshold, const ComparisonOperator& comparison_operator,
+                                              const float quantile_level) {
+    return detail::mask_threshold_downscale(igrid, ogrid, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator, Quantile,
+                                            quantile_level);
+}
+// src/api/smart.cpp:12-66
+inline vec2 smart(const Grid& igrid, const Grid& ogrid, const vec2& ivalues, int num, const StructureFunction& structure) {
+    size_t Y, X;
+    vec v = detail::flatten(ivalues, Y, X);
+    if(detail::cells(igrid) && !detail::fits(igrid, Y, X)) throw std::invalid_argument(detail::GRID_MISMATCH);
+    if(igrid.get_coordinate_type() != ogrid.get_coordinate_type()) throw std::invalid_argument("Coordinate types must be the same");
+    size_t oy = ogrid.size()[0], ox = ogrid.size()[1];
+    vec out(oy * ox, MV);
+    detail::check(gpp_smart(igrid.handle(), ogrid.handle(), v.data(), num, structure.c_struct(), out.data(), GPP_MEM_HOST));
+    return detail::unflatten(out, oy, ox);
 }
 
 // ---- util (include/gridpp.h:1454-1482) -----------------------------------------------------------------------------

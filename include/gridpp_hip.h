@@ -49,8 +49,9 @@ extern "C" {
 /* With GPP_MEM_HOST: the float INPUT fields of the call hold float64 values (numpy's default dtype); they are uploaded as
  * they are and cast to float32 on the device -- the rounding the reference's typemap applies on the host
  * (swig/vector.i:42-55).  Outputs stay float32.  Honoured by gpp_optimal_interpolation_full,
- * gpp_optimal_interpolation_ensi, gpp_neighbourhood, gpp_nearest(_levels), gpp_bilinear, gpp_simple_gradient and
- * gpp_full_gradient (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
+ * gpp_optimal_interpolation_ensi, gpp_neighbourhood, gpp_nearest(_levels), gpp_bilinear, gpp_simple_gradient,
+ * gpp_full_gradient, gpp_downscale_probability, gpp_mask_threshold_downscale (the cubes and the threshold) and gpp_smart
+ * (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
  * (their float fields), and by gpp_neighbourhood_quantile_fast for `input` only. */
 #define GPP_HOST_F64 4
 
@@ -220,6 +221,30 @@ int gpp_simple_gradient(gpp_points* igrid, gpp_points* to, const float* values, 
 int gpp_full_gradient(gpp_points* igrid, gpp_points* to, const float* values, int nt, const float* elev_gradient,
                       const float* laf_gradient, int downscaler, float* out, int mem);
 
+/* ---- ensemble downscalers (include/gridpp.h:138-143,945-990) ----------------------------------------------------------
+ * igrid is a grid, ogrid a grid (or any point set) of the same coordinate type; cubes are [ny][nx][ne] of igrid with the
+ * ne members contiguous, threshold and out are [size of ogrid].  Every output cell reads the members of its nearest input
+ * cell (what gpp_nearest computes, found once per call).  All NaN if igrid is empty.  GPP_EINVAL for a comparison operator
+ * that is none of the four.  Cubes / threshold / out follow `mem` (GPP_HOST_F64 honoured for the inputs). */
+#define GPP_LT 0
+#define GPP_LEQ 10
+#define GPP_GT 20
+#define GPP_GEQ 30
+/* members of a masked row that gpp_mask_threshold_downscale stages on chip; longer rows take a slower path through HBM */
+#define GPP_ENSEMBLE_ROW_CAP 1024
+/* gridpp::downscale_probability (src/api/downscale_probability.cpp:7-67): out = (valid members with member OP threshold) /
+ * (valid members), NaN where no member is valid. */
+int gpp_downscale_probability(gpp_points* igrid, gpp_points* ogrid, const float* values, int ne, const float* threshold,
+                              int comparison_operator, float* out, int mem);
+/* gridpp::mask_threshold_downscale_consensus / _quantile (src/api/mask_threshold_downscale_consensus.cpp:12-82): member k of
+ * a cell's masked row is NaN where threshold_values is not valid, ivalues_true where threshold_values OP threshold, else
+ * ivalues_false; out = calc_statistic(row, statistic), or calc_quantile(row, quantile) for GPP_QUANTILE (the _quantile
+ * form; _consensus passes quantile 0).  GPP_ERUNTIME "Internal error. Cannot compute statistic" for an unknown statistic,
+ * GPP_EINVAL for a quantile outside [0, 1] (a NaN quantile gives NaN).  GPP_RANDOMCHOICE: some valid member of the row. */
+int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid, const float* ivalues_true, const float* ivalues_false,
+                                 const float* threshold_values, int ne, const float* threshold, int comparison_operator,
+                                 int statistic, float quantile, float* out, int mem);
+
 /* ---- structure functions (src/api/structure.cpp) -----------------------------
  * Scalar forms of BarnesStructure, CressmanStructure, SoarStructure, ToarStructure,
  * PowerlawStructure, LinearStructure (structure.cpp:143-167,287-299,317-341,467-491,
@@ -268,6 +293,12 @@ int gpp_structure_corr(const gpp_structure* s, const float p1[7], const float p2
  * knot) for the knots a point keeps (inside its localization radius, rho > 0, the max_points largest if there are more; 0
  * elsewhere).  Scalar structure functions.  out follows `mem`. */
 int gpp_staticcorr_points(gpp_points* points, gpp_points* knots, const gpp_structure* structure, int max_points, float* out, int mem);
+
+/* gridpp::smart (src/api/smart.cpp:12-66): out [size of ogrid] = mean of `values` ([ny][nx] of igrid) over the min(num, n)
+ * input cells of largest corr(output cell, input cell) among the n cells within the structure's localization distance
+ * (rho descending, ties -> lower index of the input grid; cells with rho = 0 take part).  No validity test on the values;
+ * NaN where n = 0 or num <= 0.  Scalar structure functions.  values / out follow `mem` (GPP_HOST_F64 honoured). */
+int gpp_smart(gpp_points* igrid, gpp_points* ogrid, const float* values, int num, const gpp_structure* structure, float* out, int mem);
 
 /* ---- optimal interpolation ------------------------------------------------
  * replaces gridpp::optimal_interpolation_full (src/api/oi.cpp:138-341, Points
