@@ -1311,6 +1311,152 @@ def smart(igrid, ogrid, ivalues, num, structure):
     return out
 
 
+# ---- calibration by a curve (include/gridpp.h:79-85,731-789,1549-1557) -----------------------------------------------------
+OneToOne, MeanSlope, NearestSlope, Zero, Unchanged = 0, 10, 20, 30, 40   # include/gridpp.h:79-85
+_POLICIES = (OneToOne, MeanSlope, NearestSlope, Zero, Unchanged)
+
+
+def _ndim(a):
+    return a.dim() if _is_dev(a) else np.ndim(a)
+
+
+def _host_curve(a):
+    """A curve argument of the host-side forms -> C-contiguous float32 numpy array of any ndim."""
+    if hasattr(a, "detach") and hasattr(a, "cpu"):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
+
+
+def _curve_pair(curve_ref, curve_fcst):
+    """The two 1-D curves with the checks of src/api/curve.cpp:7-10."""
+    cr, cf = _host_curve(curve_ref), _host_curve(curve_fcst)
+    if cr.ndim != 1 or cf.ndim != 1:
+        raise ValueError("curve_ref and curve_fcst must be 1-D arrays (one curve) or 3-D arrays (one curve per cell)")
+    if cr.size != cf.size:
+        raise ValueError("curve_ref and curve_fcst must be the same size")
+    if cr.size == 0:
+        raise ValueError("curve_ref and curve_fcst cannot have size 0")
+    return cr, cf
+
+
+def _values_call(entry, values, *args):
+    """An element-wise array form: values (1-D or 2-D, host or torch CUDA) -> an array of the same shape."""
+    nd = _ndim(values)
+    if nd not in (1, 2):
+        raise RuntimeError("input must be a scalar or have 1 or 2 dimensions, got %d" % nd)
+    if _is_dev(values):
+        v = _vec(values, nd, "input")
+    else:
+        v = np.ascontiguousarray(np.asarray(values), dtype=np.float64 if _wants_f64(values) else np.float32)
+    shp = _shape(v)
+    n = int(np.prod(shp))
+    if n == 0:
+        return np.zeros(shp, np.float32)
+    mem = _mem(v)
+    _sync_if_dev(mem)
+    if not _is_dev(v) and v.dtype == np.float64:
+        mem |= _capi.HOST_F64
+    out = _empty_like_field(shp, v)
+    check(entry(_ptr(v), n, *args, _ptr(out), mem))
+    return out
+
+
+def apply_curve(fcst, curve_ref, curve_fcst, policy_below, policy_above):
+    """src/api/curve.cpp:6-133, all four overloads: a scalar, a 1-D or a 2-D field through one curve (1-D curves), or a 2-D
+    field through one curve per cell (curves (Y, X, C)).  Inside [curve_fcst[0], curve_fcst[-1]] the result is
+    interpolate(fcst, curve_fcst, curve_ref); outside, nearest_ref + slope * (fcst - nearest_fcst) with the slope of the
+    policy (Unchanged: the input).  Any curve works, sorted or not, with the reference's linear-scan rules.  The array forms
+    refuse an unknown policy whatever the data; the scalar form, like the reference, only where the input extrapolates with it."""
+    nd_ref, nd_fcst = _ndim(curve_ref), _ndim(curve_fcst)
+    if nd_ref == 3 or nd_fcst == 3:
+        return _apply_curve_field(fcst, curve_ref, curve_fcst, policy_below, policy_above)
+    cr, cf = _curve_pair(curve_ref, curve_fcst)
+    if _ndim(fcst) == 0:
+        out = C.c_float(np.nan)
+        check(lib().gpp_apply_curve_scalar(float(fcst), _ptr(cr), cr.size, _ptr(cf), cf.size, int(policy_below), int(policy_above), C.byref(out)))
+        return out.value
+    if policy_below not in _POLICIES or policy_above not in _POLICIES:
+        raise ValueError("Unknown extrapolation policy")
+    return _values_call(lib().gpp_apply_curve, fcst, _ptr(cr), cr.size, _ptr(cf), cf.size, int(policy_below), int(policy_above))
+
+
+def _apply_curve_field(fcst, curve_ref, curve_fcst, policy_below, policy_above):
+    if _ndim(curve_ref) != 3 or _ndim(curve_fcst) != 3:
+        raise ValueError("curve_ref and curve_fcst dimension sizes mismatch")
+    if _ndim(fcst) != 2:
+        raise ValueError("Fcst and curve_ref dimension sizes mismatch")
+    f64 = _wants_f64(fcst, curve_ref, curve_fcst)
+
+    def conv(a, ndim, what):
+        if _is_dev(a):
+            return _vec(a, ndim, what)
+        return _vec(a, ndim, what, np.float64 if f64 else np.float32)
+    v, cr, cf = conv(fcst, 2, "fcst"), conv(curve_ref, 3, "curve_ref"), conv(curve_fcst, 3, "curve_fcst")
+    mem = _mem(v, cr, cf)
+    if _shape(cr) != _shape(cf):   # curve.cpp:111-116
+        raise ValueError("curve_ref and curve_fcst dimension sizes mismatch")
+    if _shape(v) != _shape(cr)[:2]:
+        raise ValueError("Fcst and curve_ref dimension sizes mismatch")
+    ny, nx, nc = _shape(cr)
+    if ny * nx > 0 and nc == 0:
+        raise ValueError("curve_ref and curve_fcst cannot have size 0")
+    if policy_below not in _POLICIES or policy_above not in _POLICIES:
+        raise ValueError("Unknown extrapolation policy")
+    if ny * nx == 0:
+        return np.zeros((ny, nx), np.float32)
+    _sync_if_dev(mem)
+    if f64 and mem == _capi.MEM_HOST:
+        mem |= _capi.HOST_F64
+    out = _empty_like_field((ny, nx), v)
+    check(lib().gpp_apply_curve_field(_ptr(v), _ptr(cr), _ptr(cf), ny, nx, nc, nc, int(policy_below), int(policy_above), _ptr(out), mem))
+    return out
+
+
+def interpolate(x, iX, iY):
+    """src/api/util.cpp:377-426, scalar and vector forms: the curve (iX, iY) at x with the reference's linear-scan index rules
+    (invalid entries are skipped, duplicates of iX follow util.cpp:398-407); the end value outside [iX[0], iX[-1]], NaN for a
+    NaN x or an empty curve.  Where iX[0] is not valid the reference can reach an undefined index; this returns NaN there and
+    reads nothing out of bounds (outside the pinned behaviour)."""
+    ix, iy = _host_curve(iX), _host_curve(iY)
+    if ix.ndim != 1 or iy.ndim != 1:
+        raise RuntimeError("iX and iY must have 1 dimension")
+    if _ndim(x) == 0:
+        out = C.c_float(np.nan)
+        check(lib().gpp_interpolate_scalar(float(x), _ptr(ix), ix.size, _ptr(iy), iy.size, C.byref(out)))
+        return out.value
+    if ix.size != iy.size:
+        raise ValueError("Dimension mismatch. Cannot interpolate.")
+    if _ndim(x) != 1:
+        raise RuntimeError("x must be a scalar or have 1 dimension")
+    return _values_call(lib().gpp_interpolate, x, _ptr(ix), ix.size, _ptr(iy), iy.size)
+
+
+def quantile_mapping_curve(ref, fcst, quantiles=()):
+    """src/api/quantile_mapping.cpp:5-46 -> (curve_ref, curve_fcst): both inputs sorted; sizes 0 and 1 are returned as given.
+    With quantiles (each in [0, 1], else ValueError) entry i is element int(float32(q) * float32(S - 1)) of the inputs AS GIVEN,
+    not of the sorted copies: the reference indexes `ref` / `fcst` there (:41-42) and this reproduces it.  NaN inputs (no
+    defined order in the reference's std::sort) sort last."""
+    r, f = _host_curve(ref).ravel(), _host_curve(fcst).ravel()
+    q = _host_curve(quantiles).ravel()
+    n = max(r.size, f.size, q.size, 1)
+    out_ref, out_fcst = np.empty(n, np.float32), np.empty(n, np.float32)
+    count = C.c_int(0)
+    check(lib().gpp_quantile_mapping_curve(_ptr(r), r.size, _ptr(f), f.size, _ptr(q), q.size, _ptr(out_ref), _ptr(out_fcst), C.byref(count)))
+    return out_ref[:count.value].copy(), out_fcst[:count.value].copy()
+
+
+def monotonize_curve(curve_ref, curve_fcst):
+    """src/api/curve.cpp:134-250 -> (curve_ref, curve_fcst): pairs with a missing member are dropped, then every stretch where
+    curve_fcst does not increase by more than 0.1 is removed.  Two empty arrays where no pair is valid (the reference reads
+    an empty vector there)."""
+    cr, cf = _host_curve(curve_ref).ravel(), _host_curve(curve_fcst).ravel()
+    n = max(cr.size, cf.size, 1)
+    out_ref, out_fcst = np.empty(n, np.float32), np.empty(n, np.float32)
+    count = C.c_int(0)
+    check(lib().gpp_monotonize_curve(_ptr(cr), cr.size, _ptr(cf), cf.size, _ptr(out_ref), _ptr(out_fcst), C.byref(count)))
+    return out_ref[:count.value].copy(), out_fcst[:count.value].copy()
+
+
 def point_in_rectangle(A, B, C_, D, m):   # src/api/util.cpp:571-582
     corners = (C.c_float * 8)(A.lat, A.lon, B.lat, B.lon, C_.lat, C_.lon, D.lat, D.lon)
     inside = C.c_int(0)

@@ -74,6 +74,13 @@ SIGNATURES = {
     "gpp_downscale_probability": [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int],
     "gpp_mask_threshold_downscale": [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int],
     "gpp_smart": [vp, vp, vp, C.c_int, C.POINTER(gpp_structure), vp, C.c_int],
+    "gpp_apply_curve": [vp, C.c_longlong, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int],
+    "gpp_apply_curve_field": [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
+    "gpp_interpolate": [vp, C.c_longlong, vp, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_apply_curve_scalar": [C.c_float, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, fp],
+    "gpp_interpolate_scalar": [C.c_float, vp, C.c_int, vp, C.c_int, fp],
+    "gpp_monotonize_curve": [vp, C.c_int, vp, C.c_int, vp, vp, ip],
+    "gpp_quantile_mapping_curve": [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, ip],
     "gpp_structure_min_rho": [C.c_int, C.c_float, C.c_float, fp],
     "gpp_structure_localization_distance": [C.POINTER(gpp_structure), C.c_float, C.c_float, fp],
     "gpp_structure_corr": [C.POINTER(gpp_structure), fp, fp, C.c_int, fp],

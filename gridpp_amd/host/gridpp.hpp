@@ -13,6 +13,7 @@
 //   bilinear(Grid, Grid|Points, vec2|vec3)     :902-930
 //   Downscaler, downscaling, simple_gradient, full_gradient (all four overloads each)  :132-135,844-871,1017-1098
 //   ComparisonOperator, downscale_probability, mask_threshold_downscale_consensus / _quantile, smart  :138-143,945-990,1112
+//   Extrapolation, apply_curve (all four overloads), interpolate, quantile_mapping_curve, monotonize_curve  :79-85,731-789,1549-1557
 //   count, gridding, gridding_nearest          :938-1010
 //   fill, fill_missing, doping_square/circle, neighbourhood_search, calc_gradient
 //   calc_statistic / calc_quantile             :1454-1482
@@ -20,6 +21,7 @@
 // exactly where the reference flattens them itself (src/api/oi.cpp:69-86).  Errors: GPP_EINVAL ->
 // std::invalid_argument, everything else -> std::runtime_error (swig/gridpp.i:21-40 maps these to python).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <memory>
 #include <stdexcept>
@@ -41,6 +43,7 @@ enum Statistic { Mean = 0, Min = 10, Median = 20, Max = 30, Quantile = 40, Std =
 enum CoordinateType { Geodetic = 0, Cartesian = 1 };
 enum Downscaler { Nearest = 0, Bilinear = 1 };   // include/gridpp.h:132-135
 enum ComparisonOperator { Lt = 0, Leq = 10, Gt = 20, Geq = 30 };   // include/gridpp.h:138-143
+enum Extrapolation { OneToOne = 0, MeanSlope = 10, NearestSlope = 20, Zero = 30, Unchanged = 40 };   // include/gridpp.h:79-85
 
 namespace detail {
 inline void check(int rc) {
@@ -937,6 +940,78 @@ inline vec2 smart(const Grid& igrid, const Grid& ogrid, const vec2& ivalues, int
     vec out(oy * ox, MV);
     detail::check(gpp_smart(igrid.handle(), ogrid.handle(), v.data(), num, structure.c_struct(), out.data(), GPP_MEM_HOST));
     return detail::unflatten(out, oy, ox);
+}
+
+// ---- calibration by a curve (include/gridpp.h:79-85,731-789,1549-1557) ---------------------------------------------------
+// src/api/curve.cpp:6-77 (host only; the reference's lazy policy check)
+inline float apply_curve(float input, const vec& curve_ref, const vec& curve_fcst, Extrapolation policy_below, Extrapolation policy_above) {
+    float out = MV;
+    detail::check(gpp_apply_curve_scalar(input, curve_ref.data(), (int)curve_ref.size(), curve_fcst.data(), (int)curve_fcst.size(), (int)policy_below,
+                                         (int)policy_above, &out));
+    return out;
+}
+// src/api/curve.cpp:79-94.  The array forms refuse an unknown policy whatever the data.
+inline vec apply_curve(const vec& fcst, const vec& curve_ref, const vec& curve_fcst, Extrapolation policy_below, Extrapolation policy_above) {
+    vec out(fcst.size(), MV);
+    detail::check(gpp_apply_curve(fcst.data(), (long long)fcst.size(), curve_ref.data(), (int)curve_ref.size(), curve_fcst.data(), (int)curve_fcst.size(),
+                                  (int)policy_below, (int)policy_above, out.data(), GPP_MEM_HOST));
+    return out;
+}
+// src/api/curve.cpp:96-108 (rows may differ in length there; each row is one vector call, as in the reference)
+inline vec2 apply_curve(const vec2& fcst, const vec& curve_ref, const vec& curve_fcst, Extrapolation policy_below, Extrapolation policy_above) {
+    vec flat;
+    for(const auto& r : fcst) flat.insert(flat.end(), r.begin(), r.end());
+    vec out = apply_curve(flat, curve_ref, curve_fcst, policy_below, policy_above);
+    vec2 o(fcst.size());
+    size_t at = 0;
+    for(size_t y = 0; y < fcst.size(); y++) { o[y].assign(out.begin() + at, out.begin() + at + fcst[y].size()); at += fcst[y].size(); }
+    return o;
+}
+// src/api/curve.cpp:110-133: one curve per cell, curves (Y, X, C)
+inline vec2 apply_curve(const vec2& fcst, const vec3& curve_ref, const vec3& curve_fcst, Extrapolation policy_below, Extrapolation policy_above) {
+    size_t Y, X, yr, xr, cr, yf, xf, cf;
+    vec v = detail::flatten(fcst, Y, X), r = detail::flatten(curve_ref, yr, xr, cr), f = detail::flatten(curve_fcst, yf, xf, cf);
+    if(yr != yf || xr != xf || cr != cf) throw std::invalid_argument("curve_ref and curve_fcst dimension sizes mismatch");
+    if(Y != yr || X != xr) throw std::invalid_argument("Fcst and curve_ref dimension sizes mismatch");
+    vec out(Y * X, MV);
+    detail::check(gpp_apply_curve_field(v.data(), r.data(), f.data(), (int)Y, (int)X, (int)cr, (int)cf, (int)policy_below, (int)policy_above, out.data(),
+                                        GPP_MEM_HOST));
+    return detail::unflatten(out, Y, X);
+}
+// src/api/util.cpp:377-426
+inline float interpolate(float x, const vec& iX, const vec& iY) {
+    float out = MV;
+    detail::check(gpp_interpolate_scalar(x, iX.data(), (int)iX.size(), iY.data(), (int)iY.size(), &out));
+    return out;
+}
+inline vec interpolate(const vec& x, const vec& iX, const vec& iY) {
+    vec out(x.size(), MV);
+    detail::check(gpp_interpolate(x.data(), (long long)x.size(), iX.data(), (int)iX.size(), iY.data(), (int)iY.size(), out.data(), GPP_MEM_HOST));
+    return out;
+}
+// src/api/quantile_mapping.cpp:5-46 (host only): returns curve_ref, output_fcst receives curve_fcst
+inline vec quantile_mapping_curve(const vec& ref, const vec& fcst, vec& output_fcst, vec quantiles = vec()) {
+    const size_t cap = std::max(std::max(ref.size(), fcst.size()), std::max(quantiles.size(), (size_t)1));
+    vec out_ref(cap), out_fcst(cap);
+    int count = 0;
+    detail::check(gpp_quantile_mapping_curve(ref.data(), (int)ref.size(), fcst.data(), (int)fcst.size(), quantiles.data(), (int)quantiles.size(),
+                                             out_ref.data(), out_fcst.data(), &count));
+    out_ref.resize(count);
+    out_fcst.resize(count);
+    output_fcst = out_fcst;
+    return out_ref;
+}
+// src/api/curve.cpp:134-250 (host only): returns curve_ref, output_fcst receives curve_fcst
+inline vec monotonize_curve(vec curve_ref, vec curve_fcst, vec& output_fcst) {
+    const size_t cap = std::max(std::max(curve_ref.size(), curve_fcst.size()), (size_t)1);
+    vec out_ref(cap), out_fcst(cap);
+    int count = 0;
+    detail::check(gpp_monotonize_curve(curve_ref.data(), (int)curve_ref.size(), curve_fcst.data(), (int)curve_fcst.size(), out_ref.data(), out_fcst.data(),
+                                       &count));
+    out_ref.resize(count);
+    out_fcst.resize(count);
+    output_fcst = out_fcst;
+    return out_ref;
 }
 
 // ---- util (include/gridpp.h:1454-1482) -----------------------------------------------------------------------------

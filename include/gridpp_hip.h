@@ -52,7 +52,8 @@ extern "C" {
  * gpp_optimal_interpolation_ensi, gpp_neighbourhood, gpp_nearest(_levels), gpp_bilinear, gpp_simple_gradient,
  * gpp_full_gradient, gpp_downscale_probability, gpp_mask_threshold_downscale (the cubes and the threshold) and gpp_smart
  * (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
- * (their float fields), and by gpp_neighbourhood_quantile_fast for `input` only. */
+ * (their float fields), by gpp_neighbourhood_quantile_fast for `input` only, by gpp_apply_curve and gpp_interpolate for the values
+ * (their curves are host float32 arrays) and by gpp_apply_curve_field for the values and both curve slabs. */
 #define GPP_HOST_F64 4
 
 /* include/gridpp.h:120-123 */
@@ -244,6 +245,47 @@ int gpp_downscale_probability(gpp_points* igrid, gpp_points* ogrid, const float*
 int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid, const float* ivalues_true, const float* ivalues_false,
                                  const float* threshold_values, int ne, const float* threshold, int comparison_operator,
                                  int statistic, float quantile, float* out, int mem);
+
+/* ---- calibration by a curve (include/gridpp.h:79-85,731-789,1549-1557) -----------------------------------------------------
+ * Extrapolation policies of apply_curve (include/gridpp.h:79-85). */
+#define GPP_ONE_TO_ONE 0
+#define GPP_MEAN_SLOPE 10
+#define GPP_NEAREST_SLOPE 20
+#define GPP_ZERO 30
+#define GPP_UNCHANGED 40
+/* gridpp::apply_curve(vec | vec2, vec, vec, ...) (src/api/curve.cpp:79-108): one curve for all n values.  Inside
+ * [curve_fcst[0], curve_fcst[nc-1]] out = interpolate(fcst, curve_fcst, curve_ref), outside nearestObs + slope * (fcst -
+ * nearestFcst) with the slope of the policy (curve.cpp:6-77, quirks included: see gridpp_amd/csrc/curve.h).  The curve is always a
+ * host float32 array (the library uploads it); any curve works, sorted or not.  fcst / out follow `mem` (GPP_HOST_F64 honoured
+ * for fcst).  GPP_EINVAL before any device work: nc_ref != nc_fcst, nc == 0, a policy that is none of the five ("Unknown
+ * extrapolation policy": checked up front whatever the data -- the reference throws only when some value extrapolates with
+ * nc > 1).  n == 0 returns GPP_OK and writes nothing. */
+int gpp_apply_curve(const float* fcst, long long n, const float* curve_ref, int nc_ref, const float* curve_fcst, int nc_fcst,
+                    int policy_below, int policy_above, float* out, int mem);
+/* gridpp::apply_curve(vec2, vec3, vec3, ...) (src/api/curve.cpp:110-133): one curve per cell.  fcst / out are [ny][nx], the curves
+ * [ny][nx][nc] with nc contiguous; all follow `mem` (GPP_HOST_F64 honoured for the three inputs).  Errors as gpp_apply_curve. */
+int gpp_apply_curve_field(const float* fcst, const float* curve_ref, const float* curve_fcst, int ny, int nx, int nc_ref, int nc_fcst,
+                          int policy_below, int policy_above, float* out, int mem);
+/* gridpp::interpolate(vec, vec, vec) (src/api/util.cpp:415-426): out[i] = the curve (ix, iy) at x[i] with the linear-scan index
+ * rules of util.cpp:339-376, the end value outside [ix[0], ix[nc-1]], NaN for a NaN x or an empty curve.  ix / iy are host
+ * float32 arrays; x / out follow `mem` (GPP_HOST_F64 honoured for x).  GPP_EINVAL "Dimension mismatch. Cannot interpolate." */
+int gpp_interpolate(const float* x, long long n, const float* ix, int nc_x, const float* iy, int nc_y, float* out, int mem);
+/* Host-only forms (no GPU needed, like gpp_convert_coordinates); they run the per-value source of the kernels.
+ * gridpp::apply_curve(float, ...) (curve.cpp:6-77), with the reference's lazy policy check: an unknown policy is GPP_EINVAL only
+ * where the input extrapolates with it and nc > 1. */
+int gpp_apply_curve_scalar(float input, const float* curve_ref, int nc_ref, const float* curve_fcst, int nc_fcst, int policy_below,
+                           int policy_above, float* out);
+/* gridpp::interpolate(float, vec, vec) (util.cpp:377-414): an invalid x gives NaN before the sizes are compared, as there. */
+int gpp_interpolate_scalar(float x, const float* ix, int nc_x, const float* iy, int nc_y, float* out);
+/* gridpp::monotonize_curve (curve.cpp:134-250): out_ref / out_fcst hold nc floats, *count = entries written (0 where no pair of
+ * the curve is valid: the reference reads an empty vector there). */
+int gpp_monotonize_curve(const float* curve_ref, int nc_ref, const float* curve_fcst, int nc_fcst, float* out_ref, float* out_fcst,
+                         int* count);
+/* gridpp::quantile_mapping_curve (src/api/quantile_mapping.cpp:5-46): quantiles may be NULL (nq = 0).  out_ref / out_fcst hold
+ * max(n, nq) floats, *count = entries written.  With quantiles the index int(q * (n - 1)) selects from the UNSORTED inputs, as
+ * the reference does (:41-42).  NaN inputs sort last. */
+int gpp_quantile_mapping_curve(const float* ref, int n_ref, const float* fcst, int n_fcst, const float* quantiles, int nq,
+                               float* out_ref, float* out_fcst, int* count);
 
 /* ---- structure functions (src/api/structure.cpp) -----------------------------
  * Scalar forms of BarnesStructure, CressmanStructure, SoarStructure, ToarStructure,
