@@ -1197,8 +1197,8 @@ struct OiWorkspace {
     DevBuf<int> pair_n;
     hipEvent_t e0 = nullptr, e1 = nullptr, eu = nullptr, ev_fork = nullptr, ev_join = nullptr;
     // banded host path (round 6): upload / first pass / download per band of tile rows, and the patch of the tiles the first pass left to the list passes
-    static constexpr int MAXB = 8;
-    hipEvent_t ev_up[MAXB] = {}, ev_k[MAXB] = {}, ev_band0 = nullptr;
+    static constexpr int NBAND = 6;   // bands of tile rows, 1 : 2 : 3 : 3 : 2 : 1 (OiCall::banded_first_pass)
+    hipEvent_t ev_up[NBAND] = {}, ev_k[NBAND] = {}, ev_band0 = nullptr;
     DevBuf<float> patch;          // [tiles][64] analysis (+ [tiles][64] variance behind it)
     float* h_patch = nullptr;     // pinned mirror, then the tile ids
     size_t h_patch_cap = 0;
@@ -1499,204 +1499,310 @@ extern "C" int gpp_structure_corr(const gpp_structure* s, const float p1[7], con
 }
 
 void gpp_oi_drain_pending();
-static int oi_full_impl(gpp_points* bgrid, const float* background, const float* bvariance,
-                        gpp_points* points, const float* obs, const float* obs_variance,
-                        const float* background_at_points, const float* bvariance_at_points,
-                        const gpp_structure* st, int max_points, int allow_extrapolation,
-                        float* out, float* out_variance, int mem) {
-    GPP_TRY
-    // argument checks of oi.cpp:152-186 (sizes are implied by the handles; pointers must be present)
-    if(max_points < 0) invalid("max_points must be >= 0");
-    if(!bgrid || !points) invalid("grid/points handle is NULL");
-    if(bgrid->type != points->type)
-        invalid("Both background and observations points must be of same coordinate type (lat/lon or x/y)");
-    const int C = bgrid->n, S = points->n;
-    if(C > 0 && (!background || !out)) invalid("background/out is NULL");
-    if(S > 0 && (!obs || !obs_variance || !background_at_points)) invalid("observation arrays are NULL");
-    ensure_device();
-    g_stats = gpp_oi_stats();
-    g_stats.cells = C;
-    if(C == 0) return GPP_OK;
+namespace {
+// One optimal_interpolation call on the host: its arguments, its plan (which kernels, which streams) and what it learns from the status block.
+// A local of oi_full_impl -- completing a deferred call may run a nested oi_full_impl (gpp_oi_drain_pending) with a call object of its own.
+// The launch helpers take the stream they launch on; run_huge and fetch use the library stream.
+struct OiCall {
+    static constexpr size_t SB = 8 + 80 + 2 * GPP_NSLOT;   // status block, in 8-byte words
+    static constexpr int SHORT_ITEMS = 3072;               // as many work items as the chip holds waves of k_oi_union
+    static constexpr int NRUN_SHORT = 4 * 128, NRUN_LONG = 4 * 512;   // tiles of the k_oi grid behind a short / any other work list (grid-stride over the list)
+    static constexpr int BAND_MIN_TILE_ROWS = 16;          // the banded host path needs this many tile rows (every one of its six bands then holds one)
+    static constexpr size_t PAIR_PARK_MAX = (size_t)8 << 30;   // cells for k_oi_pairs: at most this many bytes of parked selections (128 B per cell)
 
+    // ---- the arguments, then C and S (the call object is an aggregate: oi_full_impl fills these, everything below starts from its initialiser) ----
+    gpp_points* const bgrid; const float* const background; const float* const bvariance; gpp_points* const points; const float* const obs;
+    const float* const obs_variance; const float* const background_at_points; const float* const bvariance_at_points; const gpp_structure* const st;
+    const int max_points, allow_extrapolation; float* const out; float* const out_variance; const int mem, C, S;
     OiWorkspace& ws = g_ws;
+    decltype(bgrid->union_memo)& memo = bgrid->union_memo;
+
+    // ---- fields; the staging buffers go back to the pool when the call ends ----
     InField f_bg, f_bvar, f_obs, f_ov, f_pbg, f_bvp;
     OutField f_out, f_var;
-    // Host arrays of a large grid (what a gridpp script passes, swig/vector.i:42-55,172-180): the background goes up, and the analysis comes
-    // down, in bands of tile rows beside the first pass when the call takes the tile kernel (`banded` below) -- 64 MB each way over PCIe ran
-    // strictly before and behind a 4.3 ms kernel.  Until that is known the upload is only prepared.
-    const bool band_candidate = !(mem & GPP_MEM_DEVICE) && C >= (1 << 20) && S > 0 && !path_env("GPP_OI_NO_BANDS");
-    const bool band_f64 = (mem & GPP_HOST_F64) != 0;     // float64 host arrays (numpy's default): a band goes up as doubles and is cast on the upload stream
-    Staged<double> wide_bg, wide_bv;                     // (returned to the pool at the end of the call: everything that reads them is behind the call's last synchronisation)
-    if(band_candidate) {
-        f_bg.d = f_bg.staged.get(C);
-        if(bvariance) f_bvar.d = f_bvar.staged.get(C);
-    }
-    else {
-        f_bg.bind(background, C, mem);
-        f_bvar.bind(bvariance, C, mem);
-    }
-    f_out.bind(out, C, mem);
-    f_var.bind(out_variance, C, mem);
+    Staged<double> wide_bg, wide_bv;   // float64 bands on their way up (banded path)
+    // whatever ends the call: no copy of it stays in flight on the side streams (into arrays the caller may free).  Declared behind the
+    // staging buffers, i.e. destroyed BEFORE them: the side streams are idle when a staging buffer returns to the pool.
+    struct BandGuard {
+        bool on = false;
+        ~BandGuard() { if(on) { (void)hipStreamSynchronize(stream2()); (void)hipStreamSynchronize(stream3()); } }
+    } band_guard;
 
-    if(S == 0) {   // oi.cpp:189-190: return the background
-        GPP_HIP(hipMemcpyAsync(f_out.d, f_bg.d, sizeof(float) * C, hipMemcpyDeviceToDevice, stream()));
-        if(f_var.d) {
-            if(f_bvar.d) GPP_HIP(hipMemcpyAsync(f_var.d, f_bvar.d, sizeof(float) * C, hipMemcpyDeviceToDevice, stream()));
-            else invalid("bvariance is required when the variance is requested and there are no observations");
-        }
-        f_out.finish(); f_var.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
-    }
-    f_obs.bind(obs, S, mem);
-    f_ov.bind(obs_variance, S, mem);
-    f_pbg.bind(background_at_points, S, mem);
-    f_bvp.bind(bvariance_at_points, S, mem);
+    // ---- the plan ----
+    gpp_obs_index* ix = nullptr;
+    OiArgs a = OiArgs();
+    int N = 32, WPB = 0;   // register-tile size of the solve: 32 rows (max_points <= 32, the common case) or 62 (one member cell per factorisation); waves per workgroup of k_oi_union
+    bool spatial = false, plain = false, use_lu = false, pairs_ok = false, memo_hit = false, use_union = false, big_ok = false, sp_union = false;
+    bool band_candidate = false, band_f64 = false, banded = false, band_down = false, zero_copy_out = false, steady = false; int async_slot = -1;
+    // (union path, decided behind the drain: a re-run inside it may have updated the geometry's memory)
+    bool pair_tiles = false, skip_k_oi = false, expect_long = false, overlap = false; int n_remembered = 0;
 
-    bgrid->to_device();
-    gpp_obs_index* ix = gpp_build_obs_index(points);
-
-    if(!ws.e0) { GPP_HIP(hipEventCreate(&ws.e0)); GPP_HIP(hipEventCreate(&ws.e1)); GPP_HIP(hipEventCreate(&ws.eu)); }
-    constexpr size_t SB = 8 + 80 + 2 * GPP_NSLOT;   // status block, in 8-byte words
-    if((mem & GPP_ASYNC) && !g_aslots[0].h) {
-        // everything a deferred call needs, on the FIRST call that asks for one (which itself runs synchronously: no memory of its geometry yet):
-        // page-locked status slots, events, the two streams beside the library stream -- milliseconds that must not fall into a later call
-        for(int k = 0; k < ASYNC_SLOTS; k++) {
-            AsyncSlot& sl = g_aslots[k];
-            GPP_HIP(hipHostMalloc((void**)&sl.h, SB * sizeof(unsigned long long), hipHostMallocDefault));
-            GPP_HIP(hipEventCreate(&sl.e0)); GPP_HIP(hipEventCreate(&sl.e1)); GPP_HIP(hipEventCreateWithFlags(&sl.ec, hipEventDisableTiming));
-        }
-        for(int k = 0; k < 2; k++) { GPP_HIP(hipEventCreateWithFlags(&ws.ev_pack[k], hipEventDisableTiming)); GPP_HIP(hipEventCreateWithFlags(&ws.ev_join2[k], hipEventDisableTiming)); }
-        (void)stream2(); (void)stream3();
-    }
-    // The workspace of this call -- the slot's observation block and status block -- is bound BELOW, behind the decision whether the call is deferred:
-    // a call that is not completes the deferred calls of the thread first, and one of those may need its synchronous re-run, i.e. a nested
-    // oi_full_impl that flips the slot, reallocates the slot buffers for its own observation count and overwrites the statistics (ADVICE round 5).
-    // Nothing of the workspace is touched, and no pointer into it is held, before that drain.
+    // ---- the workspace slot of this call (bound behind the drain) and its status block ----
     int wsl = 0;
-    DevBuf<float4>* pgeo_b = nullptr; DevBuf<float4>* oaux_b = nullptr; DevBuf<float4>* saux_b = nullptr;
-    DevBuf<unsigned long long>* status_b = nullptr;
-    int* d_ints = nullptr, *d_err = nullptr, *d_fb_count = nullptr, *d_big_count = nullptr, *d_huge_count = nullptr;
-    unsigned long long* d_counters = nullptr;
-    auto launch_pack = [&](hipStream_t on) {   // the observation block of this call (also clears the status block)
+    DevBuf<float4>* pgeo_b = nullptr; DevBuf<float4>* oaux_b = nullptr; DevBuf<float4>* saux_b = nullptr; DevBuf<unsigned long long>* status_b = nullptr;
+    int* d_ints = nullptr, *d_fb_count = nullptr, *d_big_count = nullptr, *d_huge_count = nullptr; unsigned long long* d_counters = nullptr;
+    const int* h_ints = nullptr;   // the page-locked mirror of the status block; fetch() copies its error word and counters here:
+    int err = 0; unsigned long long counters[80 + 2 * GPP_NSLOT];
+
+    // ---- what the attempts leave behind ----
+    bool ran_union = false, ran_overlap = false, ran_sp = false, sp_failed = false;
+    bool bands_down_done = false;   // the band downloads of this call are enqueued: the end of the call patches the declined tiles instead of copying everything
+    int overlap_left = 0, overlap_new = 0, overlap_remembered = 0, n_listed = 0, n_declined = 0, n_left = 0;   // (the last three: entries of ws.fb_list written by this call's first pass; declined tiles; 4-cell items left to k_oi)
+    const int* patch_l0 = nullptr; const int* patch_l1 = nullptr; int patch_n0 = 0, patch_n1 = 0;   // (banded path: the tiles to patch)
+
+    // ================================================= launch helpers =================================================
+    void launch_pack(hipStream_t on) {   // the observation block of this call (also clears the status block)
         hipLaunchKernelGGL(k_pack_obs, dim3((S + 255) / 256), dim3(256), 0, on, S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p,
                            f_obs.d, f_ov.d, f_pbg.d, f_bvp.d, 1, pgeo_b->p, oaux_b->p, saux_b->p, status_b->p, (int)SB);
         GPP_HIP(hipGetLastError());
-    };
-
-    // register-tile size of the solve: 32 rows (max_points <= 32, the common case) or 62 rows (everything up to 62
-    // usable observations per grid point; one member cell per factorisation)
-    const int N = (max_points > 0 && max_points <= 32) ? 32 : 62;
-    OiArgs a = OiArgs();
-    a.gx = bgrid->d_x.p; a.gy = bgrid->d_y.p; a.gz = bgrid->d_z.p; a.gelev = bgrid->d_elev.p; a.glaf = bgrid->d_laf.p;
-    a.bg = f_bg.d; a.bvar = f_bvar.d; a.out = f_out.d; a.out_var = f_var.d;
-    a.C = C; a.ny = bgrid->ny; a.nx = bgrid->nx;
-    a.tiled2d = (bgrid->nx > 0 && (long)bgrid->ny * bgrid->nx == C) ? 1 : 0;
-    a.wshift = 3;
-    if(a.tiled2d) {
-        a.wshift = gpp_tile_wshift(bgrid);
-        const int tw = 1 << a.wshift, th = 64 >> a.wshift;
-        a.tiles_x = (a.nx + tw - 1) / tw; a.ntiles = a.tiles_x * ((a.ny + th - 1) / th);
     }
-    else { a.tiles_x = 0; a.ntiles = (C + 63) / 64; }
-    a.s.smeta = ix->d_smeta.p; a.s.bin_start = ix->d_bin_start.p;
-    a.ogeo = ix->d_ogeo.p;
-    a.S = S; a.s.axis_a = ix->axis_a; a.s.axis_b = ix->axis_b; a.s.nbx = ix->nbx; a.s.nby = ix->nby;
-    a.s.amin = ix->amin; a.s.bmin = ix->bmin; a.s.inv_s = ix->inv_s;
-    a.s.st = gpp_resolve_structure(st);
-    gpp_bind_field(a.s.st, st, bgrid, points, ws.cell_idx, ws.obs_idx);
-    a.s.max_points = max_points;
-    { const double occ = (double)S / ((double)ix->nbx * ix->nby);
-      const int kk = (max_points > 0 && max_points <= N) ? max_points : N;
-      a.s.q0 = std::max(1, std::min(8, (int)std::ceil(0.5 * (std::sqrt(1.6 * kk / std::max(occ, 1e-3)) - 1.0))));
-      if(path_env("GPP_Q0")) a.s.q0 = atoi(path_env("GPP_Q0"));
-      // expected distance of the kk-th nearest observation: k_oi_union looks for its bulk disc below 1.5x that and then
-      // visits rings 0.15x wide
-      const double r_k = std::sqrt(kk / (3.14159265358979 * std::max(occ, 1e-3))) / ix->inv_s;
-      a.s.ring_r0 = (float)(1.5 * r_k); a.s.ring_dr = (float)(0.15 * r_k); }
-    a.allow_extrap = allow_extrapolation ? 1 : 0;
-    a.s.K = (max_points > 0 && max_points <= N) ? max_points : N;
-    a.debug = timing_env("GPP_OI_DEBUG") ? atoi(timing_env("GPP_OI_DEBUG")) : 0;
-
-    // Cholesky needs a symmetric positive definite P+R: true for every kernel on distances and for the even vertical / laf
-    // kernels (Barnes, Powerlaw, Linear); Cressman / SOAR / TOAR factors on SIGNED elevation / laf differences make P
-    // non-symmetric (structure.cpp:35-64), and a truncated kernel can be indefinite -> pivoted LU like the reference.
-    auto odd = [](int k) { return k == GPP_SK_CRESSMAN || k == GPP_SK_SOAR || k == GPP_SK_TOAR; };
-    const bool spatial = a.s.st.fh != nullptr;   // per-point length scales: P is not symmetric (corr(p1, p2) uses p1's scales)
-    bool use_lu = spatial || (a.s.st.v != 0 && odd(a.s.st.kv)) || (a.s.st.w != 0 && odd(a.s.st.kw)) || path_env("GPP_OI_FORCE_LU");
-    int err = 0;
-    unsigned long long counters[80 + 2 * GPP_NSLOT];
-    const bool plain = a.s.st.kh == GPP_SK_BARNES && a.s.st.kv == GPP_SK_BARNES && a.s.st.kw == GPP_SK_BARNES && !a.s.st.cv;
-    hipStream_t cur = stream();   // the stream the launch helpers below use: the library stream, or stream2() for the list passes that run beside the first pass
-    auto launch_k_oi = [&](const bool lu) {   // k_oi over a.nrun tiles (all, or the fallback list of k_oi_union)
+    void launch_k_oi(const bool lu, hipStream_t on) {   // k_oi over a.nrun tiles (all, or the fallback list of k_oi_union)
         const dim3 grid((a.nrun + 3) / 4), block(256);
         if(spatial) {   // (plain: three Barnes factors with per-point scales -- the straight-line correlation code takes them per lane)
-            if(N == 32) { if(plain) hipLaunchKernelGGL((k_oi<32, true, true, true>), grid, block, 0, cur, a); else hipLaunchKernelGGL((k_oi<32, true, false, true>), grid, block, 0, cur, a); }
-            else hipLaunchKernelGGL((k_oi<62, true, false, true>), grid, block, 0, cur, a);
+            if(N == 32) { if(plain) hipLaunchKernelGGL((k_oi<32, true, true, true>), grid, block, 0, on, a); else hipLaunchKernelGGL((k_oi<32, true, false, true>), grid, block, 0, on, a); }
+            else hipLaunchKernelGGL((k_oi<62, true, false, true>), grid, block, 0, on, a);
         }
         else if(N == 32) {
-            if(lu) hipLaunchKernelGGL((k_oi<32, true, false, false>), grid, block, 0, cur, a);
-            else if(plain) hipLaunchKernelGGL((k_oi<32, false, true, false>), grid, block, 0, cur, a);
-            else hipLaunchKernelGGL((k_oi<32, false, false, false>), grid, block, 0, cur, a);
+            if(lu) hipLaunchKernelGGL((k_oi<32, true, false, false>), grid, block, 0, on, a);
+            else if(plain) hipLaunchKernelGGL((k_oi<32, false, true, false>), grid, block, 0, on, a);
+            else hipLaunchKernelGGL((k_oi<32, false, false, false>), grid, block, 0, on, a);
         }
         else {
-            if(lu) hipLaunchKernelGGL((k_oi<62, true, false, false>), grid, block, 0, cur, a);
-            else hipLaunchKernelGGL((k_oi<62, false, false, false>), grid, block, 0, cur, a);
+            if(lu) hipLaunchKernelGGL((k_oi<62, true, false, false>), grid, block, 0, on, a);
+            else hipLaunchKernelGGL((k_oi<62, false, false, false>), grid, block, 0, on, a);
         }
         GPP_HIP(hipGetLastError());
-    };
+    }
     // Cholesky path with the 32-row tile: the cells whose observation set no other cell of their work item shares (all of them on
     // rough terrain with elevation-dependent rho) are parked by k_oi and solved by k_oi_pairs at twice the occupancy (128 B of
     // selection per cell; beyond PAIR_PARK_MAX bytes of it k_oi solves them itself as before).  k_oi over a work list leaves
     // the counts of the cells it does not visit alone: they are cleared first.
-    constexpr size_t PAIR_PARK_MAX = (size_t)8 << 30;
-    const bool pairs_ok = N == 32 && !spatial && (size_t)C * 128 <= PAIR_PARK_MAX && !path_env("GPP_OI_NO_PAIRS");
-    auto park_on = [&](const bool clear) {
+    void park_on(const bool clear, hipStream_t on) {
         a.pair_sel = ws.pair_sel.get((size_t)C * 32); a.pair_n = ws.pair_n.get((size_t)C);
-        if(clear) GPP_HIP(hipMemsetAsync(a.pair_n, 0, (size_t)C * sizeof(int), cur));
-    };
-    auto launch_pairs = [&]() {
+        if(clear) GPP_HIP(hipMemsetAsync(a.pair_n, 0, (size_t)C * sizeof(int), on));
+    }
+    void launch_pairs(hipStream_t on) {
         const dim3 grid((a.ntiles + 3) / 4), block(256);
-        if(plain) hipLaunchKernelGGL(k_oi_pairs<true>, grid, block, 0, cur, a);
-        else hipLaunchKernelGGL(k_oi_pairs<false>, grid, block, 0, cur, a);
+        if(plain) hipLaunchKernelGGL(k_oi_pairs<true>, grid, block, 0, on, a);
+        else hipLaunchKernelGGL(k_oi_pairs<false>, grid, block, 0, on, a);
         GPP_HIP(hipGetLastError());
         a.pair_sel = nullptr; a.pair_n = nullptr;
-    };
-    const int* h_ints = nullptr;   // (the page-locked mirror of the status block: bound with the workspace below)
-    auto fetch = [&]() {   // the whole status block in one copy
+    }
+    void fetch() {   // the whole status block in one copy
         GPP_HIP(hipMemcpyAsync(ws.h_status, status_b->p, SB * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream()));
         GPP_HIP(hipStreamSynchronize(stream()));
         err = h_ints[0];
         memcpy(counters, ws.h_status + 8, sizeof(counters));
-    };
-    // one factorisation per tile (k_oi_union) when the system is symmetric and max_points fits the 32-column tile;
-    // the tiles it declines, and every other configuration, run on k_oi (one factorisation per distinct selection)
-    // (With elevation / laf dependent rho the cells of a tile agree less; on smooth terrain most tiles still fit, on
-    //  white-noise elevations none does and the first pass costs a few per cent before the lists hand everything to k_oi.)
-    const bool want_union = path_env("GPP_OI_UNION") ? atoi(path_env("GPP_OI_UNION")) != 0 : true;
-    auto& memo = bgrid->union_memo;
-    const bool memo_hit = memo.points_id == points->serial && memo.h == a.s.st.h && memo.v == a.s.st.v && memo.w == a.s.st.w && memo.kh == a.s.st.kh &&
-                          memo.kv == a.s.st.kv && memo.kw == a.s.st.kw && memo.cv == a.s.st.cv && memo.max_points == max_points;
-    const bool memo_says_no = memo_hit && memo.declined > 0.5f;   // more than half of the tiles went to k_oi last time: skip the first pass
-    // (the 62-row form only for 33 <= max_points <= 62: with max_points = 0 a cell may hold more than any tile kernel can)
-    const bool use_union = !use_lu && (N == 32 || (max_points > 32 && max_points <= 62)) && want_union && !memo_says_no && !path_env("GPP_OI_NO_UNION");
-    const int WPB = N == 32 ? UnionCfg<32>::WPB : UnionCfg<64>::WPB;   // work items (waves) per workgroup of k_oi_union
-    // ---- the banded host path (see band_candidate above) --------------------------------------------------------------------------------
-    a.tile0 = 0; a.tile_n = a.ntiles;
-    const bool banded = band_candidate && a.tiled2d && use_union && N == 32 && !path_env("GPP_OI_PAIR_TILES") && a.ntiles / std::max(a.tiles_x, 1) >= 2 * OiWorkspace::MAXB;
-    if(band_candidate && !banded) {   // whole arrays after all
-        f_bg.bind(background, C, mem);
-        f_bvar.bind(bvariance, C, mem);
     }
-    if(banded && band_f64) { wide_bg.get(C); if(bvariance) wide_bv.get(C); }
-    // The analysis comes down per band only into page-locked memory (the Python mirror's result arrays, gpp_host_alloc): a copy into pageable
-    // memory blocks the host until it is done, i.e. until the band's kernel has run -- nothing behind it would be enqueued in time.
-    bool band_down = false, zero_copy_out = false;
-    if(banded) {
-        hipPointerAttribute_t at;
-        band_down = hipPointerGetAttributes(&at, out) == hipSuccess && at.type == hipMemoryTypeHost;
-        (void)hipGetLastError();
-        if(band_down && out_variance) { band_down = hipPointerGetAttributes(&at, out_variance) == hipSuccess && at.type == hipMemoryTypeHost; (void)hipGetLastError(); }
+    void mark_and_fetch() { GPP_HIP(hipEventRecord(ws.e1, stream())); fetch(); }   // (e1: the end of what the statistics time)
+    // cells with more usable observations than the 62-row tile holds are listed: symmetric systems go to k_oi_big (Cholesky, up
+    // to BIG_N observations), what that kernel cannot hold and every listed cell of a non-symmetric or spatially varying
+    // structure to k_oi_huge (pivoted elimination in HBM scratch, no capacity of its own)
+    void run_huge(const int* d_list, const int* d_count, const int ncells) {
+        // scratch for the worst case of this call: every observation a candidate, max_points (or all of them) selected
+        size_t kcap = 1; while(kcap < (size_t)S) kcap <<= 1;
+        const size_t ncap = (max_points > 0) ? (size_t)std::min(max_points, S) : (size_t)S;
+        const size_t per_wg = ncap * (ncap + 2) * sizeof(double) + kcap * sizeof(unsigned long long);
+        size_t budget = (size_t)16 << 30;   // 16 GB of the 288 GB for this rarely used path
+        if(path_env("GPP_OI_HUGE_BUDGET_MB")) budget = (size_t)atol(path_env("GPP_OI_HUGE_BUDGET_MB")) << 20;
+        if(per_wg > budget) runtime("optimal_interpolation: a grid point may select more observations than the scratch budget of the general kernel holds (set max_points, or raise GPP_OI_HUGE_BUDGET_MB)");
+        const int nwg = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)ncells, 512), budget / per_wg));
+        a.huge_kcap = (int)kcap; a.huge_ncap = (int)ncap;
+        a.huge_keys = ws.huge_keys.get((size_t)nwg * kcap);
+        a.huge_mat = ws.huge_mat.get((size_t)nwg * ncap * (ncap + 2));
+        if(spatial) hipLaunchKernelGGL(k_oi_huge<true>, dim3(nwg), dim3(256), 0, stream(), a, d_list, d_count);
+        else hipLaunchKernelGGL(k_oi_huge<false>, dim3(nwg), dim3(256), 0, stream(), a, d_list, d_count);
+        GPP_HIP(hipGetLastError());
+    }
+    void launch_union(const long items, const bool list, hipStream_t on) {   // the scalar tile kernel, one wave per work item
+        const long nb = (items + WPB - 1) / WPB;
+        const dim3 grid((unsigned)std::min<long>(nb, 0x7fffffffL)), block(64 * UnionCfg<32>::WPB);
+        // (max_points 33 .. 48: the 48-column form at two waves per SIMD; 49 .. 62: the 64-column form)
+        if(N != 32 && max_points <= 48 && !path_env("GPP_OI_NO_UNION48")) gpp_launch_union48(a, grid.x, plain, list, on);
+        else if(N != 32) gpp_launch_union64(a, grid.x, plain, list, on);
+        // (round 6: the first pass of the 32-column form shares one factorisation between the two tiles of a pair)
+        else if(!list && pair_tiles) {
+            const dim3 pgrid((unsigned)std::min<long>(union_pair_count(a), 0x7fffffffL)), pblock(128);
+            if(plain) hipLaunchKernelGGL(k_oi_union_pair<true>, pgrid, pblock, 0, on, a); else hipLaunchKernelGGL(k_oi_union_pair<false>, pgrid, pblock, 0, on, a);
+        }
+        // (the first pass is persistent: a grid that fills the chip, every wave strides over the tiles)
+        else if(plain) { if(list) hipLaunchKernelGGL((k_oi_union<true, true, 32>), grid, block, 0, on, a); else hipLaunchKernelGGL((k_oi_union<true, false, 32>), UnionCfg<32>::persistent<true>() ? dim3(union_persist_grid<k_oi_union<true, false, 32>>(block.x, nb)) : grid, block, 0, on, a); }
+        else { if(list) hipLaunchKernelGGL((k_oi_union<false, true, 32>), grid, block, 0, on, a); else hipLaunchKernelGGL((k_oi_union<false, false, 32>), grid, block, 0, on, a); }
+        GPP_HIP(hipGetLastError());
+    }
+
+    void launch_union_sp(hipStream_t on) {   // the first pass of a spatially varying Barnes structure: one LU per tile, two tiles per workgroup
+        hipLaunchKernelGGL(k_oi_union_sp<0>, dim3((unsigned)((a.ntiles + 1) / 2)), dim3(128), 0, on, a);
+        GPP_HIP(hipGetLastError());
+    }
+
+    // ================================================= the list passes =================================================
+    // The work items a pass of the tile kernel declines go to a list, and the next pass takes them as smaller items (smaller unions): a tile
+    // as 4 items of 16 cells (level 1), those as 4 items of 4 cells (level 2), or a tile straight to its sixteen 4-cell items (level 3).
+    // What is still left goes to k_oi, one factorisation per distinct selection.  The kernel pair is the scalar one (k_oi_union list form,
+    // k_oi's Cholesky) or, for a spatially varying structure, k_oi_union<true, true, 32, true> and k_oi's pivoted LU.
+    void list_pass(const int level, const int* in, const int* in_count, int* out_l, int* out_count, const long items, hipStream_t on) {
+        a.in_list = in; a.in_count = in_count; a.out_list = out_l; a.out_count = out_count; a.level = level;
+        if(!spatial) { launch_union(items, true, on); return; }
+        const long nb = (items + UnionCfg<32>::WPB - 1) / UnionCfg<32>::WPB;
+        hipLaunchKernelGGL((k_oi_union<true, true, 32, true>), dim3((unsigned)std::min<long>(nb, 0x7fffffffL)), dim3(64 * UnionCfg<32>::WPB), 0, on, a);
+        GPP_HIP(hipGetLastError());
+    }
+    // k_oi over the 4-cell items the list passes left (grid-stride over fb_list3 with a grid of nrun tiles); `run` false: only the arguments
+    void leftover_to_k_oi(const int nrun, const bool run, hipStream_t on) {
+        a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = nrun;
+        if(run) launch_k_oi(spatial, on);
+    }
+    // a short list: every declined tile straight to its sixteen 4-cell items (one pass; the latency of a pass, one lone work item, is what a
+    // short list costs), then what is still left (usually nothing: a small grid keeps the empty launch cheap)
+    void short_form(const int* in, const int* in_count, const long items, const int nrun, const bool run_k_oi, hipStream_t on) {
+        list_pass(3, in, in_count, ws.fb_list3.p, d_fb_count + 2, items, on);
+        leftover_to_k_oi(nrun, run_k_oi, on);
+    }
+    // a long list of n tiles: as 4 items of 16 cells (a list too long for the split to pay is forwarded whole by the kernel), the declined
+    // 16-cell items as 4 items of 4 cells (at most 4 n of them), then what is still left -- with the cells no other cell of their item
+    // shares a selection with parked for k_oi_pairs, unless the list is short against the grid (not worth the pass over every cell's count)
+    void long_form(const int* in, const int* in_count, const long n, const bool run_k_oi, hipStream_t on) {
+        list_pass(1, in, in_count, ws.fb_list2.p, d_fb_count + 1, 4 * n, on);
+        a.parent_count = in_count;
+        list_pass(2, ws.fb_list2.p, d_fb_count + 1, ws.fb_list3.p, d_fb_count + 2, 16 * n, on);
+        const bool pairs = pairs_ok && run_k_oi && 4 * n > a.ntiles;
+        if(pairs) park_on(true, on);
+        leftover_to_k_oi(NRUN_LONG, run_k_oi, on);
+        if(pairs) launch_pairs(on);
+    }
+    // the list passes over the tiles the first pass listed in fb_list, on the library stream
+    void short_passes(const long items) { short_form(ws.fb_list.p, d_fb_count, items, NRUN_SHORT, !skip_k_oi, stream()); }
+    void long_passes(const long n) { long_form(ws.fb_list.p, d_fb_count, n, !skip_k_oi, stream()); }
+    // the list passes over the REMEMBERED list (memo.list; its length on the device is memo.count)
+    void remembered_passes(hipStream_t on) {
+        if(16 * (long)n_remembered <= SHORT_ITEMS) short_form(memo.list.p, memo.count.p, 16 * (long)n_remembered, NRUN_SHORT, !skip_k_oi, on);
+        else long_form(memo.list.p, memo.count.p, n_remembered, !skip_k_oi, on);
+    }
+
+    // ================================================= the phases =================================================
+    // the fields of the call on the device; returns true when the call is done (no observations: the analysis is the background, oi.cpp:189-190)
+    bool stage_fields() {
+        // Host arrays of a large grid (what a gridpp script passes, swig/vector.i:42-55,172-180): the background goes up, and the analysis comes
+        // down, in bands of tile rows beside the first pass when the call takes the tile kernel (`banded` below) -- 64 MB each way over PCIe ran
+        // strictly before and behind a 4.3 ms kernel.  Until that is known the upload is only prepared.
+        band_candidate = !(mem & GPP_MEM_DEVICE) && C >= (1 << 20) && S > 0 && !path_env("GPP_OI_NO_BANDS");
+        band_f64 = (mem & GPP_HOST_F64) != 0;     // float64 host arrays (numpy's default): a band goes up as doubles and is cast on the upload stream
+        if(band_candidate) {
+            f_bg.d = f_bg.staged.get(C);
+            if(bvariance) f_bvar.d = f_bvar.staged.get(C);
+        }
+        else {
+            f_bg.bind(background, C, mem);
+            f_bvar.bind(bvariance, C, mem);
+        }
+        f_out.bind(out, C, mem);
+        f_var.bind(out_variance, C, mem);
+        if(S == 0) {
+            GPP_HIP(hipMemcpyAsync(f_out.d, f_bg.d, sizeof(float) * C, hipMemcpyDeviceToDevice, stream()));
+            if(f_var.d) {
+                if(f_bvar.d) GPP_HIP(hipMemcpyAsync(f_var.d, f_bvar.d, sizeof(float) * C, hipMemcpyDeviceToDevice, stream()));
+                else invalid("bvariance is required when the variance is requested and there are no observations");
+            }
+            f_out.finish(); f_var.finish();
+            GPP_HIP(hipStreamSynchronize(stream()));
+            return true;
+        }
+        f_obs.bind(obs, S, mem);
+        f_ov.bind(obs_variance, S, mem);
+        f_pbg.bind(background_at_points, S, mem);
+        f_bvp.bind(bvariance_at_points, S, mem);
+        return false;
+    }
+    // the observation index, the events, and on the first GPP_ASYNC call of the thread everything a deferred call needs
+    void prepare_runtime() {
+        bgrid->to_device();
+        ix = gpp_build_obs_index(points);
+        if(!ws.e0) { GPP_HIP(hipEventCreate(&ws.e0)); GPP_HIP(hipEventCreate(&ws.e1)); GPP_HIP(hipEventCreate(&ws.eu)); }
+        if((mem & GPP_ASYNC) && !g_aslots[0].h) {
+            // (that first call itself runs synchronously, no memory of its geometry yet): page-locked status slots, events, the two streams
+            // beside the library stream -- milliseconds that must not fall into a later call
+            for(int k = 0; k < ASYNC_SLOTS; k++) {
+                AsyncSlot& sl = g_aslots[k];
+                GPP_HIP(hipHostMalloc((void**)&sl.h, SB * sizeof(unsigned long long), hipHostMallocDefault));
+                GPP_HIP(hipEventCreate(&sl.e0)); GPP_HIP(hipEventCreate(&sl.e1)); GPP_HIP(hipEventCreateWithFlags(&sl.ec, hipEventDisableTiming));
+            }
+            for(int k = 0; k < 2; k++) { GPP_HIP(hipEventCreateWithFlags(&ws.ev_pack[k], hipEventDisableTiming)); GPP_HIP(hipEventCreateWithFlags(&ws.ev_join2[k], hipEventDisableTiming)); }
+            (void)stream2(); (void)stream3();
+        }
+    }
+    // the kernel arguments that do not depend on the workspace slot
+    void fill_args() {
+        N = (max_points > 0 && max_points <= 32) ? 32 : 62;
+        a.gx = bgrid->d_x.p; a.gy = bgrid->d_y.p; a.gz = bgrid->d_z.p; a.gelev = bgrid->d_elev.p; a.glaf = bgrid->d_laf.p;
+        a.bg = f_bg.d; a.bvar = f_bvar.d; a.out = f_out.d; a.out_var = f_var.d;
+        a.C = C; a.ny = bgrid->ny; a.nx = bgrid->nx;
+        a.tiled2d = (bgrid->nx > 0 && (long)bgrid->ny * bgrid->nx == C) ? 1 : 0;
+        a.wshift = 3;
+        if(a.tiled2d) {
+            a.wshift = gpp_tile_wshift(bgrid);
+            const int tw = 1 << a.wshift, th = 64 >> a.wshift;
+            a.tiles_x = (a.nx + tw - 1) / tw; a.ntiles = a.tiles_x * ((a.ny + th - 1) / th);
+        }
+        else { a.tiles_x = 0; a.ntiles = (C + 63) / 64; }
+        a.s.smeta = ix->d_smeta.p; a.s.bin_start = ix->d_bin_start.p; a.ogeo = ix->d_ogeo.p;
+        a.S = S; a.s.axis_a = ix->axis_a; a.s.axis_b = ix->axis_b; a.s.nbx = ix->nbx; a.s.nby = ix->nby;
+        a.s.amin = ix->amin; a.s.bmin = ix->bmin; a.s.inv_s = ix->inv_s;
+        a.s.st = gpp_resolve_structure(st);
+        gpp_bind_field(a.s.st, st, bgrid, points, ws.cell_idx, ws.obs_idx);
+        a.s.max_points = max_points;
+        { const double occ = (double)S / ((double)ix->nbx * ix->nby);
+          const int kk = (max_points > 0 && max_points <= N) ? max_points : N;
+          a.s.q0 = std::max(1, std::min(8, (int)std::ceil(0.5 * (std::sqrt(1.6 * kk / std::max(occ, 1e-3)) - 1.0))));
+          // expected distance of the kk-th nearest observation: k_oi_union looks for its bulk disc below 1.5x that and then
+          // visits rings 0.15x wide
+          const double r_k = std::sqrt(kk / (3.14159265358979 * std::max(occ, 1e-3))) / ix->inv_s;
+          a.s.ring_r0 = (float)(1.5 * r_k); a.s.ring_dr = (float)(0.15 * r_k); }
+        a.allow_extrap = allow_extrapolation ? 1 : 0;
+        a.s.K = (max_points > 0 && max_points <= N) ? max_points : N;
+        a.debug = timing_env("GPP_OI_DEBUG") ? atoi(timing_env("GPP_OI_DEBUG")) : 0;
+        a.tile0 = 0; a.tile_n = a.ntiles;
+    }
+    // which solver and which kernels
+    void plan_kernels() {
+        // Cholesky needs a symmetric positive definite P+R: true for every kernel on distances and for the even vertical / laf
+        // kernels (Barnes, Powerlaw, Linear); Cressman / SOAR / TOAR factors on SIGNED elevation / laf differences make P
+        // non-symmetric (structure.cpp:35-64), and a truncated kernel can be indefinite -> pivoted LU like the reference.
+        auto odd = [](int k) { return k == GPP_SK_CRESSMAN || k == GPP_SK_SOAR || k == GPP_SK_TOAR; };
+        spatial = a.s.st.fh != nullptr;   // per-point length scales: P is not symmetric (corr(p1, p2) uses p1's scales)
+        use_lu = spatial || (a.s.st.v != 0 && odd(a.s.st.kv)) || (a.s.st.w != 0 && odd(a.s.st.kw)) || path_env("GPP_OI_FORCE_LU");
+        plain = a.s.st.kh == GPP_SK_BARNES && a.s.st.kv == GPP_SK_BARNES && a.s.st.kw == GPP_SK_BARNES && !a.s.st.cv;
+        pairs_ok = N == 32 && !spatial && (size_t)C * 128 <= PAIR_PARK_MAX && !path_env("GPP_OI_NO_PAIRS");
+        // one factorisation per tile (k_oi_union) when the system is symmetric and max_points fits the 32-column tile;
+        // the tiles it declines, and every other configuration, run on k_oi (one factorisation per distinct selection)
+        // (With elevation / laf dependent rho the cells of a tile agree less; on smooth terrain most tiles still fit, on
+        //  white-noise elevations none does and the first pass costs a few per cent before the lists hand everything to k_oi.)
+        memo_hit = memo.points_id == points->serial && memo.h == a.s.st.h && memo.v == a.s.st.v && memo.w == a.s.st.w && memo.kh == a.s.st.kh &&
+                   memo.kv == a.s.st.kv && memo.kw == a.s.st.kw && memo.cv == a.s.st.cv && memo.max_points == max_points;
+        const bool memo_says_no = memo_hit && memo.declined > 0.5f;   // more than half of the tiles went to k_oi last time: skip the first pass
+        // (the 62-row form only for 33 <= max_points <= 62: with max_points = 0 a cell may hold more than any tile kernel can)
+        use_union = !use_lu && (N == 32 || (max_points > 32 && max_points <= 62)) && !memo_says_no && !path_env("GPP_OI_NO_UNION");
+        WPB = N == 32 ? UnionCfg<32>::WPB : UnionCfg<64>::WPB;
+        big_ok = N == 62;
+        // spatially varying Barnes structure on the tile path (round 6; no variance output: that needs a second substitution per cell)
+        sp_union = spatial && plain && N == 32 && !f_var.d && !path_env("GPP_OI_NO_SP_UNION");
+    }
+    // the banded host path (see stage_fields): bands or whole arrays, and how the analysis reaches the caller's arrays
+    void plan_bands() {
+        // (one launch per band needs the one-tile-per-wave form of the first pass: a persistent grid would stride over tile0 / tile_n)
+        static_assert(!UnionCfg<32>::persistent<true>(), "the banded host path launches k_oi_union per band of tile rows");
+        banded = band_candidate && a.tiled2d && use_union && N == 32 && !path_env("GPP_OI_PAIR_TILES") && a.ntiles / std::max(a.tiles_x, 1) >= BAND_MIN_TILE_ROWS;
+        if(band_candidate && !banded) {   // whole arrays after all
+            f_bg.bind(background, C, mem);
+            f_bvar.bind(bvariance, C, mem);
+            a.bg = f_bg.d; a.bvar = f_bvar.d;
+        }
+        if(!banded) return;
+        if(band_f64) { wide_bg.get(C); if(bvariance) wide_bv.get(C); }
+        // The analysis comes down per band only into page-locked memory (the Python mirror's result arrays, gpp_host_alloc): a copy into pageable
+        // memory blocks the host until it is done, i.e. until the band's kernel has run -- nothing behind it would be enqueued in time.
+        auto pinned = [](const void* p) { hipPointerAttribute_t at; const bool is = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost; (void)hipGetLastError(); return is; };
+        band_down = pinned(out) && (!out_variance || pinned(out_variance));
         // Round 6, second step: a page-locked result array is WRITTEN BY THE KERNELS THEMSELVES (it is mapped into the device's address space: the
         // stores of a tile travel over PCIe as posted writes while the kernel goes on) -- no download at all.  The per-band device-to-host copies
         // of the first step turned out to be copy KERNELS of the runtime (`__amd_rocclr_copyBuffer`) that do not run beside the first pass but
@@ -1715,482 +1821,333 @@ static int oi_full_impl(gpp_points* bgrid, const float* background, const float*
             }
         }
         if(!ws.ev_band0) GPP_HIP(hipEventCreateWithFlags(&ws.ev_band0, hipEventDisableTiming));
-        for(int b = 0; b < OiWorkspace::MAXB; b++) if(!ws.ev_up[b]) { GPP_HIP(hipEventCreateWithFlags(&ws.ev_up[b], hipEventDisableTiming)); GPP_HIP(hipEventCreateWithFlags(&ws.ev_k[b], hipEventDisableTiming)); }
+        for(int b = 0; b < OiWorkspace::NBAND; b++) if(!ws.ev_up[b]) { GPP_HIP(hipEventCreateWithFlags(&ws.ev_up[b], hipEventDisableTiming)); GPP_HIP(hipEventCreateWithFlags(&ws.ev_k[b], hipEventDisableTiming)); }
+        band_guard.on = true;
     }
-    struct BandGuard {   // whatever ends the call: no copy of it stays in flight on the side streams (into arrays the caller may free)
-        bool on;
-        ~BandGuard() { if(on) { (void)hipStreamSynchronize(stream2()); (void)hipStreamSynchronize(stream3()); (void)hipStreamSynchronize(stream4()); } }
-    } band_guard{banded};
-    bool bands_down_done = false;   // the band downloads of this call are enqueued: the end of the call patches the declined tiles instead of copying everything
-    // cells with more usable observations than the 62-row tile holds are listed: symmetric systems go to k_oi_big (Cholesky, up
-    // to BIG_N observations), what that kernel cannot hold and every listed cell of a non-symmetric or spatially varying
-    // structure to k_oi_huge (pivoted elimination in HBM scratch, no capacity of its own)
-    const bool big_ok = N == 62;
-    auto run_huge = [&](const int* d_list, const int* d_count, const int ncells) {
-        // scratch for the worst case of this call: every observation a candidate, max_points (or all of them) selected
-        size_t kcap = 1; while(kcap < (size_t)S) kcap <<= 1;
-        const size_t ncap = (max_points > 0) ? (size_t)std::min(max_points, S) : (size_t)S;
-        const size_t per_wg = ncap * (ncap + 2) * sizeof(double) + kcap * sizeof(unsigned long long);
-        size_t budget = (size_t)16 << 30;   // 16 GB of the 288 GB for this rarely used path
-        if(path_env("GPP_OI_HUGE_BUDGET_MB")) budget = (size_t)atol(path_env("GPP_OI_HUGE_BUDGET_MB")) << 20;
-        if(per_wg > budget) runtime("optimal_interpolation: a grid point may select more observations than the scratch budget of the general kernel holds (set max_points, or raise GPP_OI_HUGE_BUDGET_MB)");
-        const int nwg = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)ncells, 512), budget / per_wg));
-        a.huge_kcap = (int)kcap; a.huge_ncap = (int)ncap;
-        a.huge_keys = ws.huge_keys.get((size_t)nwg * kcap);
-        a.huge_mat = ws.huge_mat.get((size_t)nwg * ncap * (ncap + 2));
-        if(spatial) hipLaunchKernelGGL(k_oi_huge<true>, dim3(nwg), dim3(256), 0, stream(), a, d_list, d_count);
-        else hipLaunchKernelGGL(k_oi_huge<false>, dim3(nwg), dim3(256), 0, stream(), a, d_list, d_count);
-        GPP_HIP(hipGetLastError());
-    };
-    bool ran_union = false, ran_overlap = false;
-    // spatially varying Barnes structure on the tile path (round 6; no variance output: that needs a second substitution per cell)
-    const bool sp_union = spatial && plain && N == 32 && !f_var.d && !path_env("GPP_OI_NO_SP_UNION");
-    bool sp_failed = false, ran_sp = false;
-    const bool async_req = (mem & GPP_ASYNC) && (mem & GPP_MEM_DEVICE) && !path_env("GPP_OI_NO_ASYNC");
-    int async_slot = -1;
-    // `steady`: a GPP_ASYNC call that will take the overlapped branch below (the conditions of `overlap`): it is deferred, and its observation
+    // `steady`: a GPP_ASYNC call that will take the overlapped branch of run_union (the conditions of `overlap`): it is deferred, and its observation
     // block is packed on the second stream, AHEAD of the first pass of the call before it.  Every other call first completes the deferred calls
     // of this thread (they share the workspace) and packs on the library stream.
-    // (either the geometry remembers a list of declined tiles, or its last call declined none and left nothing to k_oi)
-    bool steady = async_req && N == 32 && !f_out.host && !f_var.host && use_union && !use_lu && memo_hit && !path_env("GPP_OI_NO_OVERLAP") &&
-                  ((memo.nlist > 0 && memo.list_ntiles == a.ntiles) || (memo.nlist == 0 && memo.declined == 0.0f && memo.leftover == 0));
-    if(steady) {
-        async_slot = (int)(g_async_seq++ % ASYNC_SLOTS);
-        for(const PendingOi& q : g_pending) if(!q.done && q.slot == async_slot) { async_slot = -1; break; }   // (all slots in flight: this call runs synchronously)
-        if(async_slot < 0) steady = false;
+    void plan_deferral() {
+        const bool async_req = (mem & GPP_ASYNC) && (mem & GPP_MEM_DEVICE) && !path_env("GPP_OI_NO_ASYNC");
+        // (either the geometry remembers a list of declined tiles, or its last call declined none and left nothing to k_oi)
+        steady = async_req && N == 32 && !f_out.host && !f_var.host && use_union && !use_lu && memo_hit && !path_env("GPP_OI_NO_OVERLAP") &&
+                 ((memo.nlist > 0 && memo.list_ntiles == a.ntiles) || (memo.nlist == 0 && memo.declined == 0.0f && memo.leftover == 0));
+        if(steady) {
+            async_slot = (int)(g_async_seq++ % ASYNC_SLOTS);
+            for(const PendingOi& q : g_pending) if(!q.done && q.slot == async_slot) { async_slot = -1; break; }   // (all slots in flight: this call runs synchronously)
+            if(async_slot < 0) steady = false;
+        }
     }
-    if(!steady) {
-        gpp_oi_drain_pending();
-        g_stats = gpp_oi_stats();      // (a re-run inside the drain left its own)
-        g_stats.cells = C;
+    // The workspace of this call -- the slot's observation block and status block -- is bound HERE, behind the decision whether the call is deferred:
+    // a call that is not completes the deferred calls of the thread first, and one of those may need its synchronous re-run, i.e. a nested
+    // oi_full_impl that flips the slot, reallocates the slot buffers for its own observation count and overwrites the statistics (ADVICE round 5).
+    // Nothing of the workspace is touched, and no pointer into it is held, before that drain.
+    void drain_and_bind_workspace() {
+        if(!steady) {
+            gpp_oi_drain_pending();
+            g_stats = gpp_oi_stats();      // (a re-run inside the drain left its own)
+            g_stats.cells = C;
+        }
+        wsl = ws.slot ^= 1;
+        pgeo_b = &ws.pgeo_s[wsl]; oaux_b = &ws.oaux_s[wsl]; saux_b = &ws.saux_s[wsl]; status_b = &ws.status_s[wsl];
+        pgeo_b->get(S); oaux_b->get(S); saux_b->get(S); status_b->get(SB);
+        if(!ws.h_status) GPP_HIP(hipHostMalloc((void**)&ws.h_status, (SB + 1) * sizeof(unsigned long long), hipHostMallocDefault));
+        h_ints = reinterpret_cast<const int*>(ws.h_status);
+        d_ints = reinterpret_cast<int*>(status_b->p);
+        d_fb_count = d_ints + 1; d_big_count = d_ints + 4; d_huge_count = d_ints + 5;
+        d_counters = status_b->p + 8;
+        a.s.pgeo = pgeo_b->p; a.oaux = oaux_b->p; a.saux = saux_b->p;
+        a.s.scan_stats = timing_env("GPP_SCAN_STATS") ? d_counters + 2 : nullptr;
+        a.err = d_ints; a.counters = d_counters; a.tail_count = d_ints + 6;
+        if(big_ok) {
+            ws.big_list.get((size_t)C);
+            a.big_list = ws.big_list.p; a.big_count = d_big_count;
+        }
+        if(!steady) { launch_pack(stream()); GPP_HIP(hipEventRecord(ws.e0, stream())); }
     }
-    ws.slot ^= 1;
-    wsl = ws.slot;
-    pgeo_b = &ws.pgeo_s[wsl]; oaux_b = &ws.oaux_s[wsl]; saux_b = &ws.saux_s[wsl]; status_b = &ws.status_s[wsl];
-    pgeo_b->get(S); oaux_b->get(S); saux_b->get(S);
-    status_b->get(SB);
-    if(!ws.h_status) GPP_HIP(hipHostMalloc((void**)&ws.h_status, (SB + 1) * sizeof(unsigned long long), hipHostMallocDefault));
-    h_ints = reinterpret_cast<const int*>(ws.h_status);
-    d_ints = reinterpret_cast<int*>(status_b->p);
-    d_err = d_ints; d_fb_count = d_ints + 1; d_big_count = d_ints + 4; d_huge_count = d_ints + 5;
-    d_counters = status_b->p + 8;
-    a.s.pgeo = pgeo_b->p; a.oaux = oaux_b->p; a.saux = saux_b->p;
-    a.s.scan_stats = timing_env("GPP_SCAN_STATS") ? d_counters + 2 : nullptr;
-    a.err = d_err; a.counters = d_counters; a.tail_count = d_ints + 6;
-    if(big_ok) {
-        ws.big_list.get((size_t)C);
-        a.big_list = ws.big_list.p; a.big_count = d_big_count;
+
+    // The first pass over all tiles -- on the banded host path as one launch per band of tile rows: the band's rows of the background
+    // (and of its variance) go up on the second stream, the band's launch waits for them, the band's rows of the analysis come down on
+    // the third behind it.  Bands: 1 : 2 : 3 : 3 : 2 : 1 of the tile rows -- a short first upload and a short last download are what is
+    // not hidden; every launch costs its last, partly filled round of workgroups (~45 us).  With at least BAND_MIN_TILE_ROWS tile rows
+    // every band holds one.  The tiles the first pass leaves to the list passes are final only behind those: their cells are patched
+    // at the end of the call (deliver).
+    void first_pass() {   // on the library stream
+        a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
+        if(!banded) launch_union(a.ntiles, false, stream());
+        else banded_first_pass();
+        GPP_HIP(hipEventRecord(ws.eu, stream()));   // (eu: the end of the first pass, for the statistics)
     }
-    if(!steady) { launch_pack(stream()); GPP_HIP(hipEventRecord(ws.e0, stream())); }
-    int overlap_left = 0, overlap_new = 0, overlap_remembered = 0;
-    const int* patch_l0 = nullptr; const int* patch_l1 = nullptr;
-    int patch_n0 = 0, patch_n1 = 0;
-    for(int attempt = 0; attempt < 2; ++attempt) {
-        a.in_list = nullptr; a.in_count = nullptr; a.out_list = nullptr; a.out_count = nullptr; a.nrun = a.ntiles;
-        ran_union = false; ran_overlap = false; ran_sp = false;
-        if(use_union && !use_lu) {
-            // worst case per list: every tile declined and split into 4 (level 1) resp. 16 (level 2) items
-            const int SHORT_ITEMS = 3072;   // as many work items as the chip holds waves of this kernel
-            // (the short-list pass writes up to 16 entries per declined tile, SHORT_ITEMS at most, whatever the number of tiles)
-            ws.fb_list.get((size_t)a.ntiles); ws.fb_list2.get(2 * (size_t)a.ntiles + 64);
-            ws.fb_list3.get(std::max<size_t>(4 * (size_t)a.ntiles, (size_t)SHORT_ITEMS) + 64);
-            const dim3 block(64 * UnionCfg<32>::WPB);
-            const bool pair_tiles = path_env("GPP_OI_PAIR_TILES") != nullptr;   // (off: measured 3 % slower than one tile per wave -- the waiting wave of a pair)
-            a.pair_solo = path_env("GPP_OI_PAIR_SOLO") ? 1 : 0;
-            auto launch_union = [&](const long items, const bool list) {   // one wave per work item
-                const long nb = (items + WPB - 1) / WPB;
-                const dim3 grid((unsigned)std::min<long>(nb, 0x7fffffffL));
-                // (max_points 33 .. 48: the 48-column form at two waves per SIMD; 49 .. 62: the 64-column form)
-                if(N != 32 && max_points <= 48 && !path_env("GPP_OI_NO_UNION48")) gpp_launch_union48(a, grid.x, plain, list, cur);
-                else if(N != 32) gpp_launch_union64(a, grid.x, plain, list, cur);
-                // (round 6: the first pass of the 32-column form shares one factorisation between the two tiles of a pair)
-                else if(!list && pair_tiles) {
-                    const dim3 pgrid((unsigned)std::min<long>(union_pair_count(a), 0x7fffffffL)), pblock(128);
-                    if(plain) hipLaunchKernelGGL(k_oi_union_pair<true>, pgrid, pblock, 0, cur, a); else hipLaunchKernelGGL(k_oi_union_pair<false>, pgrid, pblock, 0, cur, a);
-                }
-                // (the first pass is persistent: a grid that fills the chip, every wave strides over the tiles)
-                else if(plain) { if(list) hipLaunchKernelGGL((k_oi_union<true, true, 32>), grid, block, 0, cur, a); else hipLaunchKernelGGL((k_oi_union<true, false, 32>), UnionCfg<32>::persistent<true>() ? dim3(union_persist_grid<k_oi_union<true, false, 32>>(block.x, nb)) : grid, block, 0, cur, a); }
-                else { if(list) hipLaunchKernelGGL((k_oi_union<false, true, 32>), grid, block, 0, cur, a); else hipLaunchKernelGGL((k_oi_union<false, false, 32>), grid, block, 0, cur, a); }
+    void banded_first_pass() {
+        static constexpr int share[OiWorkspace::NBAND] = {1, 2, 3, 3, 2, 1}, total_share = 12;
+        const int th = 64 >> a.wshift, trows = a.ntiles / a.tiles_x;
+        const hipStream_t sUp = stream2(), sDown = stream3();
+        GPP_HIP(hipEventRecord(ws.ev_band0, stream()));
+        GPP_HIP(hipStreamWaitEvent(sUp, ws.ev_band0, 0));    // (the staging buffers' previous readers are behind the library stream)
+        int ty0 = 0, acc = 0;
+        for(int b = 0; b < OiWorkspace::NBAND; b++) {
+            acc += share[b];
+            const int ty1 = b == OiWorkspace::NBAND - 1 ? trows : std::max(ty0 + 1, (int)((long)trows * acc / total_share));
+            const size_t r0 = (size_t)ty0 * th, r1 = std::min<size_t>((size_t)a.ny, (size_t)ty1 * th);
+            const size_t off = r0 * a.nx, cnt = (r1 - r0) * a.nx;
+            auto up = [&](const float* src, const float* dst, Staged<double>& wide) {
+                if(!band_f64) { GPP_HIP(hipMemcpyAsync(const_cast<float*>(dst) + off, src + off, cnt * sizeof(float), hipMemcpyHostToDevice, sUp)); return; }
+                // (the rounding of the reference's PyArray_CastToType, swig/vector.i:42-55, on the device: k_stage_f64)
+                GPP_HIP(hipMemcpyAsync(wide.p + off, reinterpret_cast<const double*>(src) + off, cnt * sizeof(double), hipMemcpyHostToDevice, sUp));
+                hipLaunchKernelGGL(k_stage_f64, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, sUp, (const double*)(wide.p + off), cnt, const_cast<float*>(dst) + off);
                 GPP_HIP(hipGetLastError());
             };
-            // The first pass over all tiles -- on the banded host path as one launch per band of tile rows: the band's rows of the background
-            // (and of its variance) go up on the second stream, the band's launch waits for them, the band's rows of the analysis come down on
-            // the third behind it.  Bands: 1 : 2 : 3 : 3 : 2 : 1 of the tile rows -- a short first upload and a short last download are what is
-            // not hidden; every launch costs its last, partly filled round of workgroups (~45 us).  The tiles the first pass leaves to the
-            // list passes are final only behind those: their cells are patched at the end of the call (k_gather_tiles).
-            auto first_pass = [&]() {
-                if(!banded) { launch_union(a.ntiles, false); return; }
-                // (GPP_OI_BAND_SHARES="a,b,c,...": another split for A/B runs, at most MAXB bands)
-                int share[OiWorkspace::MAXB] = {1, 2, 3, 3, 2, 1, 0, 0};
-                int nband = 6, total_share = 12;
-                if(const char* e = path_env("GPP_OI_BAND_SHARES")) {
-                    nband = 0; total_share = 0;
-                    for(const char* q = e; *q && nband < OiWorkspace::MAXB; ) { const int v = atoi(q); if(v > 0) { share[nband++] = v; total_share += v; } while(*q && *q != ',') q++; if(*q == ',') q++; }
-                    if(nband == 0) { nband = 1; share[0] = 1; total_share = 1; }
-                }
-                const int th = 64 >> a.wshift, trows = a.ntiles / a.tiles_x;
-                const hipStream_t sUp = stream2(), sDown = stream3(), sOdd = stream4();
-                const bool two_streams = path_env("GPP_OI_BANDS_TWO_STREAMS") != nullptr;
-                // (the bands alternate between the library stream and a fourth one: the last round of a band's workgroups fills a fraction of the
-                //  chip, and in one stream the next band waits behind it -- six times ~45 us)
-                GPP_HIP(hipEventRecord(ws.ev_band0, stream()));
-                GPP_HIP(hipStreamWaitEvent(sUp, ws.ev_band0, 0));    // (the staging buffers' previous readers are behind the library stream)
-                GPP_HIP(hipStreamWaitEvent(sOdd, ws.ev_band0, 0));   // (and so is the status block the kernels count in, cleared by k_pack_obs)
-                int ty0 = 0, acc = 0;
-                for(int b = 0; b < nband; b++) {
-                    acc += share[b];
-                    const int ty1 = b == nband - 1 ? trows : std::max(ty0 + 1, (int)((long)trows * acc / total_share));
-                    const size_t r0 = (size_t)ty0 * th, r1 = std::min<size_t>((size_t)a.ny, (size_t)ty1 * th);
-                    const size_t off = r0 * a.nx, cnt = (r1 - r0) * a.nx;
-                    auto up = [&](const float* src, const float* dst, Staged<double>& wide) {
-                        if(!band_f64) { GPP_HIP(hipMemcpyAsync(const_cast<float*>(dst) + off, src + off, cnt * sizeof(float), hipMemcpyHostToDevice, sUp)); return; }
-                        // (the rounding of the reference's PyArray_CastToType, swig/vector.i:42-55, on the device: k_stage_f64)
-                        GPP_HIP(hipMemcpyAsync(wide.p + off, reinterpret_cast<const double*>(src) + off, cnt * sizeof(double), hipMemcpyHostToDevice, sUp));
-                        hipLaunchKernelGGL(k_stage_f64, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, sUp, (const double*)(wide.p + off), cnt, const_cast<float*>(dst) + off);
-                        GPP_HIP(hipGetLastError());
-                    };
-                    up(background, f_bg.d, wide_bg);
-                    if(bvariance) up(bvariance, f_bvar.d, wide_bv);
-                    GPP_HIP(hipEventRecord(ws.ev_up[b], sUp));
-                    const hipStream_t sK = ((b & 1) && two_streams) ? sOdd : stream();
-                    GPP_HIP(hipStreamWaitEvent(sK, ws.ev_up[b], 0));
-                    a.tile0 = ty0 * a.tiles_x; a.tile_n = (ty1 - ty0) * a.tiles_x;
-                    cur = sK;
-                    launch_union(a.tile_n, false);
-                    cur = stream();
-                    GPP_HIP(hipEventRecord(ws.ev_k[b], sK));
-                    if(band_down) {
-                        GPP_HIP(hipStreamWaitEvent(sDown, ws.ev_k[b], 0));
-                        GPP_HIP(hipMemcpyAsync(out + off, f_out.d + off, cnt * sizeof(float), hipMemcpyDeviceToHost, sDown));
-                        if(out_variance) GPP_HIP(hipMemcpyAsync(out_variance + off, f_var.d + off, cnt * sizeof(float), hipMemcpyDeviceToHost, sDown));
-                    }
-                    ty0 = ty1;
-                }
-                for(int b = std::max(0, nband - 2); b < nband; b++) GPP_HIP(hipStreamWaitEvent(stream(), ws.ev_k[b], 0));   // (what follows on the library stream -- the list passes, the read-back -- is behind every band, whichever stream ran the last ones)
-                a.tile0 = 0; a.tile_n = a.ntiles;
-                bands_down_done = band_down;
-            };
-            // The tiles it declined.  The usual case is a short list (or none): it is taken WITHOUT asking the host how long it
-            // is -- the short-list pass and the k_oi pass behind it are launched with fixed small grids and read the lengths
-            // on the device; a list too long for that grid is left untouched by both and handled after the one read-back of
-            // the call.  (A host round trip here cost ~25 us per call.)  When the last call with this geometry had a long
-            // list, the host asks first, as the two-level passes need its length for their grids anyway.
-            // (a geometry whose last call left nothing to k_oi: not even its empty launch; the read-back says if that was wrong)
-            const bool skip_k_oi = memo_hit && memo.leftover == 0;
-            auto short_passes = [&](const int nitems) {
-                // every declined tile straight to its sixteen 4-cell items (one pass; the latency of a pass, one lone work
-                // item, is what a short list costs)
-                a.in_list = ws.fb_list.p; a.in_count = d_fb_count; a.out_list = ws.fb_list3.p; a.out_count = d_fb_count + 2; a.level = 3;
-                launch_union(nitems, true);
-                // what is still left, one factorisation per distinct selection (grid-stride over the list)
-                a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 128;
-                if(!skip_k_oi) launch_k_oi(false);   // (usually nothing is left: a small grid keeps the empty launch cheap)
-            };
-            auto long_passes = [&](const int n1) {
-                // pass 2: the declined tiles as 4 items of 16 cells (smaller unions); a list too long for the split to pay is
-                // forwarded whole by the kernel
-                a.in_list = ws.fb_list.p; a.in_count = d_fb_count; a.out_list = ws.fb_list2.p; a.out_count = d_fb_count + 1; a.level = 1;
-                launch_union(4 * (long)n1, true);
-                // pass 3: the declined 16-cell items as 4 items of 4 cells (at most 4 n1 of them)
-                a.in_list = ws.fb_list2.p; a.in_count = d_fb_count + 1; a.out_list = ws.fb_list3.p; a.out_count = d_fb_count + 2; a.level = 2;
-                a.parent_count = d_fb_count;
-                launch_union(16 * (long)n1, true);
-                // pass 4: what is still left, one factorisation per distinct selection (grid-stride over the list)
-                a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 512;
-                const bool pairs = pairs_ok && !skip_k_oi && 4 * (long)n1 > a.ntiles;   // (a short list: not worth the pass over every cell's count)
-                if(pairs) park_on(true);
-                if(!skip_k_oi) launch_k_oi(false);
-                if(pairs) launch_pairs();
-            };
-            const bool expect_long = memo_hit && 16.0 * (double)memo.declined * (double)a.ntiles > (double)SHORT_ITEMS;
-            // Round 5: the list passes BESIDE the first pass.  The tiles a geometry declines do not depend on the values (only on the
-            // coordinates, the structure and which observations are usable), so the list of the last call is this call's list: it is kept
-            // with the geometry (memo.list, one flag byte per tile), the first pass leaves the flagged tiles alone, and the list passes over
-            // the REMEMBERED list are launched on a second stream at the same time -- their latency (one lone work item per pass: 55 us of a
-            // 0.62 ms step at 500 rows per rank, 146 us of the 4.46 ms headline) disappears behind the first pass.  Nothing depends on the
-            // memory being right: a flagged tile is solved by the list passes whatever the first pass would have made of it (all paths give
-            // the same bits), and a tile the first pass declines that was NOT flagged arrives in its out_list as before, is taken by the serial
-            // passes after the read-back and joins the remembered list.
-            const bool overlap = memo_hit && memo.nlist > 0 && memo.list_ntiles == a.ntiles && !path_env("GPP_OI_NO_OVERLAP");
-            const int n_remembered = overlap ? memo.nlist : 0;
-            const int* const d_mcount = memo.count.p;
-            auto remembered_passes = [&]() {   // the list passes over the REMEMBERED list, on `cur`
-                if(16 * (long)n_remembered <= SHORT_ITEMS) {
-                    a.in_list = memo.list.p; a.in_count = d_mcount; a.out_list = ws.fb_list3.p; a.out_count = d_fb_count + 2; a.level = 3;
-                    launch_union(16 * (long)n_remembered, true);
-                    a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 128;
-                    if(!skip_k_oi) launch_k_oi(false);
-                }
-                else {
-                    a.in_list = memo.list.p; a.in_count = d_mcount; a.out_list = ws.fb_list2.p; a.out_count = d_fb_count + 1; a.level = 1;
-                    launch_union(4 * (long)n_remembered, true);
-                    a.in_list = ws.fb_list2.p; a.in_count = d_fb_count + 1; a.out_list = ws.fb_list3.p; a.out_count = d_fb_count + 2; a.level = 2;
-                    a.parent_count = d_mcount;
-                    launch_union(16 * (long)n_remembered, true);
-                    a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 512;
-                    const bool pairs = pairs_ok && !skip_k_oi && 4 * (long)n_remembered > a.ntiles;
-                    if(pairs) park_on(true);
-                    if(!skip_k_oi) launch_k_oi(false);
-                    if(pairs) launch_pairs();
-                }
-            };
-            auto defer = [&]() -> int {
-                // GPP_ASYNC in the steady state.  Three streams: B packs this call's observation block and runs its list passes -- AHEAD of the
-                // first pass of the call before it, which still runs on A (the blocks and status blocks alternate between two workspace
-                // slots) --, A runs the first passes back to back, C copies each call's status block into its page-locked slot once its first
-                // pass (A) and its list passes (B) are done.  Nothing here waits for the host, and the host waits for nothing here.
-                AsyncSlot& sl = g_aslots[async_slot];
-                const hipStream_t sA = stream(), sB = stream2(), sC = stream3();
-                // (the buffers of this workspace slot: the deferred call that used them last must have finished its first pass and its status copy)
-                if(ws.slot_e1[wsl]) GPP_HIP(hipStreamWaitEvent(sB, ws.slot_e1[wsl], 0));
-                if(ws.slot_ec[wsl]) GPP_HIP(hipStreamWaitEvent(sB, ws.slot_ec[wsl], 0));
-                launch_pack(sB);
-                GPP_HIP(hipEventRecord(ws.ev_pack[wsl], sB));
-                cur = sB;
-                if(n_remembered > 0) remembered_passes();
-                GPP_HIP(hipEventRecord(ws.ev_join2[wsl], sB));
-                cur = sA;
-                GPP_HIP(hipStreamWaitEvent(sA, ws.ev_pack[wsl], 0));
-                GPP_HIP(hipEventRecord(sl.e0, sA));
-                a.skip_flags = n_remembered > 0 ? memo.flags.p : nullptr;
-                a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
-                launch_union(a.ntiles, false);
-                a.skip_flags = nullptr;
-                GPP_HIP(hipEventRecord(sl.e1, sA));      // (one timestamp behind the first pass: every command between two first passes is a gap on the GPU)
-                GPP_HIP(hipStreamWaitEvent(sC, sl.e1, 0));
-                GPP_HIP(hipStreamWaitEvent(sC, ws.ev_join2[wsl], 0));
-                GPP_HIP(hipMemcpyAsync(sl.h, status_b->p, SB * sizeof(unsigned long long), hipMemcpyDeviceToHost, sC));
-                GPP_HIP(hipEventRecord(sl.ec, sC));
-                ws.slot_e1[wsl] = sl.e1; ws.slot_ec[wsl] = sl.ec;
-                PendingOi pc;
-                pc.bgrid = bgrid; pc.background = background; pc.bvariance = bvariance; pc.points = points; pc.obs = obs; pc.obs_variance = obs_variance;
-                pc.background_at_points = background_at_points; pc.bvariance_at_points = bvariance_at_points; pc.st = *st; pc.max_points = max_points;
-                pc.allow_extrapolation = allow_extrapolation; pc.out = out; pc.out_variance = out_variance; pc.mem = mem & ~GPP_ASYNC;
-                pc.slot = async_slot; pc.n_remembered = n_remembered; pc.skip_k_oi = skip_k_oi;
-                pc.stats = g_stats;
-                g_pending.push_back(pc);
-                return GPP_OK;
-            };
-            if(overlap) {
-                if(!ws.ev_fork) { GPP_HIP(hipEventCreateWithFlags(&ws.ev_fork, hipEventDisableTiming)); GPP_HIP(hipEventCreateWithFlags(&ws.ev_join, hipEventDisableTiming)); }
-                if(steady) return defer();
-                GPP_HIP(hipEventRecord(ws.ev_fork, stream()));             // (behind k_pack_obs, which also cleared the status block)
-                a.skip_flags = memo.flags.p;
-                a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
-                first_pass();                                              // pass 1 on the library stream
-                GPP_HIP(hipEventRecord(ws.eu, stream()));
-                a.skip_flags = nullptr;
-                cur = stream2();
-                GPP_HIP(hipStreamWaitEvent(cur, ws.ev_fork, 0));
-                remembered_passes();
-                GPP_HIP(hipEventRecord(ws.ev_join, cur));
-                cur = stream();
-                GPP_HIP(hipStreamWaitEvent(cur, ws.ev_join, 0));
-                GPP_HIP(hipEventRecord(ws.e1, stream()));
-                fetch();
-                if(skip_k_oi && h_ints[3] > 0) {   // 4-cell items for k_oi after all (before the counts below are cleared)
-                    a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 512;
-                    launch_k_oi(false);
-                }
-                const int n_new = h_ints[1];
-                const int left_remembered = h_ints[3];
-                if(n_new > 0) {   // tiles the first pass declined that the memory did not hold: the serial passes, as without the overlap
-                    GPP_HIP(hipMemsetAsync(d_fb_count + 1, 0, 2 * sizeof(int), stream()));
-                    if(16 * (long)n_new > SHORT_ITEMS) { long_passes(n_new); if(skip_k_oi) launch_k_oi(false); }
-                    else {
-                        a.in_list = ws.fb_list.p; a.in_count = d_fb_count; a.out_list = ws.fb_list3.p; a.out_count = d_fb_count + 2; a.level = 3;
-                        launch_union(16 * (long)n_new, true);
-                        a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 512;
-                        launch_k_oi(false);
-                    }
-                }
-                if(n_new > 0 || (skip_k_oi && left_remembered > 0)) {
-                    GPP_HIP(hipEventRecord(ws.e1, stream()));
-                    fetch();
-                }
-                overlap_left = left_remembered + (n_new > 0 ? h_ints[3] : 0);
-                overlap_new = n_new; overlap_remembered = n_remembered; ran_overlap = true;
+            up(background, f_bg.d, wide_bg);
+            if(bvariance) up(bvariance, f_bvar.d, wide_bv);
+            GPP_HIP(hipEventRecord(ws.ev_up[b], sUp));
+            GPP_HIP(hipStreamWaitEvent(stream(), ws.ev_up[b], 0));
+            a.tile0 = ty0 * a.tiles_x; a.tile_n = (ty1 - ty0) * a.tiles_x;
+            launch_union(a.tile_n, false, stream());
+            GPP_HIP(hipEventRecord(ws.ev_k[b], stream()));
+            if(band_down) {
+                GPP_HIP(hipStreamWaitEvent(sDown, ws.ev_k[b], 0));
+                GPP_HIP(hipMemcpyAsync(out + off, f_out.d + off, cnt * sizeof(float), hipMemcpyDeviceToHost, sDown));
+                if(out_variance) GPP_HIP(hipMemcpyAsync(out_variance + off, f_var.d + off, cnt * sizeof(float), hipMemcpyDeviceToHost, sDown));
             }
-            else if(!expect_long) {
-                if(steady) return defer();      // (nothing declined the last time: the first pass alone, deferred)
-                a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
-                first_pass();                                              // pass 1: every tile
-                GPP_HIP(hipEventRecord(ws.eu, stream()));
-                // (a geometry that declined no tile the last time: not even the two empty launches; the read-back says if that was wrong)
-                const bool expect_none = memo_hit && memo.declined == 0.0f;
-                if(!expect_none) short_passes(SHORT_ITEMS);
-                GPP_HIP(hipEventRecord(ws.e1, stream()));
-                fetch();
-                const int n1 = h_ints[1];
-                if(16 * (long)n1 > SHORT_ITEMS || (expect_none && n1 > 0)) {   // a long list after all (or an unexpected one): nothing has touched it yet
-                    if(16 * (long)n1 > SHORT_ITEMS) long_passes(n1); else short_passes(16 * n1);
-                    GPP_HIP(hipEventRecord(ws.e1, stream()));
-                    fetch();
-                }
-            }
-            else {
-                a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
-                first_pass();                                              // pass 1: every tile
-                GPP_HIP(hipEventRecord(ws.eu, stream()));
-                // A long list is expected, and the same geometry declines the same tiles: the two-level passes are launched for the length
-                // of the last call (+ 1/8) without asking the host first -- they read the true length on the device.  Only if MORE tiles were
-                // declined than those grids hold (other observations turned invalid) are the passes run again with the true length: every
-                // pass writes the same values for the cells it handles, so that is merely slower.
-                const int cap = path_env("GPP_OI_LONG_CAP") ? atoi(path_env("GPP_OI_LONG_CAP")) : memo.n1 + memo.n1 / 8 + 64;   // (the override: tests force the second run)
-                // (the statistics counters as the first pass left them: a second run of the list passes must not count its cells twice)
-                ws.status_snap.get(SB);
-                GPP_HIP(hipMemcpyAsync(ws.status_snap.p, d_counters, (SB - 8) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream()));
-                long_passes(cap);
-                GPP_HIP(hipEventRecord(ws.e1, stream()));
-                fetch();
-                const int n1 = h_ints[1];
-                if(n1 > cap) {
-                    GPP_HIP(hipMemsetAsync(d_fb_count + 1, 0, 2 * sizeof(int), stream()));
-                    GPP_HIP(hipMemcpyAsync(d_counters, ws.status_snap.p, (SB - 8) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream()));
-                    long_passes(n1);
-                    GPP_HIP(hipEventRecord(ws.e1, stream()));
-                    fetch();
-                }
-            }
-            if(!overlap && skip_k_oi && h_ints[3] > 0) {   // 4-cell items for k_oi after all
-                a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 512;
-                launch_k_oi(false);
-                GPP_HIP(hipEventRecord(ws.e1, stream()));
-                fetch();
-            }
-            ran_union = true;
+            ty0 = ty1;
         }
-        else if(sp_union && !sp_failed) {
-            // spatially varying Barnes structure: one LU per tile (k_oi_union_sp), the tiles it declines to k_oi's pivoted LU as whole tiles
-            ws.fb_list.get((size_t)a.ntiles);
-            a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
-            a.tile0 = 0; a.tile_n = a.ntiles;
-            hipLaunchKernelGGL(k_oi_union_sp<0>, dim3((unsigned)((a.ntiles + 1) / 2)), dim3(128), 0, stream(), a);
-            GPP_HIP(hipGetLastError());
-            GPP_HIP(hipEventRecord(ws.eu, stream()));
-            GPP_HIP(hipEventRecord(ws.e1, stream()));
-            fetch();
-            const int n1 = h_ints[1];
-            if(n1 > 0) {
-                // the declined tiles as smaller items (smaller unions), as on the scalar path: a short list straight to its 4-cell items, a long one
-                // through the 16-cell level; what is still left to k_oi's pivoted LU
-                ws.fb_list2.get(2 * (size_t)a.ntiles + 64);
-                ws.fb_list3.get(std::max<size_t>(4 * (size_t)a.ntiles, (size_t)3072) + 64);
-                auto launch_sp_list = [&](const long items) {
-                    const long nb = (items + UnionCfg<32>::WPB - 1) / UnionCfg<32>::WPB;
-                    hipLaunchKernelGGL((k_oi_union<true, true, 32, true>), dim3((unsigned)std::min<long>(nb, 0x7fffffffL)), dim3(64 * UnionCfg<32>::WPB), 0, stream(), a);
-                    GPP_HIP(hipGetLastError());
-                };
-                if(16 * (long)n1 <= 3072) {
-                    a.in_list = ws.fb_list.p; a.in_count = d_fb_count; a.out_list = ws.fb_list3.p; a.out_count = d_fb_count + 2; a.level = 3;
-                    launch_sp_list(16 * (long)n1);
-                }
-                else {
-                    a.in_list = ws.fb_list.p; a.in_count = d_fb_count; a.out_list = ws.fb_list2.p; a.out_count = d_fb_count + 1; a.level = 1;
-                    launch_sp_list(4 * (long)n1);
-                    a.in_list = ws.fb_list2.p; a.in_count = d_fb_count + 1; a.out_list = ws.fb_list3.p; a.out_count = d_fb_count + 2; a.level = 2;
-                    a.parent_count = d_fb_count;
-                    launch_sp_list(16 * (long)n1);
-                }
-                a.in_list = ws.fb_list3.p; a.in_count = d_fb_count + 2; a.out_list = nullptr; a.out_count = nullptr; a.nrun = 4 * 512;
-                launch_k_oi(true);
-                GPP_HIP(hipEventRecord(ws.e1, stream()));
-                fetch();
-            }
-            ran_sp = true;
+        a.tile0 = 0; a.tile_n = a.ntiles;
+        bands_down_done = band_down;
+    }
+    // GPP_ASYNC in the steady state.  Three streams: B packs this call's observation block and runs its list passes -- AHEAD of the
+    // first pass of the call before it, which still runs on A (the blocks and status blocks alternate between two workspace
+    // slots) --, A runs the first passes back to back, C copies each call's status block into its page-locked slot once its first
+    // pass (A) and its list passes (B) are done.  Nothing here waits for the host, and the host waits for nothing here.
+    void defer() {
+        AsyncSlot& sl = g_aslots[async_slot];
+        const hipStream_t sA = stream(), sB = stream2(), sC = stream3();
+        // (the buffers of this workspace slot: the deferred call that used them last must have finished its first pass and its status copy)
+        if(ws.slot_e1[wsl]) GPP_HIP(hipStreamWaitEvent(sB, ws.slot_e1[wsl], 0));
+        if(ws.slot_ec[wsl]) GPP_HIP(hipStreamWaitEvent(sB, ws.slot_ec[wsl], 0));
+        launch_pack(sB);
+        GPP_HIP(hipEventRecord(ws.ev_pack[wsl], sB));
+        if(n_remembered > 0) remembered_passes(sB);
+        GPP_HIP(hipEventRecord(ws.ev_join2[wsl], sB));
+        GPP_HIP(hipStreamWaitEvent(sA, ws.ev_pack[wsl], 0));
+        GPP_HIP(hipEventRecord(sl.e0, sA));
+        a.skip_flags = n_remembered > 0 ? memo.flags.p : nullptr;
+        a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
+        launch_union(a.ntiles, false, sA);
+        a.skip_flags = nullptr;
+        GPP_HIP(hipEventRecord(sl.e1, sA));      // (one timestamp behind the first pass: every command between two first passes is a gap on the GPU)
+        GPP_HIP(hipStreamWaitEvent(sC, sl.e1, 0));
+        GPP_HIP(hipStreamWaitEvent(sC, ws.ev_join2[wsl], 0));
+        GPP_HIP(hipMemcpyAsync(sl.h, status_b->p, SB * sizeof(unsigned long long), hipMemcpyDeviceToHost, sC));
+        GPP_HIP(hipEventRecord(sl.ec, sC));
+        ws.slot_e1[wsl] = sl.e1; ws.slot_ec[wsl] = sl.ec;
+        PendingOi pc;
+        pc.bgrid = bgrid; pc.background = background; pc.bvariance = bvariance; pc.points = points; pc.obs = obs; pc.obs_variance = obs_variance;
+        pc.background_at_points = background_at_points; pc.bvariance_at_points = bvariance_at_points; pc.st = *st; pc.max_points = max_points;
+        pc.allow_extrapolation = allow_extrapolation; pc.out = out; pc.out_variance = out_variance; pc.mem = mem & ~GPP_ASYNC;
+        pc.slot = async_slot; pc.n_remembered = n_remembered; pc.skip_k_oi = skip_k_oi;
+        pc.stats = g_stats;
+        g_pending.push_back(pc);
+    }
+    // Round 5: the list passes BESIDE the first pass.  The tiles a geometry declines do not depend on the values (only on the
+    // coordinates, the structure and which observations are usable), so the list of the last call is this call's list: it is kept
+    // with the geometry (memo.list, one flag byte per tile), the first pass leaves the flagged tiles alone, and the list passes over
+    // the REMEMBERED list are launched on a second stream at the same time -- their latency (one lone work item per pass: 55 us of a
+    // 0.62 ms step at 500 rows per rank, 146 us of the 4.46 ms headline) disappears behind the first pass.  Nothing depends on the
+    // memory being right: a flagged tile is solved by the list passes whatever the first pass would have made of it (all paths give
+    // the same bits), and a tile the first pass declines that was NOT flagged arrives in its out_list as before, is taken by the serial
+    // passes after the read-back and joins the remembered list.
+    void union_overlapped() {
+        const hipStream_t side = stream2();
+        GPP_HIP(hipEventRecord(ws.ev_fork, stream()));             // (behind k_pack_obs, which also cleared the status block)
+        a.skip_flags = memo.flags.p;
+        first_pass();                                              // pass 1 on the library stream
+        a.skip_flags = nullptr;
+        GPP_HIP(hipStreamWaitEvent(side, ws.ev_fork, 0));
+        remembered_passes(side);
+        GPP_HIP(hipEventRecord(ws.ev_join, side));
+        GPP_HIP(hipStreamWaitEvent(stream(), ws.ev_join, 0));
+        mark_and_fetch();
+        if(skip_k_oi && h_ints[3] > 0) leftover_to_k_oi(NRUN_LONG, true, stream());   // 4-cell items for k_oi after all (before the counts below are cleared)
+        const int n_new = h_ints[1];
+        const int left_remembered = h_ints[3];
+        if(n_new > 0) {   // tiles the first pass declined that the memory did not hold: the serial passes, as without the overlap
+            GPP_HIP(hipMemsetAsync(d_fb_count + 1, 0, 2 * sizeof(int), stream()));
+            if(16 * (long)n_new > SHORT_ITEMS) { long_passes(n_new); if(skip_k_oi) launch_k_oi(false, stream()); }
+            else short_form(ws.fb_list.p, d_fb_count, 16 * (long)n_new, NRUN_LONG, true, stream());
         }
-        else {
-            const bool pairs = pairs_ok && !use_lu;
-            if(pairs) park_on(false);    // (k_oi visits every cell)
-            launch_k_oi(use_lu);
-            if(pairs) launch_pairs();
-            GPP_HIP(hipEventRecord(ws.e1, stream()));
-            fetch();
+        if(n_new > 0 || (skip_k_oi && left_remembered > 0)) mark_and_fetch();
+        overlap_left = left_remembered + (n_new > 0 ? h_ints[3] : 0);
+        overlap_new = n_new; overlap_remembered = n_remembered; ran_overlap = true;
+    }
+    // The tiles the first pass declined.  The usual case is a short list (or none): it is taken WITHOUT asking the host how long it
+    // is -- the short-list pass and the k_oi pass behind it are launched with fixed small grids and read the lengths
+    // on the device; a list too long for that grid is left untouched by both and handled after the one read-back of
+    // the call.  (A host round trip here cost ~25 us per call.)
+    void union_short_expected() {
+        first_pass();                                              // pass 1: every tile
+        // (a geometry that declined no tile the last time: not even the two empty launches; the read-back says if that was wrong)
+        const bool expect_none = memo_hit && memo.declined == 0.0f;
+        if(!expect_none) short_passes(SHORT_ITEMS);
+        mark_and_fetch();
+        const int n1 = h_ints[1];
+        if(16 * (long)n1 > SHORT_ITEMS || (expect_none && n1 > 0)) {   // a long list after all (or an unexpected one): nothing has touched it yet
+            if(16 * (long)n1 > SHORT_ITEMS) long_passes(n1); else short_passes(16 * n1);
+            mark_and_fetch();
         }
+    }
+    // A long list is expected, and the same geometry declines the same tiles: the two-level passes are launched for the length
+    // of the last call (+ 1/8) without asking the host first -- they read the true length on the device.  Only if MORE tiles were
+    // declined than those grids hold (other observations turned invalid) are the passes run again with the true length: every
+    // pass writes the same values for the cells it handles, so that is merely slower.
+    void union_long_expected() {
+        first_pass();                                              // pass 1: every tile
+        const int cap = path_env("GPP_OI_LONG_CAP") ? atoi(path_env("GPP_OI_LONG_CAP")) : memo.n1 + memo.n1 / 8 + 64;   // (the override: tests force the second run)
+        // (the statistics counters as the first pass left them: a second run of the list passes must not count its cells twice)
+        ws.status_snap.get(SB);
+        GPP_HIP(hipMemcpyAsync(ws.status_snap.p, d_counters, (SB - 8) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream()));
+        long_passes(cap);
+        mark_and_fetch();
+        const int n1 = h_ints[1];
+        if(n1 > cap) {
+            GPP_HIP(hipMemsetAsync(d_fb_count + 1, 0, 2 * sizeof(int), stream()));
+            GPP_HIP(hipMemcpyAsync(d_counters, ws.status_snap.p, (SB - 8) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream()));
+            long_passes(n1);
+            mark_and_fetch();
+        }
+    }
+    // one factorisation per tile, then the list passes; returns true when the call was deferred (nothing behind the first pass runs now)
+    bool run_union() {
+        // worst case per list: every tile declined and split into 4 (level 1) resp. 16 (level 2) items
+        // (the short-list pass writes up to 16 entries per declined tile, SHORT_ITEMS at most, whatever the number of tiles)
+        ws.fb_list.get((size_t)a.ntiles); ws.fb_list2.get(2 * (size_t)a.ntiles + 64);
+        ws.fb_list3.get(std::max<size_t>(4 * (size_t)a.ntiles, (size_t)SHORT_ITEMS) + 64);
+        pair_tiles = path_env("GPP_OI_PAIR_TILES") != nullptr;   // (off: measured 3 % slower than one tile per wave -- the waiting wave of a pair)
+        a.pair_solo = path_env("GPP_OI_PAIR_SOLO") ? 1 : 0;
+        // (a geometry whose last call left nothing to k_oi: not even its empty launch; the read-back says if that was wrong)
+        skip_k_oi = memo_hit && memo.leftover == 0;
+        // (when the last call with this geometry had a long list, the two-level passes are launched at once)
+        expect_long = memo_hit && 16.0 * (double)memo.declined * (double)a.ntiles > (double)SHORT_ITEMS;
+        overlap = memo_hit && memo.nlist > 0 && memo.list_ntiles == a.ntiles && !path_env("GPP_OI_NO_OVERLAP");
+        n_remembered = overlap ? memo.nlist : 0;
+        if(overlap && !ws.ev_fork) { GPP_HIP(hipEventCreateWithFlags(&ws.ev_fork, hipEventDisableTiming)); GPP_HIP(hipEventCreateWithFlags(&ws.ev_join, hipEventDisableTiming)); }
+        if(steady && (overlap || !expect_long)) { defer(); return true; }   // (not overlapped: nothing declined the last time, the first pass alone)
+        if(overlap) union_overlapped();
+        else if(!expect_long) union_short_expected();
+        else union_long_expected();
+        if(!overlap && skip_k_oi && h_ints[3] > 0) {   // 4-cell items for k_oi after all
+            leftover_to_k_oi(NRUN_LONG, true, stream());
+            mark_and_fetch();
+        }
+        ran_union = true;
+        return false;
+    }
+    // spatially varying Barnes structure: one LU per tile (k_oi_union_sp); the tiles it declines as smaller items, as on the scalar path (a
+    // short list straight to its 4-cell items, a long one through the 16-cell level), what is still left to k_oi's pivoted LU.  All on the library stream.
+    void run_spatial_tiles() {
+        ws.fb_list.get((size_t)a.ntiles);
+        a.out_list = ws.fb_list.p; a.out_count = d_fb_count;
+        a.tile0 = 0; a.tile_n = a.ntiles;
+        launch_union_sp(stream());
+        GPP_HIP(hipEventRecord(ws.eu, stream()));
+        mark_and_fetch();
+        const int n1 = h_ints[1];
+        if(n1 > 0) {
+            ws.fb_list2.get(2 * (size_t)a.ntiles + 64);
+            ws.fb_list3.get(std::max<size_t>(4 * (size_t)a.ntiles, (size_t)SHORT_ITEMS) + 64);
+            if(16 * (long)n1 <= SHORT_ITEMS) short_form(ws.fb_list.p, d_fb_count, 16 * (long)n1, NRUN_LONG, true, stream());
+            else long_form(ws.fb_list.p, d_fb_count, n1, true, stream());
+            mark_and_fetch();
+        }
+        ran_sp = true;
+    }
+    // every tile on k_oi, one factorisation per distinct selection
+    void run_plain() {
+        const bool pairs = pairs_ok && !use_lu;
+        if(pairs) park_on(false, stream());    // (k_oi visits every cell)
+        launch_k_oi(use_lu, stream());
+        if(pairs) launch_pairs(stream());
+        mark_and_fetch();
+    }
+
+    void count_fallbacks() {
         // (with the list passes beside the first pass its out_list holds only the tiles the memory did not know: overlap_new of them)
-        const int n_listed = ran_union ? h_ints[1] : 0;             // entries of ws.fb_list written by this call's first pass
-        const int nfb[3] = {ran_overlap ? overlap_remembered + overlap_new : n_listed, ran_union ? h_ints[2] : 0, ran_overlap ? overlap_left : (ran_union ? h_ints[3] : 0)};
-        g_stats.fallback_tiles = ran_sp ? h_ints[1] : nfb[0];
-        g_stats.fallback_subtiles = nfb[2];
+        n_listed = ran_union ? h_ints[1] : 0;
+        n_declined = ran_overlap ? overlap_remembered + overlap_new : n_listed;
+        n_left = ran_overlap ? overlap_left : (ran_union ? h_ints[3] : 0);
+        g_stats.fallback_tiles = ran_sp ? h_ints[1] : n_declined;
+        g_stats.fallback_subtiles = n_left;
         // (banded host path: the tiles whose cells the band downloads took too early -- everything the first pass did not finish itself)
         if(ran_overlap) { patch_l0 = memo.list.p; patch_n0 = overlap_remembered; patch_l1 = ws.fb_list.p; patch_n1 = overlap_new; }
         else { patch_l0 = ws.fb_list.p; patch_n0 = ran_union ? std::min(n_listed, a.ntiles) : 0; patch_l1 = nullptr; patch_n1 = 0; }
-        if(ran_union) {
-            if(!memo_hit) { memo.nlist = 0; memo.list_ntiles = 0; }
-            memo.points_id = points->serial; memo.h = a.s.st.h; memo.v = a.s.st.v; memo.w = a.s.st.w; memo.max_points = max_points;
-            memo.kh = a.s.st.kh; memo.kv = a.s.st.kv; memo.kw = a.s.st.kw; memo.cv = a.s.st.cv;
-            memo.declined = (float)nfb[0] / (float)a.ntiles;
-            memo.leftover = nfb[2];
-            memo.n1 = nfb[0];
-            // the declined tiles themselves, for the next call with this geometry (see `overlap` above).  The serial path lists EVERY declined
-            // tile in ws.fb_list: the memory is rebuilt from it; the overlapped path lists only the tiles the memory did not hold: appended.
-            // (room for every tile; nothing is launched when nothing changes -- the steady state of a repeated call)
-            const bool keep_list = !path_env("GPP_OI_NO_OVERLAP");
-            int n_add = 0;
-            if(!ran_overlap) {
-                memo.nlist = 0;
-                if(keep_list && n_listed > 0) {
-                    memo.list.get((size_t)a.ntiles); memo.flags.get((size_t)a.ntiles); memo.count.get(1);
-                    GPP_HIP(hipMemsetAsync(memo.flags.p, 0, (size_t)a.ntiles, stream()));
-                    memo.list_ntiles = a.ntiles;
-                    n_add = std::min(n_listed, a.ntiles);
-                }
-            }
-            else n_add = std::min(overlap_new, a.ntiles - memo.nlist);
-            if(n_add > 0) {
-                GPP_HIP(hipMemcpyAsync(memo.list.p + memo.nlist, ws.fb_list.p, (size_t)n_add * sizeof(int), hipMemcpyDeviceToDevice, stream()));
-                hipLaunchKernelGGL(k_flag_tiles, dim3((n_add + 255) / 256), dim3(256), 0, stream(), (const int*)(memo.list.p + memo.nlist), n_add, a.ntiles, memo.flags.p);
-                GPP_HIP(hipGetLastError());
-                memo.nlist += n_add;
-                ws.h_status[SB] = (unsigned long long)memo.nlist;      // (pinned: one word behind the mirror of the status block)
-                GPP_HIP(hipMemcpyAsync(memo.count.p, ws.h_status + SB, sizeof(int), hipMemcpyHostToDevice, stream()));
-                GPP_HIP(hipStreamSynchronize(stream()));
-            }
-        }
-        if(big_ok) {
-            const int nbig = h_ints[4];
-            if(nbig > 0 && !use_lu && !path_env("GPP_OI_NO_BIG")) {
-                const int nwg = std::min(nbig, 256);
-                a.big_keys = ws.big_keys.get((size_t)nwg * BIG_CAND);
-                a.big_mat = ws.big_mat.get((size_t)nwg * (BIG_N + 2) * BIG_N);
-                ws.huge_list.get((size_t)nbig);
-                a.huge_list = ws.huge_list.p; a.huge_count = d_huge_count;
-                hipLaunchKernelGGL(k_oi_big, dim3(nwg), dim3(256), 0, stream(), a);
-                GPP_HIP(hipGetLastError());
-                GPP_HIP(hipEventRecord(ws.e1, stream()));
-                fetch();
-                g_stats.big_cells = nbig;
-                const int nhuge = h_ints[5];
-                if(nhuge > 0) {   // beyond BIG_N observations / BIG_CAND candidates
-                    run_huge(ws.huge_list.p, d_huge_count, nhuge);
-                    GPP_HIP(hipEventRecord(ws.e1, stream()));
-                    fetch();
-                }
-            }
-            else if(nbig > 0) {   // non-symmetric / spatially varying structure (or the retry after a non-positive pivot)
-                run_huge(ws.big_list.p, d_big_count, nbig);
-                GPP_HIP(hipEventRecord(ws.e1, stream()));
-                fetch();
-                g_stats.big_cells = nbig;
-            }
-        }
-        if((err & ERR_SINGULAR) && ran_sp && !sp_failed) {   // a pivot of the unpivoted tile LU vanished: the whole call on the pivoted LU of k_oi
-            sp_failed = true;
-            g_stats.fallback_tiles = a.ntiles;
-            GPP_HIP(hipMemsetAsync(status_b->p, 0, SB * sizeof(unsigned long long), stream()));
-            continue;
-        }
-        if((err & ERR_SINGULAR) && !use_lu) {   // a pivot was not positive: redo the call with the pivoted LU, as LAPACK would
-            use_lu = true;
-            g_stats.fallback_tiles = a.ntiles;
-            GPP_HIP(hipMemsetAsync(status_b->p, 0, SB * sizeof(unsigned long long), stream()));
-            continue;
-        }
-        break;
     }
-    if(bands_down_done && !use_lu && !(err & (ERR_SINGULAR | ERR_OVERFLOW))) {
-        // the bands of the analysis are on their way down (third stream); what the list passes finished after the band of its tile left:
-        // those tiles' cells, tile-major, through a page-locked block, put in place by the host
+    void remember_geometry() {
+        if(!memo_hit) { memo.nlist = 0; memo.list_ntiles = 0; }
+        memo.points_id = points->serial; memo.h = a.s.st.h; memo.v = a.s.st.v; memo.w = a.s.st.w; memo.max_points = max_points;
+        memo.kh = a.s.st.kh; memo.kv = a.s.st.kv; memo.kw = a.s.st.kw; memo.cv = a.s.st.cv;
+        memo.declined = (float)n_declined / (float)a.ntiles; memo.leftover = n_left; memo.n1 = n_declined;
+        // the declined tiles themselves, for the next call with this geometry (see union_overlapped).  The serial path lists EVERY declined
+        // tile in ws.fb_list: the memory is rebuilt from it; the overlapped path lists only the tiles the memory did not hold: appended.
+        // (room for every tile; nothing is launched when nothing changes -- the steady state of a repeated call)
+        const bool keep_list = !path_env("GPP_OI_NO_OVERLAP");
+        int n_add = 0;
+        if(!ran_overlap) {
+            memo.nlist = 0;
+            if(keep_list && n_listed > 0) {
+                memo.list.get((size_t)a.ntiles); memo.flags.get((size_t)a.ntiles); memo.count.get(1);
+                GPP_HIP(hipMemsetAsync(memo.flags.p, 0, (size_t)a.ntiles, stream()));
+                memo.list_ntiles = a.ntiles;
+                n_add = std::min(n_listed, a.ntiles);
+            }
+        }
+        else n_add = std::min(overlap_new, a.ntiles - memo.nlist);
+        if(n_add > 0) {
+            GPP_HIP(hipMemcpyAsync(memo.list.p + memo.nlist, ws.fb_list.p, (size_t)n_add * sizeof(int), hipMemcpyDeviceToDevice, stream()));
+            hipLaunchKernelGGL(k_flag_tiles, dim3((n_add + 255) / 256), dim3(256), 0, stream(), (const int*)(memo.list.p + memo.nlist), n_add, a.ntiles, memo.flags.p);
+            GPP_HIP(hipGetLastError());
+            memo.nlist += n_add;
+            ws.h_status[SB] = (unsigned long long)memo.nlist;      // (pinned: one word behind the mirror of the status block)
+            GPP_HIP(hipMemcpyAsync(memo.count.p, ws.h_status + SB, sizeof(int), hipMemcpyHostToDevice, stream()));
+            GPP_HIP(hipStreamSynchronize(stream()));
+        }
+    }
+    void run_large_cells() {   // (see run_huge)
+        const int nbig = h_ints[4];
+        if(nbig <= 0) return;
+        g_stats.big_cells = nbig;
+        if(use_lu || path_env("GPP_OI_NO_BIG")) {   // non-symmetric / spatially varying structure (or the retry after a non-positive pivot)
+            run_huge(ws.big_list.p, d_big_count, nbig);
+            mark_and_fetch();
+            return;
+        }
+        const int nwg = std::min(nbig, 256);
+        a.big_keys = ws.big_keys.get((size_t)nwg * BIG_CAND);
+        a.big_mat = ws.big_mat.get((size_t)nwg * (BIG_N + 2) * BIG_N);
+        ws.huge_list.get((size_t)nbig);
+        a.huge_list = ws.huge_list.p; a.huge_count = d_huge_count;
+        hipLaunchKernelGGL(k_oi_big, dim3(nwg), dim3(256), 0, stream(), a);
+        GPP_HIP(hipGetLastError());
+        mark_and_fetch();
+        const int nhuge = h_ints[5];
+        if(nhuge > 0) {   // beyond BIG_N observations / BIG_CAND candidates
+            run_huge(ws.huge_list.p, d_huge_count, nhuge);
+            mark_and_fetch();
+        }
+    }
+    // a vanished pivot of the unpivoted tile LU, or a pivot of the Cholesky that was not positive: the whole call again on the pivoted LU of
+    // k_oi, as LAPACK would
+    bool must_retry() {
+        if(!(err & ERR_SINGULAR)) return false;
+        if(ran_sp && !sp_failed) sp_failed = true;
+        else if(!use_lu) use_lu = true;
+        else return false;
+        g_stats.fallback_tiles = a.ntiles;
+        GPP_HIP(hipMemsetAsync(status_b->p, 0, SB * sizeof(unsigned long long), stream()));
+        return true;
+    }
+
+    // the bands of the analysis are on their way down (third stream); what the list passes finished after the band of its tile left:
+    // those tiles' cells, tile-major, through a page-locked block, put in place by the host
+    void patch_bands() {
         const int np = patch_n0 + patch_n1;
         if(np > 0) {
             const size_t words = (size_t)np * 64 * (f_var.d ? 2 : 1) + (size_t)np;
@@ -2224,36 +2181,83 @@ static int oi_full_impl(gpp_points* bgrid, const float* background, const float*
             }
         }
     }
-    else if(zero_copy_out) GPP_HIP(hipStreamSynchronize(stream()));   // (the kernels wrote the caller's page-locked arrays themselves)
-    else if(f_out.host || f_var.host) {   // (device outputs: the stream is already idle after the status read-back)
-        if(bands_down_done) GPP_HIP(hipStreamSynchronize(stream3()));   // (a second run of the call -- pivoted LU -- wrote everything again: the early bands must not land on top of the full copy)
-        f_out.finish(); f_var.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
+    void deliver() {
+        if(bands_down_done && !use_lu && !(err & (ERR_SINGULAR | ERR_OVERFLOW))) patch_bands();
+        else if(zero_copy_out) GPP_HIP(hipStreamSynchronize(stream()));   // (the kernels wrote the caller's page-locked arrays themselves)
+        else if(f_out.host || f_var.host) {   // (device outputs: the stream is already idle after the status read-back)
+            if(bands_down_done) GPP_HIP(hipStreamSynchronize(stream3()));   // (a second run of the call -- pivoted LU -- wrote everything again: the early bands must not land on top of the full copy)
+            f_out.finish(); f_var.finish();
+            GPP_HIP(hipStreamSynchronize(stream()));
+        }
     }
-    float ms = 0;
-    GPP_HIP(hipEventElapsedTime(&ms, ws.e0, ws.e1));
-    g_stats.kernel_ms = ms;
-    g_stats.union_kernel_ms = 0;
-    if(ran_union || (ran_sp && !sp_failed)) GPP_HIP(hipEventElapsedTime(&g_stats.union_kernel_ms, ws.e0, ws.eu));
-    g_stats.cells_updated = 0; g_stats.solves = 0;
-    for(int k = 0; k < GPP_NSLOT; k++) { g_stats.cells_updated += (long long)counters[80 + 2 * k]; g_stats.solves += (long long)counters[81 + 2 * k]; }
-    if(timing_env("GPP_SCAN_STATS")) fprintf(stderr, "[gpp] scan: %llu candidates iterated, %llu survivor-branch executions, %d tiles\n", counters[2], counters[3], a.ntiles);
+    void publish_stats() {
+        GPP_HIP(hipEventElapsedTime(&g_stats.kernel_ms, ws.e0, ws.e1));
+        g_stats.union_kernel_ms = 0;
+        if(ran_union || (ran_sp && !sp_failed)) GPP_HIP(hipEventElapsedTime(&g_stats.union_kernel_ms, ws.e0, ws.eu));
+        g_stats.cells_updated = 0; g_stats.solves = 0;
+        for(int k = 0; k < GPP_NSLOT; k++) { g_stats.cells_updated += (long long)counters[80 + 2 * k]; g_stats.solves += (long long)counters[81 + 2 * k]; }
+        if(timing_env("GPP_SCAN_STATS")) fprintf(stderr, "[gpp] scan: %llu candidates iterated, %llu survivor-branch executions, %d tiles\n", counters[2], counters[3], a.ntiles);
 #ifdef GPP_UNION_PROFILE
-    { const char* nm[24] = {"cell loads", "bbox+init", "phase-1 loads", "rings", "phase 2", "classify", "union records", "P build", "eliminate", "export", "per-lane",
-                            "own classify", "B1 wait", "merge", "B2 wait", "B3 wait", "bisection", "bulk evaluations", "end_bulk", "-", "-", "-", "-", "-"};
-      const bool two = counters[20 + 24] != 0;
-      for(int w = 0; w < 2; w++) {
-          double tot = 0; for(int i = 0; i < 24; i++) tot += (double)counters[20 + 24 * w + i];
-          if(tot == 0) continue;
-          fprintf(stderr, "[gpp] union phases, wave %d (shader clocks per tile, %%):", w); for(int i = 0; i < 19; i++) fprintf(stderr, " %s %.0f (%.1f%%);", nm[i], counters[20 + 24 * w + i] / (double)a.ntiles * (two ? 2 : 1), 100.0 * counters[20 + 24 * w + i] / tot); fprintf(stderr, " total %.0f\n", tot / (double)a.ntiles * (two ? 2 : 1)); } }
+        { const char* nm[24] = {"cell loads", "bbox+init", "phase-1 loads", "rings", "phase 2", "classify", "union records", "P build", "eliminate", "export", "per-lane",
+                                "own classify", "B1 wait", "merge", "B2 wait", "B3 wait", "bisection", "bulk evaluations", "end_bulk", "-", "-", "-", "-", "-"};
+          const bool two = counters[20 + 24] != 0;
+          for(int w = 0; w < 2; w++) {
+              double tot = 0; for(int i = 0; i < 24; i++) tot += (double)counters[20 + 24 * w + i];
+              if(tot == 0) continue;
+              fprintf(stderr, "[gpp] union phases, wave %d (shader clocks per tile, %%):", w); for(int i = 0; i < 19; i++) fprintf(stderr, " %s %.0f (%.1f%%);", nm[i], counters[20 + 24 * w + i] / (double)a.ntiles * (two ? 2 : 1), 100.0 * counters[20 + 24 * w + i] / tot); fprintf(stderr, " total %.0f\n", tot / (double)a.ntiles * (two ? 2 : 1)); } }
 #endif
 #ifdef GPP_UNION_STATS
-    fprintf(stderr, "[gpp] union: fallback reasons: slots %llu, union>40 %llu, extras>12 %llu, layout %llu, per-cell extras>6 %llu; per tile: insertions %.1f, evictions %.1f, candidates evaluated outside the bulk disc %.1f, records loaded in phase 2 %.1f\n",
-                            counters[4], counters[5], counters[6], counters[7], counters[8], counters[9] / (double)a.ntiles, counters[10] / (double)a.ntiles, counters[11] / (double)a.ntiles, counters[12] / (double)a.ntiles);
+        fprintf(stderr, "[gpp] union: fallback reasons: slots %llu, union>40 %llu, extras>12 %llu, layout %llu, per-cell extras>6 %llu; per tile: insertions %.1f, evictions %.1f, candidates evaluated outside the bulk disc %.1f, records loaded in phase 2 %.1f\n",
+                                counters[4], counters[5], counters[6], counters[7], counters[8], counters[9] / (double)a.ntiles, counters[10] / (double)a.ntiles, counters[11] / (double)a.ntiles, counters[12] / (double)a.ntiles);
 #endif
-    if(timing_env("GPP_SCAN_STATS")) { fprintf(stderr, "[gpp] wave-level insertions per tile histogram:"); for(int i = 0; i < 70; i++) fprintf(stderr, " %d:%llu", i, counters[4 + i]); fprintf(stderr, "\n"); }
-    if(err & ERR_SINGULAR) runtime("optimal_interpolation: local (P+R) matrix is singular");
-    if(err & ERR_OVERFLOW) runtime("optimal_interpolation: more usable observations at a grid point than the scratch of the general kernel was sized for");
+        if(timing_env("GPP_SCAN_STATS")) { fprintf(stderr, "[gpp] wave-level insertions per tile histogram:"); for(int i = 0; i < 70; i++) fprintf(stderr, " %d:%llu", i, counters[4 + i]); fprintf(stderr, "\n"); }
+    }
+};
+}
+
+static int oi_full_impl(gpp_points* bgrid, const float* background, const float* bvariance,
+                        gpp_points* points, const float* obs, const float* obs_variance,
+                        const float* background_at_points, const float* bvariance_at_points,
+                        const gpp_structure* st, int max_points, int allow_extrapolation,
+                        float* out, float* out_variance, int mem) {
+    GPP_TRY
+    // argument checks of oi.cpp:152-186 (sizes are implied by the handles; pointers must be present)
+    if(max_points < 0) invalid("max_points must be >= 0");
+    if(!bgrid || !points) invalid("grid/points handle is NULL");
+    if(bgrid->type != points->type)
+        invalid("Both background and observations points must be of same coordinate type (lat/lon or x/y)");
+    if(bgrid->n > 0 && (!background || !out)) invalid("background/out is NULL");
+    if(points->n > 0 && (!obs || !obs_variance || !background_at_points)) invalid("observation arrays are NULL");
+    ensure_device();
+    g_stats = gpp_oi_stats();
+    g_stats.cells = bgrid->n;
+    if(bgrid->n == 0) return GPP_OK;
+
+    OiCall c{bgrid, background, bvariance, points, obs, obs_variance, background_at_points, bvariance_at_points, st, max_points, allow_extrapolation,
+             out, out_variance, mem, bgrid->n, points->n};
+    if(c.stage_fields()) return GPP_OK;   // (no observations)
+    // the plan: everything up to the decision whether the call is deferred touches nothing of the workspace slots
+    c.prepare_runtime();
+    c.fill_args();
+    c.plan_kernels();
+    c.plan_bands();
+    c.plan_deferral();
+    c.drain_and_bind_workspace();
+    for(int attempt = 0; attempt < 2; ++attempt) {
+        c.a.in_list = nullptr; c.a.in_count = nullptr; c.a.out_list = nullptr; c.a.out_count = nullptr; c.a.nrun = c.a.ntiles;
+        c.ran_union = c.ran_overlap = c.ran_sp = false;
+        if(c.use_union && !c.use_lu) { if(c.run_union()) return GPP_OK; }   // (deferred: gpp_wait completes it)
+        else if(c.sp_union && !c.sp_failed) c.run_spatial_tiles();
+        else c.run_plain();
+        c.count_fallbacks();
+        if(c.ran_union) c.remember_geometry();
+        if(c.big_ok) c.run_large_cells();
+        if(!c.must_retry()) break;
+    }
+    c.deliver();
+    c.publish_stats();
+    if(c.err & ERR_SINGULAR) runtime("optimal_interpolation: local (P+R) matrix is singular");
+    if(c.err & ERR_OVERFLOW) runtime("optimal_interpolation: more usable observations at a grid point than the scratch of the general kernel was sized for");
     return GPP_OK;
     GPP_CATCH
 }

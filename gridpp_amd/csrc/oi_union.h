@@ -118,12 +118,12 @@ template <> struct UnionCfg<32> {
     static constexpr int WPB = GPP_UNION_WPB;       // waves (work items) per workgroup
     template <bool PLAIN> static constexpr bool persistent() { return PLAIN && GPP_UNION_PERSIST != 0; }   // first pass as a persistent grid (see k_oi_union)
 };
-// NC = 48 (round 6): max_points 33 .. 46 -- 48 register columns + 8 late columns, 56 slots; 19 KB of LDS per wave and ~200 registers: TWO waves per SIMD
+// NC = 48 (round 6): max_points 33 .. 48 (what the host routes here; a tile whose union does not fit the slots is declined to the list passes) -- 48 register columns + 8 late columns, 56 slots; 19 KB of LDS per wave and ~200 registers: TWO waves per SIMD
 // where the 64-column form has 1.5 (its 22.8 KB per wave leave room for three two-wave workgroups per CU), and a quarter fewer multiply-adds.
 template <> struct UnionCfg<48> {
     static constexpr int WCAP = 56;
     static constexpr int MAXU = 56;
-    static constexpr int SOLVE = 1792;  // c = 46, 10 extras: 1756 doubles
+    static constexpr int SOLVE = 1792;  // sized for c = 46, 10 extras: 1756 doubles (max_points 47 and 48 are served too: fewer extras fit, the tile is declined sooner)
     static constexpr int WPB = 2;
     template <bool PLAIN> static constexpr bool persistent() { return false; }
 };

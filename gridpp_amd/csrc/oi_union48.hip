@@ -1,4 +1,4 @@
-// k_oi_union with 48 register columns (max_points 33..46; round 6): its own translation unit so that it compiles beside oi.hip and oi_union64.hip.
+// k_oi_union with 48 register columns (max_points 33..48; round 6): its own translation unit so that it compiles beside oi.hip and oi_union64.hip.
 #include "oi_union.h"
 
 void gpp_launch_union48(const OiArgs& a, const unsigned nblocks, const bool plain, const bool list, hipStream_t stream) {

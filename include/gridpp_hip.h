@@ -446,7 +446,9 @@ typedef struct gpp_oi_stats {
     long long cells_updated;  /* cells with at least one usable observation */
     long long solves;         /* local (P+R) factorisations actually performed */
     long long fallback_tiles; /* tiles k_oi_union handed to k_oi (or all tiles when the call was redone with the pivoted LU) */
-    float kernel_ms;          /* hipEvent time of the OI kernel(s) on the library stream */
+    float kernel_ms;          /* hipEvent time of the OI kernel(s) on the library stream.  Host-array calls on the banded path (a grid of >= 2^20 cells
+                               * that takes the tile kernel): each band's launch waits for the band's upload, so this and union_kernel_ms
+                               * include the host-to-device copies of the background; device-array calls: kernel time alone */
     float union_kernel_ms;    /* of which k_oi_union, first pass (one factorisation per tile); 0 when that kernel was not used */
     long long fallback_subtiles; /* work items (4 cells, or whole tiles) k_oi_union's list passes left to k_oi */
     long long big_cells;      /* grid points with more than 62 usable observations (done by k_oi_big) */
