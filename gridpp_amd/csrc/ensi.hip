@@ -861,219 +861,323 @@ extern "C" int gpp_ensi_last_kernel_ms(float* ms) {
     GPP_CATCH
 }
 
-extern "C" int gpp_optimal_interpolation_ensi(gpp_points* bgrid, const float* background, int ne, gpp_points* points,
-                                              const float* obs, const float* sigmas, const float* background_at_points,
-                                              const gpp_structure* st, int max_points, int allow_extrapolation,
-                                              float* out, int mem) {
-    GPP_TRY
-    if(max_points < 0) invalid("max_points must be >= 0");                                       // oi_ensi.cpp:123-124
-    if(!bgrid || !points) invalid("grid/points handle is NULL");
-    if(bgrid->type != points->type)
-        invalid("Both background and observations points must be of same coorindate type (lat/lon or x/y)");
-    if(!st) invalid("structure is NULL");
-    if(ne < 0) invalid("negative ensemble size");
-    const int C = bgrid->n, S = points->n, E = ne;
-    ensure_device();
-    g_ensi_ms = 0;
-    g_ensi_stats = gpp_ensi_stats{(long long)C, 0, 0, 0.0f};
-    if(C == 0 || E == 0) return GPP_OK;
+namespace {
+// One optimal_interpolation_ensi / optimal_interpolation_ensi_multi call on the host: the arguments both take, the fields, the valid members
+// and the kernel arguments.  A local of the two entry points below, which run its phases in order; every phase works on the library stream.
+// LAYOUT: the kernel templates are laid out in the code object in the order the member functions name them first (scan, pair, members, huge,
+// big_ns, multi, multi_huge): moving a function marked LAYOUT, or the names inside it, changes the device binary (tools/isa.sh), not the results.
+struct EnsiCall {
+    struct Field { const float* d; long n; };   // n values, E members each: what valid_members() looks at
+    using Kernel = void (*)(EnsiArgs);
+    static constexpr size_t NCOUNTERS = 80 + 1024 * 32;
+    static constexpr size_t NS_LDS = (size_t)3 * 64 * NSP * sizeof(double);   // dynamic LDS of k_ensi_big_ns
+
+    // ---- the arguments (the call object is an aggregate: the entry points fill these, everything below starts from its initialiser) ----
+    gpp_points* const bgrid; const float* const background; const int ne; gpp_points* const points; const gpp_structure* const st;
+    const int max_points, allow_extrapolation; float* const out; const int mem;
+    const int variant;   // optimal_interpolation_ensi_multi: 1 (ebe), 2 (ebesc), 3 (utem); 0: optimal_interpolation_ensi
+    const bool corr = variant != 2;
     EnsiWorkspace& ws = g_ews;
-    InField f_bg, f_obs, f_sig, f_pbg;
+
+    // ---- fields (f_bgc, f_br, f_pbgc: multi alone; f_sig: sigmas / pratios); the staging buffers go back to the pool when the call ends ----
+    InField f_bg, f_bgc, f_br, f_obs, f_sig, f_pbg, f_pbgc;
     OutField f_out;
-    f_bg.bind(background, (size_t)C * E, mem);
-    f_out.bind(out, (size_t)C * E, mem);
-    const long nbg = (long)C * E;
-    hipLaunchKernelGGL(k_copy, dim3((unsigned)((nbg + 255) / 256)), dim3(256), 0, stream(), f_bg.d, nbg, f_out.d);   // output = background (:146)
-    GPP_HIP(hipGetLastError());
-    if(S == 0) {   // oi_ensi.cpp:135-137
-        f_out.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
-    }
-    f_obs.bind(obs, S, mem);
-    f_sig.bind(sigmas, S, mem);
-    f_pbg.bind(background_at_points, (size_t)S * E, mem);
-    bgrid->to_device();
-    gpp_obs_index* ix = gpp_build_obs_index(points);
 
-    // valid members (host list; E is small)
-    std::vector<int> flags(E, 1);
-    ws.flags.upload(flags.data(), E);
-    hipLaunchKernelGGL(k_ensi_member_flags, dim3((unsigned)((nbg + 255) / 256)), dim3(256), 0, stream(), f_bg.d, nbg, E, ws.flags.p);
-    GPP_HIP(hipMemcpyAsync(flags.data(), ws.flags.p, sizeof(int) * E, hipMemcpyDeviceToHost, stream()));
-    GPP_HIP(hipStreamSynchronize(stream()));
+    int C = 0, S = 0, E = 0, nV = 0; long nbg = 0;
     std::vector<int> valid;
-    for(int e = 0; e < E; e++) if(flags[e]) valid.push_back(e);
-    const int nV = (int)valid.size();
-    // k_ensi_pair takes any number of valid members; k_ensi_big_ns (more than 32 usable observations at a grid point) holds one member per lane
-    const bool use_pair = true;
-    if(nV == 0) { f_out.finish(); GPP_HIP(hipStreamSynchronize(stream())); return GPP_OK; }
-    ws.validIdx.upload(valid.data(), nV);
-    ws.gYhat.get(S); ws.gY.get((size_t)S * nV);
-    hipLaunchKernelGGL(k_ensi_obs_prep, dim3((S + 127) / 128), dim3(128), 0, stream(), f_pbg.d, S, E, ws.validIdx.p, nV, ws.gYhat.p, ws.gY.p);
-    ws.pgeo.get(S); ws.oaux.get(S);
-    // oaux = (laf, obs, gYhat, sigma); only the observation itself must be valid (oi_ensi.cpp:235)
-    hipLaunchKernelGGL(k_pack_obs, dim3((S + 255) / 256), dim3(256), 0, stream(), S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p,
-                       f_obs.d, f_sig.d, (const float*)ws.gYhat.p, (const float*)nullptr, 0, ws.pgeo.p, ws.oaux.p);
-    GPP_HIP(hipGetLastError());
-    ws.err.get(1); ws.counters.get(80 + 1024 * 32);
-    GPP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(int), stream()));
-    GPP_HIP(hipMemsetAsync(ws.counters.p, 0, sizeof(unsigned long long) * (80 + 1024 * 32), stream()));
-    if(!ws.e0) { GPP_HIP(hipEventCreate(&ws.e0)); GPP_HIP(hipEventCreate(&ws.e1)); }
+    gpp_obs_index* ix = nullptr;
+    MultiArgs ma = MultiArgs();
+    EnsiArgs& a = ma.e;   // (optimal_interpolation_ensi hands `a` alone to its kernels)
+    bool big_ok = false; int nbig_cells = 0;   // ensi: the large-n kernels are on; cells on their list
 
-    EnsiArgs a = EnsiArgs();
-    a.gx = bgrid->d_x.p; a.gy = bgrid->d_y.p; a.gz = bgrid->d_z.p; a.gelev = bgrid->d_elev.p; a.glaf = bgrid->d_laf.p;
-    a.bg = f_bg.d; a.out = f_out.d;
-    a.C = C; a.E = E; a.ny = bgrid->ny; a.nx = bgrid->nx;
-    a.tiled2d = (bgrid->nx > 0 && (long)bgrid->ny * bgrid->nx == C) ? 1 : 0;
-    a.wshift = 3;
-    if(a.tiled2d) {
-        a.wshift = gpp_tile_wshift(bgrid);
-        const int tw = 1 << a.wshift, th = 64 >> a.wshift;
-        a.tiles_x = (a.nx + tw - 1) / tw; a.ntiles = a.tiles_x * ((a.ny + th - 1) / th);
+    // ================================================= phases of both entry points =================================================
+    void check_args() {   // oi_ensi.cpp:123-124, oi_ensi_multi.cpp:341-342; then C, S and E
+        if(max_points < 0) invalid("max_points must be >= 0");
+        if(!bgrid || !points) invalid("grid/points handle is NULL");
+        if(bgrid->type != points->type) invalid("Both background and observations points must be of same coorindate type (lat/lon or x/y)");
+        if(!st) invalid("structure is NULL");
+        if(ne < 0) invalid("negative ensemble size");
+        C = bgrid->n; S = points->n; E = ne; nbg = (long)C * E;
     }
-    else { a.tiles_x = 0; a.ntiles = (C + 63) / 64; }
-    a.s.pgeo = ws.pgeo.p; a.s.smeta = ix->d_smeta.p; a.s.bin_start = ix->d_bin_start.p;
-    a.s.axis_a = ix->axis_a; a.s.axis_b = ix->axis_b; a.s.nbx = ix->nbx; a.s.nby = ix->nby;
-    a.s.amin = ix->amin; a.s.bmin = ix->bmin; a.s.inv_s = ix->inv_s;
-    a.s.st = gpp_resolve_structure(st);
-    gpp_bind_field(a.s.st, st, bgrid, points, ws.cell_idx, ws.obs_idx);
-    a.s.max_points = max_points;
-    { const double occ = (double)S / ((double)ix->nbx * ix->nby);
-      const int kk = (max_points > 0 && max_points <= 32) ? max_points : 32;
-      a.s.q0 = std::max(1, std::min(8, (int)std::ceil(0.5 * (std::sqrt(1.6 * kk / std::max(occ, 1e-3)) - 1.0)))); }
-    a.s.scan_stats = timing_env("GPP_SCAN_STATS") ? ws.counters.p + 2 : nullptr;
-    a.s.K = (max_points > 0 && max_points <= EN) ? max_points : EN;
-    a.ogeo = ix->d_ogeo.p; a.oaux = ws.oaux.p;
-    a.gY = ws.gY.p; a.validIdx = ws.validIdx.p; a.nV = nV; a.valid_identity = (nV == E) ? 1 : 0;
-    a.sel = ws.sel.get((size_t)a.ntiles * EN * 64);
-    a.gram = ws.gram.get((size_t)a.ntiles * 2 * EN * EN);   // two matrices per tile: k_ensi_pair works on two groups at a time
-    a.debug = timing_env("GPP_ENSI_DEBUG") ? atoi(timing_env("GPP_ENSI_DEBUG")) : 0;
-    a.jtol2 = g_ensi_converge ? 0.0 : GPP_ENSI_JTOL2;
-    if(const char* jt = timing_env("GPP_ENSI_JTOL")) { if(!g_ensi_converge) { const double v = atof(jt); a.jtol2 = v * v; } }   // (experiments: |E| <= v c)   // gpp_ensi_set_convergence(1): the Jacobi sweeps run to convergence (no perturbation series to speak of)
-    a.allow_extrap = allow_extrapolation ? 1 : 0;
-    a.err = ws.err.p; a.counters = ws.counters.p;
-    // cells with more than 32 usable observations go to k_ensi_big (scalar structure functions; the spatially varying forms
-    // fail loudly there)
-    const bool big_ok = (max_points == 0 || max_points > EN) && !path_env("GPP_ENSI_NO_BIG");
-    if(big_ok) {
+    void copy_background() {   // output = background (oi_ensi.cpp:146, oi_ensi_multi.cpp:375)
+        f_bg.bind(background, (size_t)C * E, mem);
+        f_out.bind(out, (size_t)C * E, mem);
+        hipLaunchKernelGGL(k_copy, dim3((unsigned)((nbg + 255) / 256)), dim3(256), 0, stream(), f_bg.d, nbg, f_out.d);
+        GPP_HIP(hipGetLastError());
+    }
+    void finish_early() { f_out.finish(); GPP_HIP(hipStreamSynchronize(stream())); }   // the background is the answer
+    void index_obs() { bgrid->to_device(); ix = gpp_build_obs_index(points); }
+    // members valid in every one of the fields (host list; E is small): oi_ensi.cpp:187-201, oi_ensi_multi.cpp:395-418
+    void valid_members(std::initializer_list<Field> fields) {
+        std::vector<int> flags(E, 1);
+        ws.flags.upload(flags.data(), E);
+        for(const Field& f : fields)
+            hipLaunchKernelGGL(k_ensi_member_flags, dim3((unsigned)((f.n + 255) / 256)), dim3(256), 0, stream(), f.d, f.n, E, ws.flags.p);
+        GPP_HIP(hipMemcpyAsync(flags.data(), ws.flags.p, sizeof(int) * E, hipMemcpyDeviceToHost, stream()));
+        GPP_HIP(hipStreamSynchronize(stream()));
+        for(int e = 0; e < E; e++) if(flags[e]) valid.push_back(e);
+        nV = (int)valid.size();
+    }
+    void pack_obs(const float* obs, const float* fourth) {   // oaux = (laf, obs, gYhat, fourth); pgeo: the usable observations
+        ws.pgeo.get(S); ws.oaux.get(S);
+        hipLaunchKernelGGL(k_pack_obs, dim3((S + 255) / 256), dim3(256), 0, stream(), S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p,
+                           obs, fourth, (const float*)ws.gYhat.p, (const float*)nullptr, 0, ws.pgeo.p, ws.oaux.p);
+        GPP_HIP(hipGetLastError());
+    }
+    void bind_scan() {   // the grid, the observation index, the structure and the members: what both sets of kernels read
+        a.gx = bgrid->d_x.p; a.gy = bgrid->d_y.p; a.gz = bgrid->d_z.p; a.gelev = bgrid->d_elev.p; a.glaf = bgrid->d_laf.p;
+        a.bg = f_bg.d; a.out = f_out.d; a.C = C; a.E = E;
+        a.s.pgeo = ws.pgeo.p; a.s.smeta = ix->d_smeta.p; a.s.bin_start = ix->d_bin_start.p;
+        a.s.axis_a = ix->axis_a; a.s.axis_b = ix->axis_b; a.s.nbx = ix->nbx; a.s.nby = ix->nby;
+        a.s.amin = ix->amin; a.s.bmin = ix->bmin; a.s.inv_s = ix->inv_s;
+        a.s.st = gpp_resolve_structure(st);
+        gpp_bind_field(a.s.st, st, bgrid, points, ws.cell_idx, ws.obs_idx);
+        a.s.max_points = max_points;
+        a.ogeo = ix->d_ogeo.p; a.oaux = ws.oaux.p;
+        a.gY = ws.gY.p; a.validIdx = ws.validIdx.p; a.nV = nV; a.valid_identity = (nV == E) ? 1 : 0;
+        a.allow_extrap = allow_extrapolation ? 1 : 0; a.err = ws.err.p;
+    }
+    void big_lists() {   // the cells the first kernel hands on (big_count[0]) and those the second one hands on (big_count[1])
         a.big_list = ws.big_list.get(2 * (size_t)C); a.huge_list = a.big_list + C; a.big_count = ws.big_count.get(2);
         GPP_HIP(hipMemsetAsync(ws.big_count.p, 0, 2 * sizeof(int), stream()));
     }
-    GPP_HIP(hipEventRecord(ws.e0, stream()));
-    if(use_pair) {
-        a.meta = ws.meta.get((size_t)a.ntiles * 64);
-        a.hsigs = ws.hsigs.get((size_t)a.ntiles * 64);
+    void ensure_events() { if(!ws.e0) { GPP_HIP(hipEventCreate(&ws.e0)); GPP_HIP(hipEventCreate(&ws.e1)); } }
+    void start_clock() { GPP_HIP(hipEventRecord(ws.e0, stream())); }   // (e0 .. e1: what gpp_ensi_last_kernel_ms reports)
+    void finish(int& err, unsigned long long* npass = nullptr) {   // npass: counter 72 (ensi), with the other counters in a GPP_ENSI_STATS run
+        GPP_HIP(hipEventRecord(ws.e1, stream()));
+        GPP_HIP(hipMemcpyAsync(&err, ws.err.p, sizeof(int), hipMemcpyDeviceToHost, stream()));
+        if(npass) GPP_HIP(hipMemcpyAsync(npass, ws.counters.p + 72, sizeof(*npass), hipMemcpyDeviceToHost, stream()));
+        f_out.finish();
+        if(npass && timing_env("GPP_ENSI_STATS")) GPP_HIP(hipMemcpyAsync(host_counters(), ws.counters.p, sizeof(unsigned long long) * NCOUNTERS, hipMemcpyDeviceToHost, stream()));
+        GPP_HIP(hipStreamSynchronize(stream()));
+        GPP_HIP(hipEventElapsedTime(&g_ensi_ms, ws.e0, ws.e1));
+    }
+
+    // ================================================= optimal_interpolation_ensi =================================================
+    void stage_obs(const float* obs, const float* sigmas, const float* background_at_points) {
+        f_obs.bind(obs, S, mem); f_sig.bind(sigmas, S, mem);
+        f_pbg.bind(background_at_points, (size_t)S * E, mem);
+        index_obs();
+    }
+    void prep_obs() {   // the perturbations of the valid members at the observations, the observation block, the status words
+        ws.validIdx.upload(valid.data(), nV);
+        ws.gYhat.get(S); ws.gY.get((size_t)S * nV);
+        hipLaunchKernelGGL(k_ensi_obs_prep, dim3((S + 127) / 128), dim3(128), 0, stream(), f_pbg.d, S, E, ws.validIdx.p, nV, ws.gYhat.p, ws.gY.p);
+        pack_obs(f_obs.d, f_sig.d);   // (fourth: sigma; only the observation itself must be valid, oi_ensi.cpp:235)
+        ws.err.get(1); ws.counters.get(NCOUNTERS);
+        GPP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(int), stream()));
+        GPP_HIP(hipMemsetAsync(ws.counters.p, 0, sizeof(unsigned long long) * NCOUNTERS, stream()));
+        ensure_events();
+    }
+    void plan_tiles() {   // 64-cell tiles: the most square ones of a 2-D grid (gpp_tile_wshift), runs of 64 points of anything else
+        a.ny = bgrid->ny; a.nx = bgrid->nx;
+        a.tiled2d = (bgrid->nx > 0 && (long)bgrid->ny * bgrid->nx == C) ? 1 : 0;
+        a.wshift = 3;
+        if(a.tiled2d) {
+            a.wshift = gpp_tile_wshift(bgrid);
+            const int tw = 1 << a.wshift, th = 64 >> a.wshift;
+            a.tiles_x = (a.nx + tw - 1) / tw; a.ntiles = a.tiles_x * ((a.ny + th - 1) / th);
+        }
+        else { a.tiles_x = 0; a.ntiles = (C + 63) / 64; }
+    }
+    void tune_scan() {   // behind bind_scan(): the scan's start square and list length, the per-tile scratch, the experiment switches
+        const double occ = (double)S / ((double)ix->nbx * ix->nby);
+        const int kk = (max_points > 0 && max_points <= 32) ? max_points : 32;
+        a.s.q0 = std::max(1, std::min(8, (int)std::ceil(0.5 * (std::sqrt(1.6 * kk / std::max(occ, 1e-3)) - 1.0))));
+        a.s.scan_stats = timing_env("GPP_SCAN_STATS") ? ws.counters.p + 2 : nullptr;
+        a.s.K = (max_points > 0 && max_points <= EN) ? max_points : EN;
+        a.sel = ws.sel.get((size_t)a.ntiles * EN * 64);
+        a.gram = ws.gram.get((size_t)a.ntiles * 2 * EN * EN);   // two matrices per tile: k_ensi_pair works on two groups at a time
+        a.debug = timing_env("GPP_ENSI_DEBUG") ? atoi(timing_env("GPP_ENSI_DEBUG")) : 0;
+        a.jtol2 = g_ensi_converge ? 0.0 : GPP_ENSI_JTOL2;   // gpp_ensi_set_convergence(1): the Jacobi sweeps run to convergence (no perturbation series to speak of)
+        if(const char* jt = timing_env("GPP_ENSI_JTOL")) { if(!g_ensi_converge) { const double v = atof(jt); a.jtol2 = v * v; } }   // (experiments: |E| <= v c)
+        a.counters = ws.counters.p;
+        // cells with more than 32 usable observations go to k_ensi_big_ns, those it cannot hold to k_ensi_huge
+        big_ok = (max_points == 0 || max_points > EN) && !path_env("GPP_ENSI_NO_BIG");
+    }
+    // the scan, then the spectral side (k_ensi_pair: pairs of cells, warm-started along a tile) and the ensemble side in batches of tiles
+    void run_tiles() {   // LAYOUT: in front of launch_members
+        a.meta = ws.meta.get((size_t)a.ntiles * 64); a.hsigs = ws.hsigs.get((size_t)a.ntiles * 64);
         if(a.s.st.fh) hipLaunchKernelGGL(k_ensi_scan<true>, dim3(a.ntiles), dim3(64), 0, stream(), a);
         else hipLaunchKernelGGL(k_ensi_scan<false>, dim3(a.ntiles), dim3(64), 0, stream(), a);
         GPP_HIP(hipGetLastError());
         if(nV <= 1) hipLaunchKernelGGL(k_ensi_count_cells, dim3(256), dim3(256), 0, stream(), (const unsigned*)a.meta, (long)a.ntiles * 64, ws.counters.p + 72);
-        // spectral side (pairs of cells, warm-started along a tile) and ensemble side (one wave per cell) in batches of tiles: what
-        // the second kernel needs of a cell (17 KB) waits in HBM.  The park is kept between calls (freeing and re-allocating tens of
-        // GB costs seconds) and is therefore bounded: two fifths of the device memory (115 GB of 288: config 5's 110 GB go through in one
-        // batch; every batch boundary costs the tails of both kernels, 1.5 ms on config 5 -- a quarter = two batches until round 6), never more
-        // than half of what is free right now; gpp_release_workspaces() gives it back (GPP_ENSI_PARK_MB)
-        size_t park_bytes = (size_t)72 << 30;
-        {
-            size_t free_b = 0, total_b = 0;
-            if(hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-                park_bytes = std::min(total_b / 5 * 2, std::max<size_t>((free_b + ws.cpark.cap * sizeof(double)) / 2, (size_t)64 << 20));
-        }
-        if(path_env("GPP_ENSI_PARK_MB")) park_bytes = (size_t)atol(path_env("GPP_ENSI_PARK_MB")) << 20;
-        const size_t per_tile = (size_t)64 * ENSI_PARK_D * sizeof(double);
-        int tcap = (int)std::max<size_t>(1, std::min<size_t>((size_t)a.ntiles, park_bytes / per_tile));
-        for(;;) {   // (somebody else may hold the memory after all: halve the batch until the park fits)
-            try { a.cpark = ws.cpark.get((size_t)tcap * 64 * ENSI_PARK_D); break; }
-            catch(const Error&) { if(tcap <= 1) throw; (void)hipGetLastError(); tcap = (tcap + 1) / 2; }
-        }
+        const int tcap = park_tiles();
         for(int t0 = 0; t0 < a.ntiles; t0 += tcap) {
             const int nt = std::min(tcap, a.ntiles - t0);
             a.tile0 = t0;
             if(a.s.st.fh) hipLaunchKernelGGL(k_ensi_pair<true>, dim3(nt), dim3(64), 0, stream(), a);
             else hipLaunchKernelGGL(k_ensi_pair<false>, dim3(nt), dim3(64), 0, stream(), a);
-            // (at most 64 valid members: the three-waves-per-SIMD form, ensi_members3.h; GPP_ENSI_MEMBERS2: the two-area kernel it replaced)
-            if(a.nV <= 64 && !path_env("GPP_ENSI_MEMBERS2")) hipLaunchKernelGGL(k_ensi_members3, dim3((unsigned)nt * 64u), dim3(64), 0, stream(), a);
-            else if(a.nV <= 64) hipLaunchKernelGGL(k_ensi_members<true>, dim3((unsigned)nt * 64u), dim3(64), 0, stream(), a);
-            else hipLaunchKernelGGL(k_ensi_members<false>, dim3((unsigned)nt * 64u), dim3(64), 0, stream(), a);
-            GPP_HIP(hipGetLastError());
+            launch_members(nt);
         }
     }
-    GPP_HIP(hipGetLastError());
-    int nbig_cells = 0;
-    if(big_ok) {
+    // What k_ensi_members needs of a cell (17 KB) waits in HBM.  The park is kept between calls (freeing and re-allocating tens of GB costs
+    // seconds) and is therefore bounded: two fifths of the device memory (115 GB of 288: config 5's 110 GB go through in one batch; every
+    // batch boundary costs the tails of both kernels, 1.5 ms on config 5 -- a quarter = two batches until round 6), never more than half of
+    // what is free right now; gpp_release_workspaces() gives it back (GPP_ENSI_PARK_MB).  Returns the tiles of a batch.
+    int park_tiles() {
+        size_t park_bytes = (size_t)72 << 30, free_b = 0, total_b = 0;
+        if(hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+            park_bytes = std::min(total_b / 5 * 2, std::max<size_t>((free_b + ws.cpark.cap * sizeof(double)) / 2, (size_t)64 << 20));
+        if(path_env("GPP_ENSI_PARK_MB")) park_bytes = (size_t)atol(path_env("GPP_ENSI_PARK_MB")) << 20;
+        const size_t per_tile = (size_t)64 * ENSI_PARK_D * sizeof(double);
+        int tcap = (int)std::max<size_t>(1, std::min<size_t>((size_t)a.ntiles, park_bytes / per_tile));
+        for(;;) {   // (somebody else may hold the memory after all: halve the batch until the park fits)
+            try { a.cpark = ws.cpark.get((size_t)tcap * 64 * ENSI_PARK_D); return tcap; }
+            catch(const Error&) { if(tcap <= 1) throw; (void)hipGetLastError(); tcap = (tcap + 1) / 2; }
+        }
+    }
+    void launch_members(const int nt) {   // the ensemble side, one wave per cell.  LAYOUT: behind run_tiles, in front of run_huge
+        // (at most 64 valid members: the three-waves-per-SIMD form, ensi_members3.h; GPP_ENSI_MEMBERS2: the two-area kernel it replaced)
+        const dim3 grid((unsigned)nt * 64u), block(64);
+        if(a.nV <= 64 && !path_env("GPP_ENSI_MEMBERS2")) hipLaunchKernelGGL(k_ensi_members3, grid, block, 0, stream(), a);
+        else if(a.nV <= 64) hipLaunchKernelGGL(k_ensi_members<true>, grid, block, 0, stream(), a);
+        else hipLaunchKernelGGL(k_ensi_members<false>, grid, block, 0, stream(), a);
+        GPP_HIP(hipGetLastError());
+    }
+    void run_huge(const int* list, const int* count, const int nitems) {   // the general kernel, keys + E x E matrices in HBM.  LAYOUT: in front of launch_big_ns
+        const size_t mat = 2 * (size_t)nV * nV + 5 * (size_t)nV;
+        const HugeScratch hs = huge_scratch(S, mat * sizeof(double), nitems);
+        if(!hs.nwg) runtime("optimal_interpolation_ensi: the scratch of one grid point (" + std::to_string(hs.per_wg >> 20) + " MB) does not fit the budget of the general kernel (GPP_OI_HUGE_BUDGET_MB)");
+        a.huge_kcap = hs.kcap;
+        a.huge_keys = ws.huge_keys.get((size_t)hs.nwg * hs.kcap);
+        a.huge_mat = ws.huge_mat.get((size_t)hs.nwg * mat);
+        if(a.s.st.fh) hipLaunchKernelGGL(k_ensi_huge<true>, dim3(hs.nwg), dim3(256), 0, stream(), a, list, count);
+        else hipLaunchKernelGGL(k_ensi_huge<false>, dim3(hs.nwg), dim3(256), 0, stream(), a, list, count);
+        GPP_HIP(hipGetLastError());
+    }
+    void launch_big_ns(const int nbig) {   // one member per lane; forms[not FULL][not SPATIAL], FULL: 49..64 valid members.  LAYOUT: the order of `forms`
+        static constexpr Kernel forms[2][2] = {{k_ensi_big_ns<true, true>, k_ensi_big_ns<false, true>}, {k_ensi_big_ns<true, false>, k_ensi_big_ns<false, false>}};
+        const int nwg = std::min(nbig, 1024);
+        a.big_keys = ws.big_keys.get((size_t)nwg * EBIG_CAND);
+        static std::once_flag ns_once;
+        std::call_once(ns_once, [] {
+            for(const auto& row : forms) for(const Kernel k : row) GPP_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NS_LDS));
+        });
+        hipLaunchKernelGGL(forms[nV > 48 ? 0 : 1][a.s.st.fh ? 0 : 1], dim3(nwg), dim3(256), NS_LDS, stream(), a);
+        GPP_HIP(hipGetLastError());
+    }
+    void run_big() {   // the cells with more than 32 usable observations
         int nbig = 0;
         GPP_HIP(hipMemcpyAsync(&nbig, ws.big_count.p, sizeof(int), hipMemcpyDeviceToHost, stream()));
         GPP_HIP(hipStreamSynchronize(stream()));
         nbig_cells = nbig;
-        auto launch_huge = [&](const int* list, const int* count, int nitems) {   // no capacity of its own: scratch sized for this call
-            int kcap = 1;
-            while(kcap < S) kcap <<= 1;
-            // scratch per workgroup: candidate keys for every observation + the E x E matrices; within the 16 GB budget of the general
-            // kernels (like optimal_interpolation_ensi_multi): fewer workgroups when a grid point needs much
-            const size_t per_wg = (size_t)kcap * sizeof(unsigned long long) + (2 * (size_t)nV * nV + 5 * (size_t)nV) * sizeof(double);
-            size_t budget = (size_t)16 << 30;
-            if(path_env("GPP_OI_HUGE_BUDGET_MB")) budget = (size_t)atol(path_env("GPP_OI_HUGE_BUDGET_MB")) << 20;
-            if(per_wg > budget) runtime("optimal_interpolation_ensi: the scratch of one grid point (" + std::to_string(per_wg >> 20) + " MB) does not fit the budget of the general kernel (GPP_OI_HUGE_BUDGET_MB)");
-            const int nwg = (int)std::max<size_t>(1, std::min<size_t>({(size_t)nitems, (size_t)512, budget / per_wg}));
-            a.huge_kcap = kcap;
-            a.huge_keys = ws.huge_keys.get((size_t)nwg * kcap);
-            a.huge_mat = ws.huge_mat.get((size_t)nwg * (2 * (size_t)nV * nV + 5 * (size_t)nV));
-            if(a.s.st.fh) hipLaunchKernelGGL(k_ensi_huge<true>, dim3(nwg), dim3(256), 0, stream(), a, list, count);
-            else hipLaunchKernelGGL(k_ensi_huge<false>, dim3(nwg), dim3(256), 0, stream(), a, list, count);
-            GPP_HIP(hipGetLastError());
-        };
-        if(nbig > 0 && nV > 16384) runtime("optimal_interpolation_ensi: more than 16384 valid ensemble members at a grid point with more than 32 observations are not supported on the GPU path (the general kernel stages one row of Y in 64 KB of LDS)");
-        if(nbig > 0 && nV > EMAXV) launch_huge(a.big_list, a.big_count, nbig);      // more valid members than one lane each: the general kernel
-        else if(nbig > 0) {
-            const int nwg = std::min(nbig, 1024);
-            a.big_keys = ws.big_keys.get((size_t)nwg * EBIG_CAND);
-            {
-                const size_t ns_lds = (size_t)3 * 64 * NSP * sizeof(double);
-                static std::once_flag ns_once;
-                std::call_once(ns_once, [=] {
-                    GPP_HIP(hipFuncSetAttribute((const void*)k_ensi_big_ns<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ns_lds));
-                    GPP_HIP(hipFuncSetAttribute((const void*)k_ensi_big_ns<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ns_lds));
-                    GPP_HIP(hipFuncSetAttribute((const void*)k_ensi_big_ns<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ns_lds));
-                    GPP_HIP(hipFuncSetAttribute((const void*)k_ensi_big_ns<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ns_lds));
-                });
-                const bool full = nV > 48;
-                if(a.s.st.fh) { if(full) hipLaunchKernelGGL((k_ensi_big_ns<true, true>), dim3(nwg), dim3(256), ns_lds, stream(), a); else hipLaunchKernelGGL((k_ensi_big_ns<true, false>), dim3(nwg), dim3(256), ns_lds, stream(), a); }
-                else { if(full) hipLaunchKernelGGL((k_ensi_big_ns<false, true>), dim3(nwg), dim3(256), ns_lds, stream(), a); else hipLaunchKernelGGL((k_ensi_big_ns<false, false>), dim3(nwg), dim3(256), ns_lds, stream(), a); }
-            }
-            GPP_HIP(hipGetLastError());
-            int nhuge = 0;   // cells with more candidates than the LDS sort of k_ensi_big holds (or no convergence of the iteration)
-            GPP_HIP(hipMemcpyAsync(&nhuge, ws.big_count.p + 1, sizeof(int), hipMemcpyDeviceToHost, stream()));
-            GPP_HIP(hipStreamSynchronize(stream()));
-            if(nhuge > 0) launch_huge(a.huge_list, a.big_count + 1, nhuge);
-        }
+        if(nbig <= 0) return;
+        if(nV > 16384) runtime("optimal_interpolation_ensi: more than 16384 valid ensemble members at a grid point with more than 32 observations are not supported on the GPU path (the general kernel stages one row of Y in 64 KB of LDS)");
+        if(nV > EMAXV) { run_huge(a.big_list, a.big_count, nbig); return; }   // more valid members than one lane each: the general kernel
+        launch_big_ns(nbig);
+        int nhuge = 0;   // cells with more candidates than the LDS sort of k_ensi_big_ns holds (or no convergence of the iteration)
+        GPP_HIP(hipMemcpyAsync(&nhuge, ws.big_count.p + 1, sizeof(int), hipMemcpyDeviceToHost, stream()));
+        GPP_HIP(hipStreamSynchronize(stream()));
+        if(nhuge > 0) run_huge(a.huge_list, a.big_count + 1, nhuge);
     }
-    GPP_HIP(hipEventRecord(ws.e1, stream()));
-    int err = 0;
-    unsigned long long npass = 0;
-    GPP_HIP(hipMemcpyAsync(&err, ws.err.p, sizeof(int), hipMemcpyDeviceToHost, stream()));
-    GPP_HIP(hipMemcpyAsync(&npass, ws.counters.p + 72, sizeof(npass), hipMemcpyDeviceToHost, stream()));
-    f_out.finish();
-    static thread_local std::vector<unsigned long long> hcv(80 + 1024 * 32);
-    unsigned long long* const hc = hcv.data();
-    if(timing_env("GPP_ENSI_STATS")) GPP_HIP(hipMemcpyAsync(hc, ws.counters.p, sizeof(unsigned long long) * hcv.size(), hipMemcpyDeviceToHost, stream()));
-    GPP_HIP(hipStreamSynchronize(stream()));
-    GPP_HIP(hipEventElapsedTime(&g_ensi_ms, ws.e0, ws.e1));
-    // grid points the call left untouched because their E x E system is singular or not finite (the reference's "Condition number error in
-    // N points. Using raw values in those points.", oi_ensi.cpp:386-390,557-561; the mirrors print it): with fewer than two valid members
-    // that is every grid point with an observation in range, the large-n cells (all of them have observations) included
-    g_ensi_stats.kernel_ms = g_ensi_ms;
-    g_ensi_stats.condition_passthrough = (long long)npass + ((nV <= 1 && big_ok) ? (long long)nbig_cells : 0);
-    if(timing_env("GPP_ENSI_STATS")) {
+    // GPP_ENSI_STATS (diagnostic builds): the host copy of the counters
+    static unsigned long long* host_counters() { static thread_local std::vector<unsigned long long> hcv(NCOUNTERS); return hcv.data(); }
+    void print_stats() {
+        if(!timing_env("GPP_ENSI_STATS")) return;
+        unsigned long long* const hc = host_counters();
         unsigned long long sw = 0; for(int i = 0; i < 32; i++) sw += hc[4 + i];
-        fprintf(stderr, "[gpp] ensi: %llu cells solved, %.2f Jacobi sweeps per cell\n", hc[1], hc[1] ? (use_pair ? GPP_ENSI_JCHUNK / 16.0 : 1.0) * (double)sw / (double)hc[1] : 0.0);
+        fprintf(stderr, "[gpp] ensi: %llu cells solved, %.2f Jacobi sweeps per cell\n", hc[1], hc[1] ? GPP_ENSI_JCHUNK / 16.0 * (double)sw / (double)hc[1] : 0.0);
         for(int sl = 0; sl < 1024; sl++) for(int i = 0; i < 12; i++) { hc[40 + i] += hc[80 + sl * 32 + i]; hc[60 + i] += hc[80 + sl * 32 + 16 + i]; }
         unsigned long long tot = 0; for(int i = 0; i < 12; i++) tot += hc[40 + i];
         unsigned long long tot2 = 0; for(int i = 0; i < 12; i++) tot2 += hc[60 + i];
         if(tot2) { fprintf(stderr, "[gpp] ensi members phases (%% of wave cycles):"); for(int i = 0; i < 12; i++) fprintf(stderr, " %d:%.1f", i, 100.0 * (double)hc[60 + i] / (double)tot2); fprintf(stderr, "\n"); }
         if(tot) { fprintf(stderr, "[gpp] ensi phases (%% of wave cycles):"); for(int i = 0; i < 10; i++) fprintf(stderr, " %d:%.1f", i, 100.0 * (double)hc[40 + i] / (double)tot); fprintf(stderr, "\n"); }
     }
-    if(err & 1) runtime(big_ok ? "Internal error. optimal_interpolation_ensi: candidate scratch of the general kernel too small"
-                               : "optimal_interpolation_ensi: a grid point has more usable observations than the 32-row tile kernel holds and the large-n kernels are switched off (GPP_ENSI_NO_BIG)");
+
+    // ================================================= optimal_interpolation_ensi_multi =================================================
+    int multi_wgs() const { return std::min(C, 2048); }   // workgroups of k_ensi_multi (grid-stride over the grid points)
+    void stage_multi(const float* bratios, const float* background_corr, const float* pobs, const float* pratios, const float* pbackground, const float* pbackground_corr) {
+        if(corr) { f_bgc.bind(background_corr, (size_t)C * E, mem); f_pbgc.bind(pbackground_corr, (size_t)S * E, mem); }
+        f_br.bind(bratios, C, mem);
+        f_obs.bind(pobs, variant == 3 ? (size_t)S : (size_t)S * E, mem);
+        f_sig.bind(pratios, S, mem);
+        f_pbg.bind(pbackground, (size_t)S * E, mem);
+        index_obs();
+    }
+    void multi_valid_members() {   // members valid in every field (:395-418)
+        const Field bg{f_bg.d, nbg}, pbg{f_pbg.d, (long)S * E};
+        if(corr) valid_members({bg, pbg, {f_bgc.d, bg.n}, {f_pbgc.d, pbg.n}});
+        else valid_members({bg, pbg});
+    }
+    void prep_multi_obs() {   // the per-observation ensemble quantities, the observation block, the error word
+        if(nV > 16384) runtime("optimal_interpolation_ensi_multi: more than 16384 valid ensemble members are not supported on the GPU path (the general kernel stages one row of Y in 64 KB of LDS)");
+        if(variant == 1 && nV > 4096) runtime("optimal_interpolation_ensi_multi_ebe: more than 4096 valid ensemble members are not supported on the GPU path");
+        ws.validIdx.upload(valid.data(), nV);
+        ws.gYhat.get(S); ws.gY.get((size_t)S * nV); ws.gYm.get((size_t)S * nV); ws.obs0.get(S);
+        hipLaunchKernelGGL(k_multi_obs_prep, dim3((S + 127) / 128), dim3(128), 0, stream(), variant, f_pbg.d, corr ? f_pbgc.d : f_pbg.d, f_obs.d, S, E,
+                           (const int*)ws.validIdx.p, nV, ws.gY.p, ws.gYm.p, ws.gYhat.p, ws.obs0.p);
+        pack_obs(ws.obs0.p, f_sig.d);   // (obs[.][0] / obs and pratio: an observation is usable when that first value is valid, :480)
+        ws.err.get(1);
+        GPP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(int), stream()));
+        ensure_events();
+    }
+    void fill_multi_args() {
+        bind_scan();
+        if(a.s.st.fh) runtime("optimal_interpolation_ensi_multi: spatially varying structure functions are not supported on the GPU path");
+        ma.gYm = ws.gYm.p; ma.bgc = corr ? f_bgc.d : f_bg.d; ma.bratios = f_br.d;
+        ma.pobs2 = f_obs.d; ma.pbg2 = f_pbg.d;
+        ma.oob = (variant != 3 && valid[nV - 1] != nV - 1) ? 1 : 0;
+        a.big_keys = ws.big_keys.get((size_t)multi_wgs() * EBIG_CAND);
+    }
+    int launch_multi() {   // returns the grid points beyond the LDS areas of k_ensi_multi
+        static constexpr void (*forms[3])(MultiArgs) = {k_ensi_multi<1>, k_ensi_multi<2>, k_ensi_multi<3>};
+        hipLaunchKernelGGL(forms[variant - 1], dim3(multi_wgs()), dim3(256), 0, stream(), ma);
+        GPP_HIP(hipGetLastError());
+        int nhuge = 0;
+        GPP_HIP(hipMemcpyAsync(&nhuge, ws.big_count.p + 1, sizeof(int), hipMemcpyDeviceToHost, stream()));
+        GPP_HIP(hipStreamSynchronize(stream()));
+        return nhuge;
+    }
+    void run_multi_huge(const bool all, const int nhuge) {   // the general kernel over the huge list, or (all) over every grid point
+        static constexpr void (*forms[3])(MultiArgs, const int*, const int*) = {k_ensi_multi_huge<1>, k_ensi_multi_huge<2>, k_ensi_multi_huge<3>};
+        const size_t ncap = (variant == 3) ? 0 : (size_t)((max_points > 0) ? std::min(max_points, S) : S);
+        const size_t stride = std::max(ncap * (ncap + 1) + (size_t)nV, 2 * (size_t)nV * nV + 6 * (size_t)nV);
+        const HugeScratch hs = huge_scratch(S, stride * sizeof(double), nhuge);
+        if(!hs.nwg) runtime("optimal_interpolation_ensi_multi: a grid point may select " + std::to_string(ncap) + " observations: its system does not fit the scratch budget of the GPU path");
+        a.huge_kcap = hs.kcap; ma.huge_ncap = (int)ncap; ma.huge_stride = stride;
+        a.huge_keys = ws.huge_keys.get((size_t)hs.nwg * hs.kcap);
+        a.huge_mat = ws.huge_mat.get((size_t)hs.nwg * stride);
+        hipLaunchKernelGGL(forms[variant - 1], dim3(hs.nwg), dim3(256), 0, stream(), ma, all ? nullptr : a.huge_list, all ? nullptr : a.big_count + 1);
+        GPP_HIP(hipGetLastError());
+    }
+};
+}
+
+extern "C" int gpp_optimal_interpolation_ensi(gpp_points* bgrid, const float* background, int ne, gpp_points* points,
+                                              const float* obs, const float* sigmas, const float* background_at_points,
+                                              const gpp_structure* st, int max_points, int allow_extrapolation,
+                                              float* out, int mem) {
+    GPP_TRY
+    EnsiCall c{bgrid, background, ne, points, st, max_points, allow_extrapolation, out, mem, 0};
+    c.check_args();
+    ensure_device();
+    g_ensi_ms = 0;
+    g_ensi_stats = gpp_ensi_stats{(long long)c.C, 0, 0, 0.0f};
+    if(c.C == 0 || c.E == 0) return GPP_OK;
+    c.copy_background();
+    if(c.S == 0) { c.finish_early(); return GPP_OK; }    // oi_ensi.cpp:135-137
+    c.stage_obs(obs, sigmas, background_at_points);
+    c.valid_members({{c.f_bg.d, c.nbg}});
+    if(c.nV == 0) { c.finish_early(); return GPP_OK; }
+    c.prep_obs();
+    c.plan_tiles();
+    c.bind_scan();
+    c.tune_scan();
+    if(c.big_ok) c.big_lists();
+    c.start_clock();
+    c.run_tiles();   // k_ensi_pair takes any number of valid members
+    if(c.big_ok) c.run_big();
+    int err = 0; unsigned long long npass = 0;
+    c.finish(err, &npass);
+    // grid points the call left untouched because their E x E system is singular or not finite (the reference's "Condition number error in
+    // N points. Using raw values in those points.", oi_ensi.cpp:386-390,557-561; the mirrors print it): with fewer than two valid members
+    // that is every grid point with an observation in range, the large-n cells (all of them have observations) included
+    g_ensi_stats.kernel_ms = g_ensi_ms;
+    g_ensi_stats.condition_passthrough = (long long)npass + ((c.nV <= 1 && c.big_ok) ? (long long)c.nbig_cells : 0);
+    c.print_stats();
+    if(err & 1) runtime(c.big_ok ? "Internal error. optimal_interpolation_ensi: candidate scratch of the general kernel too small"
+                                 : "optimal_interpolation_ensi: a grid point has more usable observations than the 32-row tile kernel holds and the large-n kernels are switched off (GPP_ENSI_NO_BIG)");
     return GPP_OK;
     GPP_CATCH
 }
@@ -1085,127 +1189,27 @@ extern "C" int gpp_optimal_interpolation_ensi_multi(int variant, gpp_points* bgr
                                                     const float* pratios, const float* pbackground, const float* pbackground_corr,
                                                     const gpp_structure* st, int max_points, int allow_extrapolation, float* out, int mem) {
     GPP_TRY
+    EnsiCall c{bgrid, background, ne, points, st, max_points, allow_extrapolation, out, mem, variant};
     if(variant < 1 || variant > 3) invalid("variant must be 1 (ebe), 2 (ebesc) or 3 (utem)");
-    if(max_points < 0) invalid("max_points must be >= 0");                                      // :341-342
-    if(!bgrid || !points) invalid("grid/points handle is NULL");
-    if(bgrid->type != points->type)
-        invalid("Both background and observations points must be of same coorindate type (lat/lon or x/y)");
-    if(!st) invalid("structure is NULL");
-    if(ne < 0) invalid("negative ensemble size");
+    c.check_args();
     if(mem & GPP_HOST_F64) invalid("GPP_HOST_F64 is not supported by optimal_interpolation_ensi_multi");
-    const bool corr = variant != 2;
-    const int C = bgrid->n, S = points->n, E = ne;
     ensure_device();
     g_ensi_ms = 0;
-    if(C == 0 || E == 0) return GPP_OK;
-    EnsiWorkspace& ws = g_ews;
-    InField f_bg, f_bgc, f_br, f_obs, f_pr, f_pbg, f_pbgc;
-    OutField f_out;
-    f_bg.bind(background, (size_t)C * E, mem);
-    f_out.bind(out, (size_t)C * E, mem);
-    const long nbg = (long)C * E;
-    hipLaunchKernelGGL(k_copy, dim3((unsigned)((nbg + 255) / 256)), dim3(256), 0, stream(), f_bg.d, nbg, f_out.d);   // output = background (:375)
-    GPP_HIP(hipGetLastError());
-    if(S == 0) { f_out.finish(); GPP_HIP(hipStreamSynchronize(stream())); return GPP_OK; }        // :361-363
-    if(corr) { f_bgc.bind(background_corr, (size_t)C * E, mem); f_pbgc.bind(pbackground_corr, (size_t)S * E, mem); }
-    f_br.bind(bratios, C, mem);
-    f_obs.bind(pobs, variant == 3 ? (size_t)S : (size_t)S * E, mem);
-    f_pr.bind(pratios, S, mem);
-    f_pbg.bind(pbackground, (size_t)S * E, mem);
-    bgrid->to_device();
-    gpp_obs_index* ix = gpp_build_obs_index(points);
-    // members valid in every field (:395-418)
-    std::vector<int> flags(E, 1);
-    ws.flags.upload(flags.data(), E);
-    const long npb = (long)S * E;
-    hipLaunchKernelGGL(k_ensi_member_flags, dim3((unsigned)((nbg + 255) / 256)), dim3(256), 0, stream(), f_bg.d, nbg, E, ws.flags.p);
-    hipLaunchKernelGGL(k_ensi_member_flags, dim3((unsigned)((npb + 255) / 256)), dim3(256), 0, stream(), f_pbg.d, npb, E, ws.flags.p);
-    if(corr) {
-        hipLaunchKernelGGL(k_ensi_member_flags, dim3((unsigned)((nbg + 255) / 256)), dim3(256), 0, stream(), f_bgc.d, nbg, E, ws.flags.p);
-        hipLaunchKernelGGL(k_ensi_member_flags, dim3((unsigned)((npb + 255) / 256)), dim3(256), 0, stream(), f_pbgc.d, npb, E, ws.flags.p);
-    }
-    GPP_HIP(hipMemcpyAsync(flags.data(), ws.flags.p, sizeof(int) * E, hipMemcpyDeviceToHost, stream()));
-    GPP_HIP(hipStreamSynchronize(stream()));
-    std::vector<int> valid;
-    for(int e = 0; e < E; e++) if(flags[e]) valid.push_back(e);
-    const int nV = (int)valid.size();
-    if(nV == 0) { f_out.finish(); GPP_HIP(hipStreamSynchronize(stream())); return GPP_OK; }      // :419-420
-    if(nV > 16384) runtime("optimal_interpolation_ensi_multi: more than 16384 valid ensemble members are not supported on the GPU path (the general kernel stages one row of Y in 64 KB of LDS)");
-    if(variant == 1 && nV > 4096) runtime("optimal_interpolation_ensi_multi_ebe: more than 4096 valid ensemble members are not supported on the GPU path");
-    ws.validIdx.upload(valid.data(), nV);
-    ws.gYhat.get(S); ws.gY.get((size_t)S * nV); ws.gYm.get((size_t)S * nV); ws.obs0.get(S);
-    hipLaunchKernelGGL(k_multi_obs_prep, dim3((S + 127) / 128), dim3(128), 0, stream(), variant, f_pbg.d, corr ? f_pbgc.d : f_pbg.d, f_obs.d, S, E,
-                       (const int*)ws.validIdx.p, nV, ws.gY.p, ws.gYm.p, ws.gYhat.p, ws.obs0.p);
-    ws.pgeo.get(S); ws.oaux.get(S);
-    // oaux = (laf, obs[.][0] / obs, gYhat, pratio); an observation is usable when that first value is valid (:480)
-    hipLaunchKernelGGL(k_pack_obs, dim3((S + 255) / 256), dim3(256), 0, stream(), S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p,
-                       (const float*)ws.obs0.p, f_pr.d, (const float*)ws.gYhat.p, (const float*)nullptr, 0, ws.pgeo.p, ws.oaux.p);
-    GPP_HIP(hipGetLastError());
-    ws.err.get(1);
-    GPP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(int), stream()));
-    if(!ws.e0) { GPP_HIP(hipEventCreate(&ws.e0)); GPP_HIP(hipEventCreate(&ws.e1)); }
-    MultiArgs ma = MultiArgs();
-    EnsiArgs& a = ma.e;
-    a.gx = bgrid->d_x.p; a.gy = bgrid->d_y.p; a.gz = bgrid->d_z.p; a.gelev = bgrid->d_elev.p; a.glaf = bgrid->d_laf.p;
-    a.bg = f_bg.d; a.out = f_out.d;
-    a.C = C; a.E = E;
-    a.s.pgeo = ws.pgeo.p; a.s.smeta = ix->d_smeta.p; a.s.bin_start = ix->d_bin_start.p;
-    a.s.axis_a = ix->axis_a; a.s.axis_b = ix->axis_b; a.s.nbx = ix->nbx; a.s.nby = ix->nby;
-    a.s.amin = ix->amin; a.s.bmin = ix->bmin; a.s.inv_s = ix->inv_s;
-    a.s.st = gpp_resolve_structure(st);
-    gpp_bind_field(a.s.st, st, bgrid, points, ws.cell_idx, ws.obs_idx);
-    if(a.s.st.fh) runtime("optimal_interpolation_ensi_multi: spatially varying structure functions are not supported on the GPU path");
-    a.s.max_points = max_points;
-    a.ogeo = ix->d_ogeo.p; a.oaux = ws.oaux.p;
-    a.gY = ws.gY.p; a.validIdx = ws.validIdx.p; a.nV = nV; a.valid_identity = (nV == E) ? 1 : 0;
-    a.allow_extrap = allow_extrapolation ? 1 : 0;
-    a.err = ws.err.p;
-    ma.gYm = ws.gYm.p; ma.bgc = corr ? f_bgc.d : f_bg.d; ma.bratios = f_br.d;
-    ma.pobs2 = f_obs.d; ma.pbg2 = f_pbg.d;
-    ma.oob = (variant != 3 && valid[nV - 1] != nV - 1) ? 1 : 0;
-    const int nwg = std::min(C, 2048);
-    a.big_keys = ws.big_keys.get((size_t)nwg * EBIG_CAND);
-    a.big_list = ws.big_list.get(2 * (size_t)C); a.huge_list = a.big_list + C; a.big_count = ws.big_count.get(2);
-    GPP_HIP(hipMemsetAsync(ws.big_count.p, 0, 2 * sizeof(int), stream()));
-    GPP_HIP(hipEventRecord(ws.e0, stream()));
-    const bool all_huge = variant == 3 && nV > EMAXV;   // utem keeps one member per lane in k_ensi_multi: more go to the general kernel
-    if(!all_huge) {
-        if(variant == 1) hipLaunchKernelGGL(k_ensi_multi<1>, dim3(nwg), dim3(256), 0, stream(), ma);
-        else if(variant == 2) hipLaunchKernelGGL(k_ensi_multi<2>, dim3(nwg), dim3(256), 0, stream(), ma);
-        else hipLaunchKernelGGL(k_ensi_multi<3>, dim3(nwg), dim3(256), 0, stream(), ma);
-        GPP_HIP(hipGetLastError());
-    }
-    int nhuge = C;
-    if(!all_huge) {
-        GPP_HIP(hipMemcpyAsync(&nhuge, ws.big_count.p + 1, sizeof(int), hipMemcpyDeviceToHost, stream()));
-        GPP_HIP(hipStreamSynchronize(stream()));
-    }
-    if(nhuge > 0) {   // the grid points beyond the LDS areas of k_ensi_multi: scratch sized for this call, within a budget
-        int kcap = 1;
-        while(kcap < S) kcap <<= 1;
-        const size_t ncap = (variant == 3) ? 0 : (size_t)((max_points > 0) ? std::min(max_points, S) : S);
-        const size_t stride = std::max(ncap * (ncap + 1) + (size_t)nV, 2 * (size_t)nV * nV + 6 * (size_t)nV);
-        size_t budget = (size_t)16 << 30;
-        if(path_env("GPP_OI_HUGE_BUDGET_MB")) budget = (size_t)atol(path_env("GPP_OI_HUGE_BUDGET_MB")) << 20;
-        const size_t per_wg = stride * sizeof(double) + (size_t)kcap * sizeof(unsigned long long);
-        if(per_wg > budget) runtime("optimal_interpolation_ensi_multi: a grid point may select " + std::to_string(ncap) + " observations: its system does not fit the scratch budget of the GPU path");
-        const int hwg = (int)std::max<size_t>(1, std::min<size_t>({(size_t)nhuge, (size_t)512, budget / per_wg}));
-        ma.e.huge_kcap = kcap; ma.huge_ncap = (int)ncap; ma.huge_stride = stride;
-        ma.e.huge_keys = ws.huge_keys.get((size_t)hwg * kcap);
-        ma.e.huge_mat = ws.huge_mat.get((size_t)hwg * stride);
-        const int* list = all_huge ? nullptr : a.huge_list;
-        const int* cnt = all_huge ? nullptr : a.big_count + 1;
-        if(variant == 1) hipLaunchKernelGGL(k_ensi_multi_huge<1>, dim3(hwg), dim3(256), 0, stream(), ma, list, cnt);
-        else if(variant == 2) hipLaunchKernelGGL(k_ensi_multi_huge<2>, dim3(hwg), dim3(256), 0, stream(), ma, list, cnt);
-        else hipLaunchKernelGGL(k_ensi_multi_huge<3>, dim3(hwg), dim3(256), 0, stream(), ma, list, cnt);
-        GPP_HIP(hipGetLastError());
-    }
-    GPP_HIP(hipEventRecord(ws.e1, stream()));
+    if(c.C == 0 || c.E == 0) return GPP_OK;
+    c.copy_background();
+    if(c.S == 0) { c.finish_early(); return GPP_OK; }    // oi_ensi_multi.cpp:361-363
+    c.stage_multi(bratios, background_corr, pobs, pratios, pbackground, pbackground_corr);
+    c.multi_valid_members();
+    if(c.nV == 0) { c.finish_early(); return GPP_OK; }   // :419-420
+    c.prep_multi_obs();
+    c.fill_multi_args();
+    c.big_lists();
+    c.start_clock();
+    const bool all_huge = variant == 3 && c.nV > EMAXV;   // utem keeps one member per lane in k_ensi_multi: more go to the general kernel
+    const int nhuge = all_huge ? c.C : c.launch_multi();
+    if(nhuge > 0) c.run_multi_huge(all_huge, nhuge);   // scratch sized for this call, within a budget
     int err = 0;
-    GPP_HIP(hipMemcpyAsync(&err, ws.err.p, sizeof(int), hipMemcpyDeviceToHost, stream()));
-    f_out.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    GPP_HIP(hipEventElapsedTime(&g_ensi_ms, ws.e0, ws.e1));
+    c.finish(err);
     if(err & 4) runtime("optimal_interpolation_ensi_multi: an ensemble member is invalid in front of a valid one: the reference indexes its innovation matrix with the original member index (oi_ensi_multi.cpp:565), which is out of bounds");
     if(err & 2) runtime("optimal_interpolation_ensi_multi: singular matrix at a grid point (arma::inv fails in the reference)");
     if(err & 1) runtime("Internal error. optimal_interpolation_ensi_multi: scratch of the general kernel too small");

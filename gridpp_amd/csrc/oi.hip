@@ -1600,18 +1600,14 @@ struct OiCall {
     // structure to k_oi_huge (pivoted elimination in HBM scratch, no capacity of its own)
     void run_huge(const int* d_list, const int* d_count, const int ncells) {
         // scratch for the worst case of this call: every observation a candidate, max_points (or all of them) selected
-        size_t kcap = 1; while(kcap < (size_t)S) kcap <<= 1;
         const size_t ncap = (max_points > 0) ? (size_t)std::min(max_points, S) : (size_t)S;
-        const size_t per_wg = ncap * (ncap + 2) * sizeof(double) + kcap * sizeof(unsigned long long);
-        size_t budget = (size_t)16 << 30;   // 16 GB of the 288 GB for this rarely used path
-        if(path_env("GPP_OI_HUGE_BUDGET_MB")) budget = (size_t)atol(path_env("GPP_OI_HUGE_BUDGET_MB")) << 20;
-        if(per_wg > budget) runtime("optimal_interpolation: a grid point may select more observations than the scratch budget of the general kernel holds (set max_points, or raise GPP_OI_HUGE_BUDGET_MB)");
-        const int nwg = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)ncells, 512), budget / per_wg));
-        a.huge_kcap = (int)kcap; a.huge_ncap = (int)ncap;
-        a.huge_keys = ws.huge_keys.get((size_t)nwg * kcap);
-        a.huge_mat = ws.huge_mat.get((size_t)nwg * ncap * (ncap + 2));
-        if(spatial) hipLaunchKernelGGL(k_oi_huge<true>, dim3(nwg), dim3(256), 0, stream(), a, d_list, d_count);
-        else hipLaunchKernelGGL(k_oi_huge<false>, dim3(nwg), dim3(256), 0, stream(), a, d_list, d_count);
+        const HugeScratch hs = huge_scratch(S, ncap * (ncap + 2) * sizeof(double), ncells);
+        if(!hs.nwg) runtime("optimal_interpolation: a grid point may select more observations than the scratch budget of the general kernel holds (set max_points, or raise GPP_OI_HUGE_BUDGET_MB)");
+        a.huge_kcap = hs.kcap; a.huge_ncap = (int)ncap;
+        a.huge_keys = ws.huge_keys.get((size_t)hs.nwg * hs.kcap);
+        a.huge_mat = ws.huge_mat.get((size_t)hs.nwg * ncap * (ncap + 2));
+        if(spatial) hipLaunchKernelGGL(k_oi_huge<true>, dim3(hs.nwg), dim3(256), 0, stream(), a, d_list, d_count);
+        else hipLaunchKernelGGL(k_oi_huge<false>, dim3(hs.nwg), dim3(256), 0, stream(), a, d_list, d_count);
         GPP_HIP(hipGetLastError());
     }
     void launch_union(const long items, const bool list, hipStream_t on) {   // the scalar tile kernel, one wave per work item

@@ -1,6 +1,7 @@
 // Shared by oi.hip and ensi.hip: observation index, Barnes device functions, the per-tile candidate scan.
 #pragma once
 #include "common.h"
+#include <algorithm>
 
 #pragma clang fp contract(off)
 using gpp::DevBuf;
@@ -37,6 +38,21 @@ int gpp_tile_wshift(gpp_points* grid);   // oi.hip
 struct DevStructure;
 DevStructure gpp_resolve_structure(const gpp_structure* s);   // oi.hip: validation + localization distance
 void gpp_bind_field(DevStructure& d, const gpp_structure* s, gpp_points* bgrid, gpp_points* points, gpp::DevBuf<int>& cbuf, gpp::DevBuf<int>& obuf);
+
+// Scratch of the general ("huge") kernels (k_oi_huge, k_ensi_huge, k_ensi_multi_huge): no capacity of their own, sized per call.  A
+// workgroup holds a candidate key for every observation (kcap of them: the next power of two >= S) and mat_bytes_per_wg of matrices;
+// all workgroups together stay within 16 GB of the 288 GB (GPP_OI_HUGE_BUDGET_MB) -- fewer workgroups when a grid point needs much,
+// nwg == 0 when one alone (per_wg bytes) does not fit: the caller throws its own message.
+struct HugeScratch { int kcap, nwg; size_t per_wg; };
+inline HugeScratch huge_scratch(const int S, const size_t mat_bytes_per_wg, const int nitems) {
+    int kcap = 1;
+    while(kcap < S) kcap <<= 1;
+    const size_t per_wg = mat_bytes_per_wg + (size_t)kcap * sizeof(unsigned long long);
+    size_t budget = (size_t)16 << 30;
+    if(gpp::path_env("GPP_OI_HUGE_BUDGET_MB")) budget = (size_t)atol(gpp::path_env("GPP_OI_HUGE_BUDGET_MB")) << 20;
+    if(per_wg > budget) return {kcap, 0, per_wg};
+    return {kcap, (int)std::max<size_t>(1, std::min<size_t>({(size_t)nitems, (size_t)512, budget / per_wg})), per_wg};
+}
 
 // -------------------------------------------------------------------------------------------
 // device helpers
