@@ -1132,7 +1132,8 @@ struct EnsiCall {
     void run_multi_huge(const bool all, const int nhuge) {   // the general kernel over the huge list, or (all) over every grid point
         static constexpr void (*forms[3])(MultiArgs, const int*, const int*) = {k_ensi_multi_huge<1>, k_ensi_multi_huge<2>, k_ensi_multi_huge<3>};
         const size_t ncap = (variant == 3) ? 0 : (size_t)((max_points > 0) ? std::min(max_points, S) : S);
-        const size_t stride = std::max(ncap * (ncap + 1) + (size_t)nV, 2 * (size_t)nV * nV + 6 * (size_t)nV);
+        // ebe / ebesc: the system with its right-hand side, then xL; utem: Pinv, the eigenvectors and six vectors of nV
+        const size_t stride = (variant == 3) ? 2 * (size_t)nV * nV + 6 * (size_t)nV : ncap * (ncap + 1) + (size_t)nV;
         const HugeScratch hs = huge_scratch(S, stride * sizeof(double), nhuge);
         if(!hs.nwg) runtime("optimal_interpolation_ensi_multi: a grid point may select " + std::to_string(ncap) + " observations: its system does not fit the scratch budget of the GPU path");
         a.huge_kcap = hs.kcap; ma.huge_ncap = (int)ncap; ma.huge_stride = stride;

@@ -7,7 +7,7 @@
 //                 every member e (any number of members), the anti-extrapolation clamp, out = background + dx;
 //   utem        : the E x E square-root filter of optimal_interpolation_ensi with Pinv = Yc^T Rinv Yc + I, Rinv = rho / pratio,
 //                 W' = ensStd sqrt((E-1) P) + ratio w 1^T applied to the normalised perturbations of background_corr
-//                 (E <= 64 valid members, n <= 512).
+//                 (E <= 64 valid members; any n up to the EBIG_CAND candidates of the LDS sort, 64 observations at a time).
 // These functions have no performance configuration in BASELINE.json; the kernel is written for correctness first.
 #pragma once
 

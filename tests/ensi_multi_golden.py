@@ -21,10 +21,20 @@ CASES = load()
 NAMES = sorted(CASES)
 
 
-def check(out, case):
-    exp = case["expected"].reshape(out.shape)
+def compare(out, exp):
+    """The measure of every ensi_multi comparison: the NaN pattern of the expected values, and |out - exp| / max(|exp|, 1e-2) < RTOL
+    on every other value.  Returns the largest such error."""
+    exp = exp.reshape(out.shape)
     assert (np.isnan(out) == np.isnan(exp)).all()
     m = ~np.isnan(exp)
+    if not m.any():
+        return 0.0
     err = np.abs(out[m].astype(np.float64) - exp[m].astype(np.float64)) / np.maximum(np.abs(exp[m]), 1e-2)
+    print("ensi_multi: largest error %.3g at value %d of %d" % (err.max(), int(np.flatnonzero(m.ravel())[err.argmax()]), m.size))
     assert err.max() < RTOL, err.max()
+    return float(err.max())
+
+
+def check(out, case):
+    compare(out, case["expected"])
     assert np.nanmax(np.abs(out - case["background"].reshape(out.shape))) > 0.05

@@ -13,13 +13,14 @@ def _run(c, grid_overload):
     h, v, w, mp, allow = c["params"]
     variant = str(c["variant"])
     Y, X, E = [int(t) for t in c["shape"]]
-    points = gridpp.Points(c["plat"], c["plon"], c["pelev"], c["plaf"])
+    ctype = int(c["ctype"]) if "ctype" in c else gridpp.Geodetic   # (tests/ensi_multi_cases.py: Cartesian cases)
+    points = gridpp.Points(c["plat"], c["plon"], c["pelev"], c["plaf"], ctype)
     st = gridpp.BarnesStructure(h, v, w)
     if grid_overload:
-        b = gridpp.Grid(c["blat"].reshape(Y, X), c["blon"].reshape(Y, X), c["belev"].reshape(Y, X), c["blaf"].reshape(Y, X))
+        b = gridpp.Grid(c["blat"].reshape(Y, X), c["blon"].reshape(Y, X), c["belev"].reshape(Y, X), c["blaf"].reshape(Y, X), ctype)
         br, bg, bgc = c["bratios"].reshape(Y, X), c["background"].reshape(Y, X, E), c["background_corr"].reshape(Y, X, E)
     else:
-        b = gridpp.Points(c["blat"], c["blon"], c["belev"], c["blaf"])
+        b = gridpp.Points(c["blat"], c["blon"], c["belev"], c["blaf"], ctype)
         br, bg, bgc = c["bratios"], c["background"], c["background_corr"]
     if variant == "ebe":
         out = gridpp.optimal_interpolation_ensi_multi_ebe(b, br, bg, bgc, points, c["pobs"], c["pratios"], c["pbackground"], c["pbackground_corr"], st, int(mp), bool(allow))
@@ -42,8 +43,6 @@ def test_ensi_multi_golden_vectors(name, grid_overload):
 @pytest.mark.parametrize("variant", ["ebe", "ebesc", "utem"])
 def test_ensi_multi_random_vs_oracle(variant):
     from oracle import oracle as O
-    import sys, os
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     rng = np.random.default_rng(7)
     n, E, S = 300, 12, 70
     blat, blon = rng.random(n).astype(np.float32), rng.random(n).astype(np.float32)
