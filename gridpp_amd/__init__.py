@@ -1586,6 +1586,38 @@ def neighbourhood_quantile_ens_fast(input, quantile, halfwidth, thresholds):
     return neighbourhood_quantile_fast(input, quantile, halfwidth, thresholds)
 
 
+# ---- window statistics along the time axis (include/gridpp.h:1602-1611, src/api/window.cpp) -----------
+_WINDOW_STATISTICS = (Mean, Min, Median, Max, Std, Variance, Sum, Count, RandomChoice)
+
+
+def window(array, length, statistic, before=False, keep_missing=False, missing_edges=True):
+    """src/api/window.cpp:6-156: the statistic over a window of `length` time steps for every (case, time) of a 2-D array; the
+    window ends at the time step (before) or is centred on it (an odd length), clipped to the row.  Mean / Sum / Count are
+    differences of the row's sequential float32 prefix sum, as in the reference; Count ignores keep_missing and missing_edges.
+    keep_missing: NaN where the window holds a missing value; missing_edges: NaN where the window overshoots the row.
+    (0, T) gives (0, 0) and (Y, 0) gives (Y, 0), as there.  Quantile and Unknown raise RuntimeError (the reference throws
+    inside its loop; here before any device work)."""
+    if length <= 0:
+        raise ValueError("Length variable must be > 0")
+    dev = _is_dev(array)
+    arr = _vec(array, 2, "array") if dev else _vec(array, 2, "array", np.float64 if _wants_f64(array) else np.float32)
+    ny, nx = _shape(arr)
+    if ny == 0 or nx == 0:
+        return _empty_like_field((0, 0) if ny == 0 else (ny, 0), arr)
+    if length % 2 == 0 and not before:
+        raise ValueError("Length variable must be an odd number")
+    if statistic not in _WINDOW_STATISTICS:
+        raise RuntimeError("Internal error. Cannot compute statistic")
+    mem = _mem(arr)
+    _sync_if_dev(mem)
+    if not dev and arr.dtype == np.float64:
+        mem |= _capi.HOST_F64
+    out = _empty_like_field((ny, nx), arr)
+    check(lib().gpp_window(_ptr(arr), ny, nx, int(length), int(statistic), int(bool(before)), int(bool(keep_missing)), int(bool(missing_edges)),
+                           _ptr(out), mem))
+    return out
+
+
 # ---- util (include/gridpp.h:1454-1482, src/api/util.cpp) ---------------------------------------------
 def calc_statistic(array, statistic):
     """gridpp::calc_statistic for a vector (-> float) or a 2-D array (-> one value per row)."""

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("GPP_LIB") or os.path.join(_HERE, "lib", "libgridpp_hi
 GPP_OK, GPP_EINVAL, GPP_ERUNTIME, GPP_ENODEVICE = 0, -1, -2, -3
 MEM_HOST, MEM_DEVICE, ASYNC, HOST_F64, Q_HOST = 0, 1, 2, 4, 8
 ENSEMBLE_ROW_CAP = 1024   # GPP_ENSEMBLE_ROW_CAP of include/gridpp_hip.h
+WINDOW_TILE_ROWS, WINDOW_TILE_COLS, WINDOW_FUSED_SPAN = 64, 32, 31   # GPP_WINDOW_* of include/gridpp_hip.h
 
 
 class gpp_structure(C.Structure):
@@ -112,6 +113,7 @@ SIGNATURES = {
     "gpp_neighbourhood": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
     "gpp_neighbourhood_brute_force": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int],
     "gpp_neighbourhood_quantile_fast": [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_window": [vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
 }
 STRING_GETTERS = ("gpp_last_error", "gpp_version")
 

@@ -1014,6 +1014,21 @@ inline vec monotonize_curve(vec curve_ref, vec curve_fcst, vec& output_fcst) {
     return out_ref;
 }
 
+// ---- window statistics along the time axis (include/gridpp.h:1602-1611) ------------------------------------------------
+// src/api/window.cpp:6-156: array is (case, time).  std::invalid_argument for length <= 0 and, for a non-empty array, for an even
+// length without `before`; std::runtime_error for Quantile / Unknown (thrown inside the reference's loop, here before device work).
+inline vec2 window(const vec2& array, int length, Statistic statistic, bool before = false, bool keep_missing = false, bool missing_edges = true) {
+    if(length <= 0) throw std::invalid_argument("Length variable must be > 0");
+    size_t Y, T;
+    vec a = detail::flatten(array, Y, T);
+    if(Y == 0) return vec2();        // window.cpp:14-17
+    if(T == 0) return vec2(Y);       // :19-22
+    vec out(Y * T, MV);
+    detail::check(gpp_window(a.data(), (long long)Y, (int)T, length, (int)statistic, before ? 1 : 0, keep_missing ? 1 : 0, missing_edges ? 1 : 0, out.data(),
+                             GPP_MEM_HOST));
+    return detail::unflatten(out, Y, T);
+}
+
 // ---- util (include/gridpp.h:1454-1482) -----------------------------------------------------------------------------
 inline float calc_statistic(const vec& array, Statistic statistic) {
     float out = MV;

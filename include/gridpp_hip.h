@@ -53,7 +53,7 @@ extern "C" {
  * gpp_full_gradient, gpp_downscale_probability, gpp_mask_threshold_downscale (the cubes and the threshold) and gpp_smart
  * (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
  * (their float fields), by gpp_neighbourhood_quantile_fast for `input` only, by gpp_apply_curve and gpp_interpolate for the values
- * (their curves are host float32 arrays) and by gpp_apply_curve_field for the values and both curve slabs. */
+ * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs and by gpp_window for `array`. */
 #define GPP_HOST_F64 4
 
 /* include/gridpp.h:120-123 */
@@ -439,6 +439,25 @@ int gpp_calc_quantile(const float* array, long rows, int len, const float* quant
  * gridpp::get_neighbourhood_thresholds (neighbourhood.cpp:243-295) over the n
  * values of a flattened field.  out holds num floats; *count = number written. */
 int gpp_calc_even_quantiles(const float* values, long n, int num, int only_valid, float* out, int* count, int mem);
+
+/* ---- window statistics along the time axis (src/api/window.cpp) -----------------
+ * gridpp::window (src/api/window.cpp:6-156, include/gridpp.h:1602-1611): array and out are [ny][nx] = (case, time) with time
+ * contiguous; out[y][x] = the statistic over the window [x - length + 1, x] (before != 0) or [x - length / 2, x + length / 2] of row
+ * y, clipped to the row.  NaN and +-Inf do not count (util.cpp:16-18).  GPP_MEAN / GPP_SUM / GPP_COUNT take differences of the row's
+ * sequential float32 prefix sum, as the reference does (window.cpp:33-111: the result is that difference, not the exact window sum);
+ * Count ignores the two flags.  GPP_MIN / GPP_MAX / GPP_MEDIAN / GPP_STD / GPP_VARIANCE / GPP_RANDOMCHOICE are calc_statistic over the
+ * clipped window (window.cpp:112-153).  keep_missing: NaN where the window holds a value that does not count; missing_edges: NaN where
+ * the window reaches past either end of the row.  Checks in the reference's order, all before any device work: GPP_EINVAL "Length
+ * variable must be > 0"; ny * nx == 0 returns GPP_OK and writes nothing; GPP_EINVAL "Length variable must be an odd number" (an even
+ * length with before == 0); GPP_ERUNTIME for GPP_QUANTILE and any value that is no statistic (the reference throws inside its loop).
+ * array / out follow `mem` (GPP_HOST_F64 honoured for array).  Any length and any nx: spans that do not fit the fused tile
+ * (GPP_WINDOW_FUSED_SPAN) take a general path with the same results. */
+#define GPP_WINDOW_TILE_ROWS 64    /* rows of a tile of the fused kernels */
+#define GPP_WINDOW_TILE_COLS 32    /* columns of a chunk of a tile */
+#define GPP_WINDOW_FUSED_SPAN 31   /* fused while back + lead <= this: back = length - 1 (before) or length / 2, lead = 0 (before) or
+                                    * length / 2 rounded up to a multiple of 4, both after clamping length / 2 and length - 1 to nx */
+int gpp_window(const float* array, long long ny, int nx, int length, int statistic, int before, int keep_missing, int missing_edges,
+               float* out, int mem);
 
 /* per-call statistics of the last OI call on this thread (diagnostics / bench) */
 typedef struct gpp_oi_stats {
