@@ -1618,6 +1618,90 @@ def window(array, length, statistic, before=False, keep_missing=False, missing_e
     return out
 
 
+# ---- verification scores (include/gridpp.h:103-110; src/api/metric_optimizer.cpp:185-244, neighbourhood_score.cpp) ----
+Ets, Ts, Kss, Pc, Bias, Hss = 0, 1, 20, 30, 40, 50
+_METRICS = (Ets, Ts, Kss, Pc, Bias, Hss)
+
+
+def _metric(metric):
+    if metric not in _METRICS:
+        raise ValueError("Unknown metric")
+    return int(metric)
+
+
+def _score_vector(a, name):
+    if _is_dev(a):
+        import torch
+        if a.dim() != 1:
+            raise RuntimeError("%s must have 1 dimension" % name)
+        return a.contiguous().to(torch.float32)
+    return _vec(a, 1, name)
+
+
+def calc_score(*args):
+    """src/api/metric_optimizer.cpp:185-244, the three overloads of include/gridpp.h:
+
+    calc_score(a, b, c, d, metric): the score of a contingency table, host arithmetic with the reference's float / double promotions.
+    calc_score(ref, fcst, threshold, metric) and calc_score(ref, fcst, threshold, fthreshold, metric): the table of the first
+    len(fcst) elements (counted on the GPU; numpy arrays or torch CUDA tensors), then the same rule.  A NaN ref is counted nowhere, a NaN
+    fcst as c or d, and every count stops at 2**24, all as in the reference.  The five-argument forms are told apart by whether the first
+    argument is a scalar.  A ref shorter than fcst is read out of bounds by the reference; here it raises ValueError("ref and fcst not the
+    same size").  Empty vectors need no GPU: Bias is 1, every other metric NaN."""
+    if len(args) not in (4, 5):
+        raise TypeError("calc_score takes 4 or 5 arguments")
+    out = C.c_float()
+    if len(args) == 5 and not _is_dev(args[0]) and np.ndim(args[0]) == 0:
+        a, b, c, d, metric = args
+        check(lib().gpp_calc_score_table(float(a), float(b), float(c), float(d), _metric(metric), C.byref(out)))
+        return out.value
+    if len(args) == 4:
+        ref, fcst, threshold, metric = args
+        fthreshold = threshold
+    else:
+        ref, fcst, threshold, fthreshold, metric = args
+    metric = _metric(metric)
+    ref, fcst = _score_vector(ref, "ref"), _score_vector(fcst, "fcst")
+    n = _shape(fcst)[0]
+    if _shape(ref)[0] < n:
+        raise ValueError("ref and fcst not the same size")
+    mem = _mem(ref, fcst) if n else _capi.MEM_HOST
+    if n:
+        _sync_if_dev(mem)
+    check(lib().gpp_calc_score(_ptr(ref), _ptr(fcst), n, float(threshold), float(fthreshold), metric, C.byref(out), mem))
+    return out.value
+
+
+def neighbourhood_score(grid, points, fcst, ref, half_width, metric, threshold):
+    """src/api/neighbourhood_score.cpp:6-60: the score of every grid cell over the (2 half_width + 1)^2 cells around it (clipped to the
+    grid): the observations `ref` at `points` are gridded (gridding_nearest, min_num 1, Mean), a cell counts where that and `fcst` are
+    both finite, and the fractions of a / b / c / d cells of the window go through calc_score.  fcst: a numpy array or a torch CUDA tensor
+    (the result is then one too); ref: a host vector.  Checks in the reference's order: "Grid size is not the same as forecast values",
+    "half_width must be greater than 0", "Unknown metric", "Points size is not the same as values".  An empty grid gives an empty array."""
+    dev = _is_dev(fcst)
+    f = _vec(fcst, 2, "fcst") if dev else _vec(fcst, 2, "fcst", np.float64 if _wants_f64(fcst) else np.float32)
+    shp = _shape(f)
+    ny, nx = grid.size()
+    if shp[0] != 0 and tuple(shp) != (ny, nx):                 # src/api/util.cpp:427-429
+        raise ValueError("Grid size is not the same as forecast values")
+    if half_width <= 0:
+        raise ValueError("half_width must be greater than 0")
+    metric = _metric(metric)
+    r = _vec(ref, 1, "ref")
+    if r.shape[0] != points.size():
+        raise ValueError("Points size is not the same as values")
+    if ny * nx == 0:
+        return _empty_like_field((ny, nx), f)
+    if shp[0] == 0:   # (the reference reads fcst[0] of an empty vector here)
+        raise ValueError("Grid size is not the same as forecast values")
+    mem = _mem(f)
+    _sync_if_dev(mem)
+    if not dev and f.dtype == np.float64:
+        mem |= _capi.HOST_F64
+    out = _empty_like_field((ny, nx), f)
+    check(lib().gpp_neighbourhood_score(grid._h, points._h, _ptr(f), _ptr(r), int(half_width), metric, float(threshold), _ptr(out), mem))
+    return out
+
+
 # ---- util (include/gridpp.h:1454-1482, src/api/util.cpp) ---------------------------------------------
 def calc_statistic(array, statistic):
     """gridpp::calc_statistic for a vector (-> float) or a 2-D array (-> one value per row)."""

@@ -13,6 +13,7 @@ GPP_OK, GPP_EINVAL, GPP_ERUNTIME, GPP_ENODEVICE = 0, -1, -2, -3
 MEM_HOST, MEM_DEVICE, ASYNC, HOST_F64, Q_HOST = 0, 1, 2, 4, 8
 ENSEMBLE_ROW_CAP = 1024   # GPP_ENSEMBLE_ROW_CAP of include/gridpp_hip.h
 WINDOW_TILE_ROWS, WINDOW_TILE_COLS, WINDOW_FUSED_SPAN = 64, 32, 31   # GPP_WINDOW_* of include/gridpp_hip.h
+SCORE_TILE_COLS, SCORE_TILE_ROWS, SCORE_FUSED_MAXHW = 64, 32, 16   # GPP_SCORE_* of include/gridpp_hip.h
 
 
 class gpp_structure(C.Structure):
@@ -114,6 +115,9 @@ SIGNATURES = {
     "gpp_neighbourhood_brute_force": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int],
     "gpp_neighbourhood_quantile_fast": [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int],
     "gpp_window": [vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
+    "gpp_calc_score_table": [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp],
+    "gpp_calc_score": [vp, vp, C.c_longlong, C.c_float, C.c_float, C.c_int, fp, C.c_int],
+    "gpp_neighbourhood_score": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int],
 }
 STRING_GETTERS = ("gpp_last_error", "gpp_version")
 

@@ -197,6 +197,9 @@ struct gpp_nn_index;    // runtime.hip: uniform-cell index for nearest-neighbour
 // runtime.hip: nearest-neighbour indices of nq device-resident query points in p (exact metric, ties -> lowest index)
 void gpp_nearest_device(gpp_points* p, const float* d_qx, const float* d_qy, const float* d_qz, int nq, int include_match, int* d_out);
 
+// radius.hip: the device steps of gridding_nearest, values and result in HBM (to->n > 0); returns after the stream has run them
+void gpp_gridding_nearest_device(gpp_points* to, gpp_points* from, const float* d_values, int min_num, int statistic, float* d_out);
+
 struct gpp_points {
     int n = 0, ny = 0, nx = 0, type = GPP_GEODETIC;
     std::vector<float> lats, lons, elevs, lafs, x, y, z;   // host copies (float32, as the reference stores them)

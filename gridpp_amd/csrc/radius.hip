@@ -381,28 +381,16 @@ extern "C" int gpp_gridding(gpp_points* to, gpp_points* from, const float* value
     GPP_CATCH
 }
 
-extern "C" int gpp_gridding_nearest(gpp_points* to, gpp_points* from, const float* values, int min_num, int statistic, float* out, int mem) {
-    GPP_TRY
-    ensure_device();
-    check_same_type(from, to);
-    if(min_num < 0) invalid("min_num must be >= 0");   // gridding.cpp:68-69
+// The device steps of gridding_nearest (gridding.cpp:85-131): d_values [size of from] and d_out [size of to] are in HBM; everything is
+// enqueued on the library stream and nothing is waited for.  Shared by gpp_gridding_nearest and gpp_neighbourhood_score (score.hip), which
+// classifies the gridded field where it lies.  to->n > 0.
+void gpp_gridding_nearest_device(gpp_points* to, gpp_points* from, const float* d_values, int min_num, int statistic, float* d_out) {
     const int no = to->n, S = from->n;
-    if(no == 0) {
-        if(S > 0) runtime("gridding_nearest: no output location to assign the points to");   // the reference indexes an empty vector here
-        return GPP_OK;
-    }
-    OutField o;
-    o.bind(out, no, mem);
     if(S == 0) {
-        hipLaunchKernelGGL(k_fill_value, dim3((no + 255) / 256), dim3(256), 0, stream(), o.d, (size_t)no, NAN);
+        hipLaunchKernelGGL(k_fill_value, dim3((no + 255) / 256), dim3(256), 0, stream(), d_out, (size_t)no, NAN);
         GPP_HIP(hipGetLastError());
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        return;
     }
-    if(!values) invalid("values is NULL");
-    InField v;
-    v.bind(values, S, mem);
     from->to_device();
     DevBuf<int> target, starget, order, iota, cnt;
     target.get(S); starget.get(S); order.get(S); iota.get(S); cnt.get(no);
@@ -422,10 +410,31 @@ extern "C" int gpp_gridding_nearest(gpp_points* to, gpp_points* from, const floa
     scan_counts(cnt.p, no, wide, offset);
     DevBuf<float> val;
     val.get(S);
-    hipLaunchKernelGGL(k_gather_sorted, dim3((S + 255) / 256), dim3(256), 0, stream(), v.d, order.p, S, val.p);
+    hipLaunchKernelGGL(k_gather_sorted, dim3((S + 255) / 256), dim3(256), 0, stream(), d_values, order.p, S, val.p);
     hipLaunchKernelGGL(k_segment_statistic, dim3((no + 255) / 256), dim3(256), 0, stream(), val.p, offset.p, 0ll, cnt.p, 0, no, min_num, statistic,
-                       1, o.d);
+                       1, d_out);
     GPP_HIP(hipGetLastError());
+    GPP_HIP(hipStreamSynchronize(stream()));   // the workspaces above are freed on return
+}
+
+extern "C" int gpp_gridding_nearest(gpp_points* to, gpp_points* from, const float* values, int min_num, int statistic, float* out, int mem) {
+    GPP_TRY
+    ensure_device();
+    check_same_type(from, to);
+    if(min_num < 0) invalid("min_num must be >= 0");   // gridding.cpp:68-69
+    const int no = to->n, S = from->n;
+    if(no == 0) {
+        if(S > 0) runtime("gridding_nearest: no output location to assign the points to");   // the reference indexes an empty vector here
+        return GPP_OK;
+    }
+    OutField o;
+    o.bind(out, no, mem);
+    InField v;
+    if(S > 0) {
+        if(!values) invalid("values is NULL");
+        v.bind(values, S, mem);
+    }
+    gpp_gridding_nearest_device(to, from, v.d, min_num, statistic, o.d);
     o.finish();
     GPP_HIP(hipStreamSynchronize(stream()));
     return GPP_OK;

@@ -17,6 +17,7 @@
 //   count, gridding, gridding_nearest          :938-1010
 //   fill, fill_missing, doping_square/circle, neighbourhood_search, calc_gradient
 //   calc_statistic / calc_quantile             :1454-1482
+//   Metric, calc_score (three overloads), neighbourhood_score  :103-110
 // Nested vectors are flattened once, handed to the C-ABI as host buffers (GPP_MEM_HOST) and un-flattened,
 // exactly where the reference flattens them itself (src/api/oi.cpp:69-86).  Errors: GPP_EINVAL ->
 // std::invalid_argument, everything else -> std::runtime_error (swig/gridpp.i:21-40 maps these to python).
@@ -44,6 +45,7 @@ enum CoordinateType { Geodetic = 0, Cartesian = 1 };
 enum Downscaler { Nearest = 0, Bilinear = 1 };   // include/gridpp.h:132-135
 enum ComparisonOperator { Lt = 0, Leq = 10, Gt = 20, Geq = 30 };   // include/gridpp.h:138-143
 enum Extrapolation { OneToOne = 0, MeanSlope = 10, NearestSlope = 20, Zero = 30, Unchanged = 40 };   // include/gridpp.h:79-85
+enum Metric { Ets = 0, Ts = 1, Kss = 20, Pc = 30, Bias = 40, Hss = 50 };   // include/gridpp.h:103-110
 
 namespace detail {
 inline void check(int rc) {
@@ -1027,6 +1029,37 @@ inline vec2 window(const vec2& array, int length, Statistic statistic, bool befo
     detail::check(gpp_window(a.data(), (long long)Y, (int)T, length, (int)statistic, before ? 1 : 0, keep_missing ? 1 : 0, missing_edges ? 1 : 0, out.data(),
                              GPP_MEM_HOST));
     return detail::unflatten(out, Y, T);
+}
+
+// ---- verification scores (src/api/metric_optimizer.cpp:185-244, src/api/neighbourhood_score.cpp:6-60) ---------------------------------
+// calc_score of a contingency table: host arithmetic with the reference's promotions; std::invalid_argument("Unknown metric").
+inline float calc_score(float a, float b, float c, float d, Metric metric) {
+    float out = MV;
+    detail::check(gpp_calc_score_table(a, b, c, d, (int)metric, &out));
+    return out;
+}
+// the table of the first fcst.size() elements, counted on the GPU (nothing to count needs none).  A ref shorter than fcst is read out of
+// bounds by the reference: std::invalid_argument here.
+inline float calc_score(const vec& ref, const vec& fcst, float threshold, float fthreshold, Metric metric) {
+    if(ref.size() < fcst.size()) throw std::invalid_argument("ref and fcst not the same size");
+    float out = MV;
+    detail::check(gpp_calc_score(ref.data(), fcst.data(), (long long)fcst.size(), threshold, fthreshold, (int)metric, &out, GPP_MEM_HOST));
+    return out;
+}
+inline float calc_score(const vec& ref, const vec& fcst, float threshold, Metric metric) { return calc_score(ref, fcst, threshold, threshold, metric); }
+// neighbourhood_score.cpp:6-60, the checks in its order (the last one is gridding_nearest's)
+inline vec2 neighbourhood_score(const Grid& grid, const Points& points, const vec2& fcst, const vec& ref, int half_width, Metric metric, float threshold) {
+    size_t Y, X;
+    vec f = detail::flatten(fcst, Y, X);
+    if(Y != 0 && !detail::fits(grid, Y, X)) throw std::invalid_argument("Grid size is not the same as forecast values");
+    if(half_width <= 0) throw std::invalid_argument("half_width must be greater than 0");
+    calc_score(0, 0, 0, 0, metric);
+    if((int)ref.size() != points.size()) throw std::invalid_argument("Points size is not the same as values");
+    if(detail::cells(grid) == 0) return vec2(grid.size()[0]);
+    if(Y == 0) throw std::invalid_argument("Grid size is not the same as forecast values");   // (the reference reads fcst[0] of an empty vector here)
+    vec out(Y * X, MV);
+    detail::check(gpp_neighbourhood_score(grid.handle(), points.handle(), f.data(), ref.data(), half_width, (int)metric, threshold, out.data(), GPP_MEM_HOST));
+    return detail::unflatten(out, Y, X);
 }
 
 // ---- util (include/gridpp.h:1454-1482) -----------------------------------------------------------------------------

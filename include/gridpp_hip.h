@@ -53,7 +53,7 @@ extern "C" {
  * gpp_full_gradient, gpp_downscale_probability, gpp_mask_threshold_downscale (the cubes and the threshold) and gpp_smart
  * (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
  * (their float fields), by gpp_neighbourhood_quantile_fast for `input` only, by gpp_apply_curve and gpp_interpolate for the values
- * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs and by gpp_window for `array`. */
+ * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs, by gpp_window for `array` and by gpp_neighbourhood_score for `fcst`. */
 #define GPP_HOST_F64 4
 
 /* include/gridpp.h:120-123 */
@@ -458,6 +458,38 @@ int gpp_calc_even_quantiles(const float* values, long n, int num, int only_valid
                                     * length / 2 rounded up to a multiple of 4, both after clamping length / 2 and length - 1 to nx */
 int gpp_window(const float* array, long long ny, int nx, int length, int statistic, int before, int keep_missing, int missing_edges,
                float* out, int mem);
+
+/* ---- verification scores (include/gridpp.h:103-110,  src/api/metric_optimizer.cpp:185-244, src/api/neighbourhood_score.cpp) ----
+ * gridpp::Metric (include/gridpp.h:103-110). */
+#define GPP_METRIC_ETS 0
+#define GPP_METRIC_TS 1
+#define GPP_METRIC_KSS 20
+#define GPP_METRIC_PC 30
+#define GPP_METRIC_BIAS 40
+#define GPP_METRIC_HSS 50
+/* gridpp::calc_score(a, b, c, d, metric) (metric_optimizer.cpp:207-244) with the reference's float / double promotions, operation for
+ * operation.  Host only, no GPU needed.  GPP_EINVAL "Unknown metric" for a value that is none of the six. */
+int gpp_calc_score_table(float a, float b, float c, float d, int metric, float* out);
+/* gridpp::calc_score(ref, fcst, threshold, fthreshold, metric) (metric_optimizer.cpp:188-206; the four-argument form passes threshold
+ * twice): the contingency table of the first n elements of both vectors, counted on the device in integers, then the scalar rule above.  A
+ * NaN ref is counted nowhere, a NaN fcst as c or d (it fails `fcst > fthreshold`), as in the reference, whose float counters stop growing
+ * at 2^24: every count is clamped to 16777216.  n == 0 needs no device (Bias is 1, the others NaN).  The caller makes sure that ref holds n
+ * elements (the reference reads past a shorter one).  ref / fcst follow `mem`; *out is host memory. */
+int gpp_calc_score(const float* ref, const float* fcst, long long n, float threshold, float fthreshold, int metric, float* out, int mem);
+/* gridpp::neighbourhood_score (neighbourhood_score.cpp:6-60): fcst and out are [ny][nx] of `grid` (a grid handle) and follow `mem`
+ * (GPP_HOST_F64 honoured for fcst); ref is a HOST array of one value per point of `points`, whatever `mem` says.  ref_grid =
+ * gridding_nearest(grid, points, ref, 1, Mean); a cell counts where ref_grid and fcst are both finite, as a / b (fcst > threshold, ref_grid
+ * > / <= threshold) or c / d; out = calc_score of the four fractions (float)((double)n / area) over the window [y +- half_width] x [x +-
+ * half_width] clipped to the grid, area = the cells of the clipped window.  GPP_EINVAL before any device work: "half_width must be greater
+ * than 0", then "Unknown metric".  The sizes of fcst and ref are the caller's to check (the reference's first and last check).  An empty
+ * grid returns GPP_OK and writes nothing.  Half widths up to GPP_SCORE_FUSED_MAXHW take one fused kernel (row and column pass over one
+ * byte per cell, the four counts packed in 16-bit lanes, which holds while (2 half_width + 1)^2 < 65536); wider ones, and every call
+ * under the path override GPP_SCORE_GENERAL, a separable pair with 32-bit counters.  Both give the same bits. */
+#define GPP_SCORE_TILE_COLS 64      /* output columns of a strip of the fused kernel */
+#define GPP_SCORE_TILE_ROWS 32      /* rows of a chunk of the strip */
+#define GPP_SCORE_FUSED_MAXHW 16    /* the ring of the fused kernel holds 32 + 2 * 16 rows; (2 * 16 + 1)^2 = 1089 < 65536 */
+int gpp_neighbourhood_score(gpp_points* grid, gpp_points* points, const float* fcst, const float* ref, int half_width, int metric,
+                            float threshold, float* out, int mem);
 
 /* per-call statistics of the last OI call on this thread (diagnostics / bench) */
 typedef struct gpp_oi_stats {
