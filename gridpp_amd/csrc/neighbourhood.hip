@@ -22,6 +22,7 @@
 #include <atomic>
 #include "common.h"
 #include <algorithm>
+#include <utility>
 #include <rocprim/rocprim.hpp>
 
 #pragma clang fp contract(off)
@@ -637,6 +638,14 @@ __device__ __forceinline__ void bm_lds_barrier() {
 #define BM_MAXHW 16          // BM_C + 2 BM_MAXHW <= BM_RING
 #define BM_RP (BM_W + 1)     // pitch of the ring rows (doubles)
 #define BM_P (BM_W + 2 * BM_MAXHW + 1)   // pitch of the chunk's rows (floats; odd, and wide enough for every thread's unconditional store)
+// The rows of a [Y][X] plane that a workgroup of the marching kernels with the output rows [ya, yb) fetches end here: it loads whole chunks of BM_C rows, from
+// row yl0 = ya - hw through the chunk that holds row yb - 1 + hw, so up to BM_C - 1 rows beyond its last window are read (they feed no output).  THE HOST'S COPY OF
+// `yl0` AND `nchunk` IN k_box_march AND k_minmax_march BELOW -- change them together (sharing one function with the kernels changes their code, if not their results).
+// The banded host path has these rows in place before such a workgroup runs (NbhCall::upload_band).
+inline long bm_rows_fetched(int ya, int yb, int hw, int Y) {
+    const int yl0 = ya - hw, nchunk = (yb - 1 + hw - yl0) / BM_C + 1;
+    return std::min<long>(Y, (long)yl0 + (long)nchunk * BM_C);
+}
 __host__ __device__ inline size_t bm_tin_bytes(int) { return (((size_t)BM_C * BM_P * sizeof(float)) + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t bm_lds_bytes(int hw) { return bm_tin_bytes(hw) + (size_t)BM_RING * (BM_RP * sizeof(double) + BM_W + 1) + 2 * sizeof(int); }
 template <int HW>
@@ -1132,13 +1141,15 @@ __global__ void k_qf_interp(const float* __restrict__ ya, long C, int T, const f
 // host side
 // -------------------------------------------------------------------------------------------
 namespace {
+struct QfPadKey {   // the padding of the quantile_fast count planes is in place for this buffer (this ALLOCATION of it), shape, thresholds and members
+    const void* ptr = nullptr; unsigned long long gen = 0; int y = 0, x = 0, t = 0, e = 0;
+    bool operator==(const QfPadKey& o) const { return ptr == o.ptr && gen == o.gen && y == o.y && x == o.x && t == o.t && e == o.e; }
+};
 struct NbWorkspace {
     DevBuf<float> flat, tmp, tmp2, planes, thr, qf;
     DevBuf<double> rs;
     DevBuf<int> rc, plane_flags;
-    const void* pad_ptr = nullptr;   // the padding of the quantile_fast count planes is in place for this buffer (this ALLOCATION of it) and shape
-    unsigned long long pad_gen = 0;
-    int pad_y = 0, pad_x = 0, pad_t = 0, pad_e = 0;
+    QfPadKey pad;                    // (a default key -- a null buffer -- matches no call: "nothing remembered")
     hipEvent_t ev_band0 = nullptr, ev_up[6] = {};   // banded host path of gpp_neighbourhood
     int spec_nt = -1, spec_U = -1;   // quantile_fast: the number of distinct thresholds the last call with spec_nt thresholds had (its table was usable)
     int* h_pin = nullptr;            // a few page-locked words for the read-back at the end of such a call
@@ -1146,11 +1157,10 @@ struct NbWorkspace {
 thread_local NbWorkspace g_nb;
 
 #ifdef GPP_POISON
-// Diagnostic build only (tools/hostile/build.sh, tools/nbh_hostile_soak.py): the call-to-call workspaces of the neighbourhood family set to
-// `byte`.  The byte planes of the fused quantile_fast path carry state across calls BY DESIGN (their padding is written once per layout,
-// gpp_neighbourhood_quantile_fast below): keep_padding = 0 poisons the whole buffer and forgets the layout (the next call must lay the
-// padding out again); keep_padding = 1 poisons everything EXCEPT the padding of the remembered layout -- every cell byte of every plane
-// -- so that the cache is exercised while a count pass that leaves a cell unwritten is still caught.
+// Diagnostic build only (tools/hostile/build.sh, tools/nbh_hostile_soak.py): the call-to-call workspaces of the neighbourhood family set to `byte`.  The byte planes of
+// the fused quantile_fast path carry state across calls BY DESIGN (their padding is written once per layout, QfCall::padded_planes below): keep_padding = 0 poisons the
+// whole buffer and forgets the layout (the next call must lay the padding out again); keep_padding = 1 poisons everything EXCEPT the padding of the remembered layout
+// -- every cell byte of every plane -- so that the cache is exercised while a count pass that leaves a cell unwritten is still caught.
 __global__ void k_poison_plane_cells(unsigned char* __restrict__ cnt8, QfGeom g, int nplanes, int byte) {
     const long cell = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if(cell >= (long)g.Y * g.X) return;
@@ -1163,13 +1173,13 @@ extern "C" int gpp_debug_poison_nbh_workspace(int byte, int keep_padding) {
     NbWorkspace& w = g_nb;
     w.flat.poison(byte); w.tmp.poison(byte); w.tmp2.poison(byte); w.thr.poison(byte); w.qf.poison(byte);
     w.rs.poison(byte); w.rc.poison(byte); w.plane_flags.poison(byte);
-    if(keep_padding && w.pad_ptr && w.pad_ptr == (const void*)w.planes.p && w.pad_gen == w.planes.gen) {
-        const QfGeom g = qf_geom(w.pad_y, w.pad_x);
+    if(keep_padding && w.pad.ptr && w.pad.ptr == (const void*)w.planes.p && w.pad.gen == w.planes.gen) {
+        const QfGeom g = qf_geom(w.pad.y, w.pad.x);
         const long C = (long)g.Y * g.X;
-        hipLaunchKernelGGL(k_poison_plane_cells, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), reinterpret_cast<unsigned char*>(w.planes.p), g, w.pad_t + 1, byte);
+        hipLaunchKernelGGL(k_poison_plane_cells, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), reinterpret_cast<unsigned char*>(w.planes.p), g, w.pad.t + 1, byte);
         GPP_HIP(hipGetLastError());
     }
-    else { w.planes.poison(byte); w.pad_ptr = nullptr; }
+    else { w.planes.poison(byte); w.pad = QfPadKey(); }
     GPP_HIP(hipStreamSynchronize(stream()));
     return GPP_OK;
     GPP_CATCH
@@ -1204,58 +1214,44 @@ void qf_count_launch_nl(const float* d_in, long C, int E, const float* d_thr, in
     hipLaunchKernelGGL((k_qf_count<NL>), dim3((unsigned)grid), dim3(64), lds, stream(), d_in, C, E, d_thr, T, lut, cnt8, g, Uexp);
     GPP_HIP(hipGetLastError());
 }
+template <int... I> auto qf_count_form(std::integer_sequence<int, I...>, int U) { static constexpr decltype(&qf_count_launch_nl<3>) forms[] = {qf_count_launch_nl<I + 3>...}; return forms[U - 1]; }
 void qf_count_launch(const float* d_in, long C, int E, const float* d_thr, int T, const QfLut* lut, int U, unsigned char* cnt8, const QfGeom& g, const int Uexp) {
-    switch(U + 2) {
-#define QF_NL_CASE(n) case n: qf_count_launch_nl<n>(d_in, C, E, d_thr, T, lut, cnt8, g, Uexp); break;
-        QF_NL_CASE(3) QF_NL_CASE(4) QF_NL_CASE(5) QF_NL_CASE(6) QF_NL_CASE(7) QF_NL_CASE(8) QF_NL_CASE(9) QF_NL_CASE(10)
-        QF_NL_CASE(11) QF_NL_CASE(12) QF_NL_CASE(13) QF_NL_CASE(14) QF_NL_CASE(15) QF_NL_CASE(16) QF_NL_CASE(17) QF_NL_CASE(18)
-#undef QF_NL_CASE
-        default: runtime("Internal error. quantile_fast: number of distinct thresholds");
+    if(U < 1 || U > 16) runtime("Internal error. quantile_fast: number of distinct thresholds");
+    qf_count_form(std::make_integer_sequence<int, 16>(), U)(d_in, C, E, d_thr, T, lut, cnt8, g, Uexp);   // k_qf_count<3 .. 18>
+}
+// The launch geometry of the marching kernels (k_box_march: Mean / Sum / Count of `nplanes` planes; k_minmax_march: Min / Max of one) for a [Y][X] plane: strips of
+// W columns x `segs` row segments of SH rows (whole chunks; a segment's first chunk is run-in: 2 hw rows) x planes, about three workgroups per CU.  !ok: the two-pass kernels.
+struct MarchGeom {
+    int W = 0, strips = 0, SH = 0, segs = 0; bool ok = false;
+    MarchGeom() = default;
+    MarchGeom(int Y, int X, int hw, int statistic, int nplanes = 1) {
+        const bool box = statistic == GPP_MEAN || statistic == GPP_SUM || statistic == GPP_COUNT;
+        if((!box && statistic != GPP_MIN && statistic != GPP_MAX) || hw > (box ? BM_MAXHW : BM_MM_MAXHW) || nplanes > 65535 || path_env("GPP_BOX_TWO_PASS")) return;
+        W = box || hw <= BM_MAXHW ? BM_W : BM_W / 2; strips = (X + W - 1) / W;
+        const long fill = path_env("GPP_BM_FILL") ? std::max(1, atoi(path_env("GPP_BM_FILL"))) : box ? 768 : 1280;   // (A/B: workgroups the launch aims for)
+        const long want = std::max<long>(1, fill / std::max<long>(1, (long)strips * nplanes));
+        const int even = (int)std::min<long>(want, (Y + BM_C - 1) / BM_C);
+        SH = ((Y + even - 1) / even + BM_C - 1) / BM_C * BM_C;
+        while((Y + SH - 1) / SH > 65535) SH += BM_C;   // gridDim.y is a 16-bit quantity
+        segs = (Y + SH - 1) / SH; ok = true;
     }
+    dim3 grid(int nseg, int nplanes = 1) const { return dim3(strips, nseg < 0 ? segs : nseg, nplanes); }   // nseg < 0: every segment; else a band of them (from seg0)
+};
+// The marching kernels by halfwidth (a template parameter: every window loop unrolls): k_box_march<0 .. BM_MAXHW>, k_minmax_march<0 .. BM_MM_MAXHW, Max | Min>
+using BoxMarch = void (*)(const float*, int, int, int, float*, int, int, int);
+using MinMaxMarch = void (*)(const float*, int, int, float*, int, int);
+struct MinMaxForm { MinMaxMarch max, min; size_t lds; };
+template <int... HW> BoxMarch box_march(std::integer_sequence<int, HW...>, int hw) { static constexpr BoxMarch forms[] = {k_box_march<HW>...}; return forms[hw]; }
+template <int... HW> const MinMaxForm& minmax_march(std::integer_sequence<int, HW...>, int hw) {
+    static const MinMaxForm forms[] = {{k_minmax_march<HW, true>, k_minmax_march<HW, false>, bm_minmax_lds_bytes<HW>()}...};
+    return forms[hw];
 }
 // Mean / Sum / Count of `nplanes` [Y][X] planes
-// The launch geometry of the marching kernels for a [Y][X] plane: row segments of SH rows, `segs` of them.  (seg0, nseg): the band of segments a launch covers --
-// all of them, or one band of the banded host path of gpp_neighbourhood.
-struct MarchGeom { int SH = 0, segs = 0; bool ok = false; };
-MarchGeom march_geom(int Y, int X, int hw, int statistic, int nplanes = 1) {
-    MarchGeom g;
-    if(path_env("GPP_BOX_TWO_PASS")) return g;
-    if(statistic == GPP_MEAN || statistic == GPP_SUM || statistic == GPP_COUNT) {
-        if(hw > BM_MAXHW || nplanes > 65535) return g;
-        const int strips = (X + BM_W - 1) / BM_W;
-        const long fill = path_env("GPP_BM_FILL") ? std::max(1, atoi(path_env("GPP_BM_FILL"))) : 768;   // (A/B: workgroups the launch aims for)
-        const long want = std::max<long>(1, fill / std::max<long>(1, (long)strips * nplanes));
-        const int segs = (int)std::min<long>(want, (Y + BM_C - 1) / BM_C);
-        g.SH = ((Y + segs - 1) / segs + BM_C - 1) / BM_C * BM_C;
-    }
-    else if(statistic == GPP_MIN || statistic == GPP_MAX) {
-        if(hw > BM_MM_MAXHW) return g;
-        const int W = hw <= BM_MAXHW ? BM_W : BM_W / 2;
-        const int strips = (X + W - 1) / W;
-        const long fill = path_env("GPP_BM_FILL") ? std::max(1, atoi(path_env("GPP_BM_FILL"))) : 1280;
-        const long want = std::max<long>(1, fill / strips);
-        const int segs = (int)std::min<long>(want, (Y + BM_C - 1) / BM_C);
-        g.SH = ((Y + segs - 1) / segs + BM_C - 1) / BM_C * BM_C;
-    }
-    else return g;
-    while((Y + g.SH - 1) / g.SH > 65535) g.SH += BM_C;
-    g.segs = (Y + g.SH - 1) / g.SH;
-    g.ok = true;
-    return g;
-}
 void box_stat(const float* d_in, int Y, int X, int nplanes, int hw, int statistic, float* d_out, int qf_reps = 0, int seg0 = 0, int nseg = -1) {
-    if(hw <= BM_MAXHW && nplanes <= 65535 && !path_env("GPP_BOX_TWO_PASS")) {   // both passes in one kernel (k_box_march)
-        // about three workgroups per CU: strips x row segments x planes; a segment is a whole number of chunks (its first chunk is run-in: 2 hw rows)
-        const int strips = (X + BM_W - 1) / BM_W;
-        const MarchGeom mg = march_geom(Y, X, hw, GPP_MEAN, nplanes);
-        const int SH = mg.SH;
-        const dim3 grid(strips, nseg < 0 ? mg.segs : nseg, nplanes);
-        switch(hw) {
-#define BM_CASE(n) case n: hipLaunchKernelGGL(k_box_march<n>, grid, dim3(256), bm_lds_bytes(n), stream(), d_in, Y, X, statistic, d_out, qf_reps, SH, seg0); break;
-            BM_CASE(0) BM_CASE(1) BM_CASE(2) BM_CASE(3) BM_CASE(4) BM_CASE(5) BM_CASE(6) BM_CASE(7) BM_CASE(8)
-            BM_CASE(9) BM_CASE(10) BM_CASE(11) BM_CASE(12) BM_CASE(13) BM_CASE(14) BM_CASE(15) BM_CASE(16)
-#undef BM_CASE
-        }
+    const MarchGeom mg(Y, X, hw, statistic, nplanes);
+    if(mg.ok) {   // both passes in one kernel (k_box_march)
+        const BoxMarch kernel = box_march(std::make_integer_sequence<int, BM_MAXHW + 1>(), hw);
+        hipLaunchKernelGGL(kernel, mg.grid(nseg, nplanes), dim3(256), bm_lds_bytes(hw), stream(), d_in, Y, X, statistic, d_out, qf_reps, mg.SH, seg0);
         GPP_HIP(hipGetLastError());
         return;
     }
@@ -1295,23 +1291,11 @@ void brute(const float* d_in, int Y, int X, int E, int hw, int statistic, float 
 // neighbourhood(vec2, hw, stat) on a device-resident plane (neighbourhood.cpp:28-242)
 void neighbourhood2d(const float* d_in, int Y, int X, int hw, int statistic, float* d_out, int seg0 = 0, int nseg = -1) {
     long C = (long)Y * X;
-    if(statistic == GPP_MEAN || statistic == GPP_SUM || statistic == GPP_COUNT) box_stat(d_in, Y, X, 1, hw, statistic, d_out, 0, seg0, nseg);
-    else if((statistic == GPP_MIN || statistic == GPP_MAX) && hw <= BM_MM_MAXHW && !path_env("GPP_BOX_TWO_PASS")) {   // both passes in one kernel (k_minmax_march)
-        const int W = hw <= BM_MAXHW ? BM_W : BM_W / 2;
-        const int strips = (X + W - 1) / W;
-        const MarchGeom mg = march_geom(Y, X, hw, statistic);
-        const int SH = mg.SH;
-        const dim3 grid(strips, nseg < 0 ? mg.segs : nseg);
-        const bool mx = statistic == GPP_MAX;
-        switch(hw) {
-#define BM_CASE(n) case n: if(mx) hipLaunchKernelGGL((k_minmax_march<n, true>), grid, dim3(256), bm_minmax_lds_bytes<n>(), stream(), d_in, Y, X, d_out, SH, seg0); \
-                           else hipLaunchKernelGGL((k_minmax_march<n, false>), grid, dim3(256), bm_minmax_lds_bytes<n>(), stream(), d_in, Y, X, d_out, SH, seg0); break;
-            BM_CASE(0) BM_CASE(1) BM_CASE(2) BM_CASE(3) BM_CASE(4) BM_CASE(5) BM_CASE(6) BM_CASE(7) BM_CASE(8)
-            BM_CASE(9) BM_CASE(10) BM_CASE(11) BM_CASE(12) BM_CASE(13) BM_CASE(14) BM_CASE(15) BM_CASE(16)
-            BM_CASE(17) BM_CASE(18) BM_CASE(19) BM_CASE(20) BM_CASE(21) BM_CASE(22) BM_CASE(23) BM_CASE(24)
-            BM_CASE(25) BM_CASE(26) BM_CASE(27) BM_CASE(28) BM_CASE(29) BM_CASE(30) BM_CASE(31) BM_CASE(32)
-#undef BM_CASE
-        }
+    if(statistic == GPP_MEAN || statistic == GPP_SUM || statistic == GPP_COUNT) return box_stat(d_in, Y, X, 1, hw, statistic, d_out, 0, seg0, nseg);
+    const MarchGeom mg(Y, X, hw, statistic);   // (of Min and Max: !ok for every other statistic)
+    if(mg.ok) {   // both passes in one kernel (k_minmax_march)
+        const MinMaxForm& f = minmax_march(std::make_integer_sequence<int, BM_MM_MAXHW + 1>(), hw);
+        hipLaunchKernelGGL(statistic == GPP_MAX ? f.max : f.min, mg.grid(nseg), dim3(256), f.lds, stream(), d_in, Y, X, d_out, mg.SH, seg0);
         GPP_HIP(hipGetLastError());
     }
     else if(statistic == GPP_MIN || statistic == GPP_MAX) {
@@ -1335,91 +1319,225 @@ void neighbourhood2d(const float* d_in, int Y, int X, int hw, int statistic, flo
     }
     else brute(d_in, Y, X, 1, hw, statistic, 0.0f, d_out);   // Median, RandomChoice (:236-238)
 }
-}   // namespace
-
-static void check_stat(int s) {
+void check_stat(int s) {
     switch(s) {
         case GPP_MEAN: case GPP_MIN: case GPP_MEDIAN: case GPP_MAX: case GPP_QUANTILE: case GPP_STD: case GPP_VARIANCE:
         case GPP_SUM: case GPP_COUNT: case GPP_RANDOMCHOICE: return;
         default: runtime("Internal error. Cannot compute statistic");
     }
 }
-
-extern "C" int gpp_neighbourhood(const float* input, int ny, int nx, int ne, int is3d, int halfwidth, int statistic, float* out, int mem) {
-    GPP_TRY
-    if(halfwidth < 0) invalid("Half width must be > 0");                                          // :29-30
-    if(statistic == GPP_QUANTILE) invalid("Use neighbourhood_quantile for computing neighbourhood quantiles");   // :31-32
-    check_stat(statistic);
-    if(ny < 0 || nx < 0 || ne < 0) invalid("negative size");
-    if(ny == 0 || nx == 0 || ne == 0) return GPP_OK;                                                // :33-34
-    ensure_device();
-    const long C = (long)ny * nx;
+// The frame the entry points share: the input field and the result bound to device memory; done(): the result on its way back, the library stream drained.
+struct Fields {
     InField in; OutField o;
-    // Round 6: a large 2-D plane in host memory (numpy in, numpy out: 64 MB up, a 0.07 ms kernel, 64 MB down -- 2.4 ms for a 4000 x 4000 plane) travels in
-    // bands of the marching kernels' row segments: a band's rows (+ the halfwidth rows below it) go up on the second stream, the band's launch waits for
-    // them, and a page-locked result array is written by the kernels themselves (mapped host memory: optimal_interpolation's host path, oi.hip).
-    if(!is3d && !(mem & GPP_MEM_DEVICE) && C >= (1L << 20) && !path_env("GPP_NBH_NO_BANDS")) {
-        const MarchGeom mg = march_geom(ny, nx, halfwidth, statistic);
+    void bind(const float* src, size_t nin, float* dst, size_t nout, int mem) { in.bind(src, nin, mem); o.bind(dst, nout, mem); }
+    int done() { o.finish(); GPP_HIP(hipStreamSynchronize(stream())); return GPP_OK; }
+};
+
+// One gpp_neighbourhood call on the host, a local of the entry point below.  The banded host path (round 6): a large 2-D plane in host memory (numpy in, numpy out: 64 MB up,
+// a 0.07 ms kernel, 64 MB down -- 2.4 ms for a 4000 x 4000 plane) travels in bands of the marching kernels' row segments: a band's rows (+ the rows below it that its last
+// chunk fetches) go up on the second stream, the band's launch waits for them, and a page-locked result array is written by the kernels themselves (mapped host memory:
+// optimal_interpolation's host path, oi.hip).
+struct NbhCall : Fields {
+    const float* const input; const int ny, nx, ne, is3d, halfwidth, statistic; float* const out; const int mem;
+    NbWorkspace& ws = g_nb; const long C = (long)ny * nx;
+    MarchGeom mg; int nband = 0, band_end[6] = {};   // banded path: the segments, and the segment behind the last one of every band;
+    float* d_in = nullptr; void* d_out = nullptr;    // the staged plane, the caller's result array as the device sees it;
+    Staged<double> wide; long up = 0;                // the bands of a float64 array before their cast, the rows uploaded so far
+
+    bool check_args() const {   // false: an empty field, nothing to do
+        if(halfwidth < 0) invalid("Half width must be > 0");                                          // :29-30
+        if(statistic == GPP_QUANTILE) invalid("Use neighbourhood_quantile for computing neighbourhood quantiles");   // :31-32
+        check_stat(statistic);
+        if(ny < 0 || nx < 0 || ne < 0) invalid("negative size");
+        return ny != 0 && nx != 0 && ne != 0;                                                           // :33-34
+    }
+    bool bands_eligible() {   // a large 2-D host plane, a marching kernel with at least four segments, a result array the device can write
+        if(is3d || (mem & GPP_MEM_DEVICE) || C < (1L << 20) || path_env("GPP_NBH_NO_BANDS")) return false;
+        mg = MarchGeom(ny, nx, halfwidth, statistic);
         hipPointerAttribute_t at;
-        void* dp = nullptr;
-        bool okp = mg.ok && mg.segs >= 4 && hipPointerGetAttributes(&at, out) == hipSuccess && at.type == hipMemoryTypeHost && hipHostGetDevicePointer(&dp, out, 0) == hipSuccess && dp != nullptr;
+        const bool ok = mg.ok && mg.segs >= 4 && hipPointerGetAttributes(&at, out) == hipSuccess && at.type == hipMemoryTypeHost && hipHostGetDevicePointer(&d_out, out, 0) == hipSuccess && d_out != nullptr;
         (void)hipGetLastError();
-        if(okp) {
-            const bool f64 = (mem & GPP_HOST_F64) != 0;
-            float* const d_in = in.staged.get((size_t)C);
-            Staged<double> wide;
-            if(f64) wide.get((size_t)C);
-            if(!g_nb.ev_band0) {
-                GPP_HIP(hipEventCreateWithFlags(&g_nb.ev_band0, hipEventDisableTiming));
-                for(int b = 0; b < 6; b++) GPP_HIP(hipEventCreateWithFlags(&g_nb.ev_up[b], hipEventDisableTiming));
-            }
-            struct Guard { ~Guard() { (void)hipStreamSynchronize(stream2()); (void)hipStreamSynchronize(stream()); } } guard;   // (nothing of the call stays in flight, whatever ends it)
-            const hipStream_t sUp = stream2();
-            GPP_HIP(hipEventRecord(g_nb.ev_band0, stream()));
-            GPP_HIP(hipStreamWaitEvent(sUp, g_nb.ev_band0, 0));     // (the staging buffer's previous readers are behind the library stream)
-            static const int share[6] = {1, 2, 3, 3, 2, 1};
-            const int nband = std::min(6, mg.segs);
-            int s0 = 0, acc = 0, tot = 0;
-            for(int b = 0; b < nband; b++) tot += share[b];
-            long up = 0;    // rows uploaded so far
-            for(int b = 0; b < nband; b++) {
-                acc += share[b];
-                const int s1 = b == nband - 1 ? mg.segs : std::max(s0 + 1, (int)((long)mg.segs * acc / tot));
-                const long need = std::min<long>(ny, (long)s1 * mg.SH + halfwidth);       // the band's windows reach `halfwidth` rows below its last row
-                if(need > up) {
-                    const size_t off = (size_t)up * nx, cnt = (size_t)(need - up) * nx;
-                    if(!f64) GPP_HIP(hipMemcpyAsync(d_in + off, input + off, cnt * sizeof(float), hipMemcpyHostToDevice, sUp));
-                    else {
-                        GPP_HIP(hipMemcpyAsync(wide.p + off, reinterpret_cast<const double*>(input) + off, cnt * sizeof(double), hipMemcpyHostToDevice, sUp));
-                        hipLaunchKernelGGL(k_stage_f64, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, sUp, (const double*)(wide.p + off), cnt, d_in + off);
-                        GPP_HIP(hipGetLastError());
-                    }
-                    up = need;
-                }
-                GPP_HIP(hipEventRecord(g_nb.ev_up[b], sUp));
-                GPP_HIP(hipStreamWaitEvent(stream(), g_nb.ev_up[b], 0));
-                neighbourhood2d(d_in, ny, nx, halfwidth, statistic, static_cast<float*>(dp), s0, s1 - s0);
-                s0 = s1;
-            }
-            GPP_HIP(hipStreamSynchronize(stream()));
-            GPP_HIP(hipStreamSynchronize(sUp));
-            return GPP_OK;
+        return ok;
+    }
+    void plan_bands() {   // the segments in shares of 1 : 2 : 3 : 3 : 2 : 1 (the first of them as many as there are bands), every band at least one segment
+        static const int share[6] = {1, 2, 3, 3, 2, 1};
+        nband = std::min(6, mg.segs);
+        int acc = 0, tot = 0;
+        for(int b = 0; b < nband; b++) tot += share[b];
+        for(int b = 0; b < nband; b++) {
+            acc += share[b];
+            band_end[b] = b == nband - 1 ? mg.segs : std::max((b ? band_end[b - 1] : 0) + 1, (int)((long)mg.segs * acc / tot));
         }
     }
-    in.bind(input, (size_t)C * ne, mem);
-    o.bind(out, C, mem);
-    const float* plane = in.d;
-    if(is3d) {   // 3-D form: member statistic first (:12-27)
-        float* flat = g_nb.flat.get(C);
+    void upload_band(int b, hipStream_t s) {   // every row the band's launch fetches that is not up yet
+        const long need = bm_rows_fetched((band_end[b] - 1) * mg.SH, std::min(ny, band_end[b] * mg.SH), halfwidth, ny);
+        if(need <= up) return;
+        const size_t off = (size_t)up * nx, cnt = (size_t)(need - up) * nx;
+        if(!(mem & GPP_HOST_F64)) GPP_HIP(hipMemcpyAsync(d_in + off, input + off, cnt * sizeof(float), hipMemcpyHostToDevice, s));
+        else {
+            GPP_HIP(hipMemcpyAsync(wide.p + off, reinterpret_cast<const double*>(input) + off, cnt * sizeof(double), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_stage_f64, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, (const double*)(wide.p + off), cnt, d_in + off);
+            GPP_HIP(hipGetLastError());
+        }
+        up = need;
+    }
+    void launch_band(int b, hipStream_t s) {   // behind the band's upload, on the library stream
+        const int s0 = b ? band_end[b - 1] : 0;
+        GPP_HIP(hipEventRecord(ws.ev_up[b], s));
+        GPP_HIP(hipStreamWaitEvent(stream(), ws.ev_up[b], 0));
+        neighbourhood2d(d_in, ny, nx, halfwidth, statistic, static_cast<float*>(d_out), s0, band_end[b] - s0);
+    }
+    void run_bands() {
+        plan_bands();
+        d_in = in.staged.get((size_t)C); if(mem & GPP_HOST_F64) wide.get((size_t)C);
+        if(!ws.ev_band0) {
+            GPP_HIP(hipEventCreateWithFlags(&ws.ev_band0, hipEventDisableTiming));
+            for(int b = 0; b < 6; b++) GPP_HIP(hipEventCreateWithFlags(&ws.ev_up[b], hipEventDisableTiming));
+        }
+        struct Guard { ~Guard() { (void)hipStreamSynchronize(stream2()); (void)hipStreamSynchronize(stream()); } } guard;   // (nothing of the call stays in flight, whatever ends it)
+        GPP_HIP(hipEventRecord(ws.ev_band0, stream()));
+        GPP_HIP(hipStreamWaitEvent(stream2(), ws.ev_band0, 0));     // (the staging buffer's previous readers are behind the library stream)
+        for(int b = 0; b < nband; b++) { upload_band(b, stream2()); launch_band(b, stream2()); }
+        GPP_HIP(hipStreamSynchronize(stream()));
+        GPP_HIP(hipStreamSynchronize(stream2()));
+    }
+    void member_statistic() {   // 3-D form: member statistic first (:12-27), into ws.flat
+        float* flat = ws.flat.get(C);
         if(statistic == GPP_MEDIAN) hipLaunchKernelGGL(k_member_quantile, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), in.d, C, ne, 0.5f, flat);
         else if(statistic == GPP_RANDOMCHOICE) brute(in.d, ny, nx, ne, 0, GPP_RANDOMCHOICE, 0, flat);
         else member_pass(in.d, C, ne, 0, statistic, nullptr, 0, flat);
-        plane = flat;
     }
-    neighbourhood2d(plane, ny, nx, halfwidth, statistic, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+};
+
+// One gpp_neighbourhood_quantile_fast call on the host (neighbourhood.cpp:296-522), a local of the entry point below.  3-D input with at most 254 members, 16 thresholds
+// and a halfwidth of 16 takes the FUSED path: byte counts in padded planes + the box pass of qf_box.hip.  The counts come from the rank / sum-of-absolute-differences pass
+// (k_qf_count, RANKED) when the rows are whole float4s and the threshold table (k_qf_lut) is usable, from the compare-per-threshold member pass otherwise.  A ranked call
+// may SPECULATE: launch the count pass for the number of distinct thresholds the LAST call had, with no host round trip in front of the kernels.
+struct QfCall : Fields {
+    const float* const input; const int ny, nx, ne, is3d; const float* const quantile; const int nq, halfwidth; const float* const thresholds; const int nt;
+    float* const out; const int mem;
+    NbWorkspace& ws = g_nb; const long C = (long)ny * nx;
+    // GPP_Q_HOST: the quantile argument is host memory although the field is in HBM (the scalar quantile of a script beside a device-resident
+    // cube: uploaded by the caller and read back here for its validation it cost two transfers and a host round trip per call)
+    const int qmem = (mem & GPP_Q_HOST) ? GPP_MEM_HOST : (mem & ~GPP_HOST_F64);   // GPP_HOST_F64 applies to `input` only: quantile / thresholds stay float32
+    const bool q_on_device = (qmem & GPP_MEM_DEVICE) != 0;
+    InField qf, th; bool fused = false, ranked = false;
+    std::vector<float> hq_buf; float* hq = nullptr;   // quantiles of a device-resident argument on their way to the host
+    int* rowflag = nullptr; QfLut* lut = nullptr; int U = 0;   // of a round: the rows' flags (+ "the count pass stopped"), the table, its distinct thresholds
+
+    bool check_args() const {   // false: an empty field, nothing to do
+        if(halfwidth < 0) invalid("Half width must be > 0");                                   // :303-304,419-420
+        if(ny <= 0 || nx <= 0 || ne <= 0) return false;                                         // :306-307
+        if(nq != 1 && nq != C) invalid("Quantile must be the same size as input, or size (1, 1)");   // :312-313
+        if(nt < 0) invalid("negative number of thresholds");
+        return true;
+    }
+    // Quantile validation (:315-321).  Host values are checked where they are, when the call binds its fields; values in HBM are asked for with fetch_q() -- a copy
+    // queued on the library stream -- and checked with check_fetched_q() behind the next wait for that stream, which the caller shares with whatever else it reads back.
+    void check_q(const float* v) const { for(int i = 0; i < nq; i++) if(is_valid(v[i]) && (v[i] < 0 || v[i] > 1)) invalid("All quantiles must be >= 0 and <= 1"); }
+    void fetch_q() {   // (a scalar into the page-locked words, once they exist)
+        if(!q_on_device) return;
+        hq = (nq == 1 && ws.h_pin) ? reinterpret_cast<float*>(ws.h_pin + 1) : (hq_buf.resize(nq), hq_buf.data());
+        GPP_HIP(hipMemcpyAsync(hq, quantile, sizeof(float) * nq, hipMemcpyDeviceToHost, stream()));
+    }
+    void check_fetched_q() const { if(q_on_device) check_q(hq); }
+    void bind_fields() {
+        bind(input, (size_t)C * ne, out, C, mem);
+        fused = nt > 0 && is3d && ne <= 254 && nt <= 16 && halfwidth <= QF_MAXHW && C < (1L << 31) && !path_env("GPP_QF_NO_FUSED");
+        ranked = fused && (ne & 3) == 0 && (reinterpret_cast<size_t>(in.d) & 15) == 0 && !path_env("GPP_QF_NO_RANKS");
+        if(nt > 0) th.bind(thresholds, nt, mem & ~GPP_HOST_F64);
+        if(!q_on_device) check_q(quantile);
+    }
+    int all_missing() {   // :330-331: no thresholds
+        fetch_q();
+        if(q_on_device) GPP_HIP(hipStreamSynchronize(stream()));
+        check_fetched_q();
+        hipLaunchKernelGGL(k_fill_nan, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), o.d, C);
+        return done();
+    }
+    void bind_quantile() {
+        qf.bind(quantile, nq, qmem);
+        if(!ws.h_pin) GPP_HIP(hipHostMalloc((void**)&ws.h_pin, 64, hipHostMallocDefault));
+    }
+    bool may_speculate() const { return fused && ranked && ws.spec_nt == nt && ws.spec_U >= 0 && !path_env("GPP_QF_NO_SPEC"); }
+    // The threshold table and the rows' flags of a round.  A plain round waits for the table's head (and the quantiles) here and remembers the number of distinct
+    // thresholds for the next call's speculation; a speculative one takes the remembered number and waits for nothing.
+    void begin_round(const bool spec) {
+        int lut_head[5] = {0, 0, 0, 1, 0};   // scale, off, U, flag, ident
+        if(fused) rowflag = ws.plane_flags.get(ny + 2);
+        if(ranked) {
+            lut = reinterpret_cast<QfLut*>(ws.qf.get((sizeof(QfLut) + 3) / 4));
+            hipLaunchKernelGGL(k_qf_lut, dim3(1), dim3(QF_NB), 0, stream(), th.d, nt, lut, rowflag, fused ? ny + 2 : 0);
+            GPP_HIP(hipGetLastError());
+            if(!spec) GPP_HIP(hipMemcpyAsync(lut_head, lut, sizeof(lut_head), hipMemcpyDeviceToHost, stream()));
+        }
+        else if(fused) GPP_HIP(hipMemsetAsync(rowflag, 0, sizeof(int) * (ny + 2), stream()));
+        U = ws.spec_U;
+        if(spec) return;
+        fetch_q();
+        if(ranked || q_on_device) GPP_HIP(hipStreamSynchronize(stream()));
+        check_fetched_q();
+        if(!ranked) return;
+        if(lut_head[3]) ranked = false;   // two thresholds in one bucket / a non-finite threshold: the compare-per-threshold pass
+        else { ws.spec_nt = nt; ws.spec_U = U = lut_head[2]; }
+    }
+    // the count planes, their padding in place: it is written when the planes are laid out (the passes only ever write the cells of the field)
+    unsigned char* padded_planes(const QfGeom& g) {
+        unsigned char* cnt8 = reinterpret_cast<unsigned char*>(ws.planes.get(((size_t)(nt + 1) * g.Pp + 3) / 4));
+        const QfPadKey key{cnt8, ws.planes.gen, ny, nx, nt, ne};
+        if(ws.pad == key) return cnt8;
+        ws.pad = QfPadKey();
+        GPP_HIP(hipMemsetAsync(cnt8, 255, (size_t)nt * g.Pp, stream()));
+        GPP_HIP(hipMemsetAsync(cnt8 + (size_t)nt * g.Pp, ne, (size_t)g.Pp, stream()));
+        ws.pad = key;
+        return cnt8;
+    }
+    void fused_passes(const bool spec) {   // the count pass, by ranks or by compares, and the box pass
+        QfGeom g = qf_geom(ny, nx);
+        unsigned char* cnt8 = padded_planes(g);
+        g.rowflag = rowflag;
+        if(ranked) qf_count_launch(in.d, C, ne, th.d, nt, lut, U, cnt8, g, spec ? U : -1);
+        else member_pass(in.d, C, ne, 2, 0, th.d, nt, reinterpret_cast<float*>(cnt8), g);
+        qf_box_launch(cnt8, g, ne, halfwidth, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
+    }
+    // the one read-back of a speculative round: did the count pass run, and the quantile(s) for the validation a plain round does first
+    bool speculation_held() {
+        GPP_HIP(hipMemcpyAsync(ws.h_pin, rowflag + ny + 1, sizeof(int), hipMemcpyDeviceToHost, stream()));
+        fetch_q();
+        GPP_HIP(hipStreamSynchronize(stream()));
+        check_fetched_q();
+        if(ws.h_pin[0] != 0) ws.spec_nt = ws.spec_U = -1;   // other thresholds than the last call's: the passes stopped on the device
+        return ws.h_pin[0] == 0;
+    }
+    bool round(const bool spec) {   // false: a speculative round that must be repeated the plain way
+        begin_round(spec);
+        if(!fused) { unfused_passes(); return true; }
+        fused_passes(spec);
+        return !spec || speculation_held();
+    }
+    void unfused_passes() {   // fractions per threshold, their neighbourhood means, the interpolation
+        ws.pad = QfPadKey();      // (the planes below are the same buffer)
+        float* planes = ws.planes.get((size_t)nt * C);
+        float* stats = ws.tmp2.get((size_t)nt * C);
+        member_pass(in.d, C, ne, 1, 0, th.d, nt, planes);                 // fractions per threshold (:453-472)
+        // stats[t] = neighbourhood(temp, hw, Mean) (:473) with the yarray epilogue (:494-506) fused into the column pass
+        box_stat(planes, ny, nx, nt, halfwidth, GPP_MEAN, stats, is3d ? ne : 1);
+        hipLaunchKernelGGL(k_qf_interp, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
+        GPP_HIP(hipGetLastError());
+    }
+};
+}   // namespace
+
+extern "C" int gpp_neighbourhood(const float* input, int ny, int nx, int ne, int is3d, int halfwidth, int statistic, float* out, int mem) {
+    GPP_TRY
+    NbhCall c{{}, input, ny, nx, ne, is3d, halfwidth, statistic, out, mem};
+    if(!c.check_args()) return GPP_OK;
+    ensure_device();
+    if(c.bands_eligible()) { c.run_bands(); return GPP_OK; }
+    c.bind(input, (size_t)c.C * ne, out, c.C, mem);
+    if(is3d) c.member_statistic();
+    neighbourhood2d(is3d ? c.ws.flat.p : c.in.d, ny, nx, halfwidth, statistic, c.o.d);
+    return c.done();
     GPP_CATCH
 }
 
@@ -1431,127 +1549,27 @@ extern "C" int gpp_neighbourhood_brute_force(const float* input, int ny, int nx,
         invalid("calc_quantile: Quantile must be between 0 and 1 inclusive");   // util.cpp:113-115
     if(ny <= 0 || nx <= 0 || ne <= 0) return GPP_OK;
     ensure_device();
-    const long C = (long)ny * nx;
-    InField in; OutField o;
-    in.bind(input, (size_t)C * ne, mem);
-    o.bind(out, C, mem);
-    brute(in.d, ny, nx, ne, halfwidth, statistic, quantile, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    Fields f;
+    f.bind(input, (size_t)ny * nx * ne, out, (size_t)ny * nx, mem);
+    brute(f.in.d, ny, nx, ne, halfwidth, statistic, quantile, f.o.d);
+    return f.done();
     GPP_CATCH
 }
 
 extern "C" int gpp_neighbourhood_quantile_fast(const float* input, int ny, int nx, int ne, int is3d, const float* quantile, int nq,
                                                int halfwidth, const float* thresholds, int nt, float* out, int mem) {
     GPP_TRY
-    if(halfwidth < 0) invalid("Half width must be > 0");                                   // :303-304,419-420
-    if(ny <= 0 || nx <= 0 || ne <= 0) return GPP_OK;                                        // :306-307
-    const long C = (long)ny * nx;
-    if(nq != 1 && nq != C) invalid("Quantile must be the same size as input, or size (1, 1)");   // :312-313
-    if(nt < 0) invalid("negative number of thresholds");
+    QfCall c{{}, input, ny, nx, ne, is3d, quantile, nq, halfwidth, thresholds, nt, out, mem};
+    if(!c.check_args()) return GPP_OK;
     ensure_device();
-    InField in, qf, th;
-    OutField o;
-    in.bind(input, (size_t)C * ne, mem);
-    o.bind(out, C, mem);
-    // 3-D input with at most 254 members, 16 thresholds and a halfwidth of 16: byte counts in padded planes + the box pass of
-    // qf_box.hip.  The counts come from the rank / sum-of-absolute-differences pass (k_qf_count) when the rows are whole float4s
-    const bool fused = nt > 0 && is3d && ne <= 254 && nt <= 16 && halfwidth <= QF_MAXHW && C < (1L << 31) && !path_env("GPP_QF_NO_FUSED");
-    bool ranked = fused && (ne & 3) == 0 && (reinterpret_cast<size_t>(in.d) & 15) == 0 && !path_env("GPP_QF_NO_RANKS");
-    if(nt > 0) th.bind(thresholds, nt, mem & ~GPP_HOST_F64);   // GPP_HOST_F64 applies to `input` only: quantile / thresholds stay float32
-    // GPP_Q_HOST: the quantile argument is host memory although the field is in HBM (the scalar quantile of a script beside a device-resident
-    // cube: uploaded by the caller and read back here for its validation it cost two transfers and a host round trip per call)
-    const int qmem = (mem & GPP_Q_HOST) ? GPP_MEM_HOST : (mem & ~GPP_HOST_F64);
-    auto check_q = [&](const float* hq) {   // :315-321
-        for(int i = 0; i < nq; i++)
-            if(is_valid(hq[i]) && (hq[i] < 0 || hq[i] > 1)) invalid("All quantiles must be >= 0 and <= 1");
-    };
-    const bool q_on_device = (qmem & GPP_MEM_DEVICE) != 0;
-    if(!q_on_device) check_q(quantile);
-    if(nt == 0) {   // :330-331: all missing
-        if(q_on_device) {
-            std::vector<float> hq(nq);
-            GPP_HIP(hipMemcpyAsync(hq.data(), quantile, sizeof(float) * nq, hipMemcpyDeviceToHost, stream())); GPP_HIP(hipStreamSynchronize(stream()));
-            check_q(hq.data());
-        }
-        hipLaunchKernelGGL(k_fill_nan, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), o.d, C);
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
-    }
-    qf.bind(quantile, nq, qmem);
-    if(!g_nb.h_pin) GPP_HIP(hipHostMalloc((void**)&g_nb.h_pin, 64, hipHostMallocDefault));
-    // Two rounds at most: the first may launch the count pass for the number of distinct thresholds the LAST call had (no host round trip in
-    // front of the kernels: the table's head and the quantile are read back once, behind the box pass); a table that turns out different
-    // stops the passes on the device and the second round does what every call did until round 5 -- wait for the table, then launch.
-    for(int round = 0; round < 2; round++) {
-        QfLut* lut = nullptr;
-        int lut_head[5] = {0, 0, 0, 1, 0};   // scale, off, U, flag, ident
-        int* rowflag = nullptr;
-        const bool spec = fused && ranked && round == 0 && g_nb.spec_nt == nt && g_nb.spec_U >= 0 && !path_env("GPP_QF_NO_SPEC");
-        if(fused) rowflag = g_nb.plane_flags.get(ny + 2);
-        if(ranked) {
-            lut = reinterpret_cast<QfLut*>(g_nb.qf.get((sizeof(QfLut) + 3) / 4));
-            hipLaunchKernelGGL(k_qf_lut, dim3(1), dim3(QF_NB), 0, stream(), th.d, nt, lut, rowflag, fused ? ny + 2 : 0);
-            GPP_HIP(hipGetLastError());
-            if(!spec) GPP_HIP(hipMemcpyAsync(lut_head, lut, sizeof(lut_head), hipMemcpyDeviceToHost, stream()));
-        }
-        else if(fused) GPP_HIP(hipMemsetAsync(rowflag, 0, sizeof(int) * (ny + 2), stream()));
-        std::vector<float> hq;
-        if(q_on_device && !spec) {   // quantile validation needs the values on the host
-            hq.resize(nq);
-            GPP_HIP(hipMemcpyAsync(hq.data(), quantile, sizeof(float) * nq, hipMemcpyDeviceToHost, stream()));
-        }
-        if(!spec && (ranked || q_on_device)) GPP_HIP(hipStreamSynchronize(stream()));
-        if(q_on_device && !spec) check_q(hq.data());
-        if(!spec && ranked) {
-            if(lut_head[3]) ranked = false;   // two thresholds in one bucket / a non-finite threshold: the compare-per-threshold pass
-            else { g_nb.spec_nt = nt; g_nb.spec_U = lut_head[2]; }
-        }
-        if(!fused) break;
-        QfGeom g = qf_geom(ny, nx);
-        unsigned char* cnt8 = reinterpret_cast<unsigned char*>(g_nb.planes.get(((size_t)(nt + 1) * g.Pp + 3) / 4));
-        if(g_nb.pad_ptr != cnt8 || g_nb.pad_gen != g_nb.planes.gen || g_nb.pad_y != ny || g_nb.pad_x != nx || g_nb.pad_t != nt || g_nb.pad_e != ne) {
-            // the padding is written when the planes are laid out (the passes below only ever write the cells of the field)
-            g_nb.pad_ptr = nullptr;
-            GPP_HIP(hipMemsetAsync(cnt8, 255, (size_t)nt * g.Pp, stream()));
-            GPP_HIP(hipMemsetAsync(cnt8 + (size_t)nt * g.Pp, ne, (size_t)g.Pp, stream()));
-            g_nb.pad_ptr = cnt8; g_nb.pad_gen = g_nb.planes.gen; g_nb.pad_y = ny; g_nb.pad_x = nx; g_nb.pad_t = nt; g_nb.pad_e = ne;
-        }
-        g.rowflag = rowflag;
-        if(ranked) qf_count_launch(in.d, C, ne, th.d, nt, lut, spec ? g_nb.spec_U : lut_head[2], cnt8, g, spec ? g_nb.spec_U : -1);
-        else member_pass(in.d, C, ne, 2, 0, th.d, nt, reinterpret_cast<float*>(cnt8), g);
-#ifdef QF_SIDE_EXPERIMENT   // timing experiment only: the box pass on the second stream WITHOUT waiting for the counts (wrong results)
-        if(path_env("GPP_QF_SIDE")) { qf_box_launch(cnt8, g, ne, halfwidth, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d, stream2()); GPP_HIP(hipStreamSynchronize(stream2())); }
-        else
-#endif
-        qf_box_launch(cnt8, g, ne, halfwidth, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
-        if(spec) {   // the one read-back of the call: did the count pass run, and the quantile(s) for the validation the slow round does first
-            GPP_HIP(hipMemcpyAsync(g_nb.h_pin, rowflag + ny + 1, sizeof(int), hipMemcpyDeviceToHost, stream()));
-            if(q_on_device) {
-                if(nq == 1) GPP_HIP(hipMemcpyAsync(g_nb.h_pin + 1, quantile, sizeof(float), hipMemcpyDeviceToHost, stream()));
-                else { hq.resize(nq); GPP_HIP(hipMemcpyAsync(hq.data(), quantile, sizeof(float) * nq, hipMemcpyDeviceToHost, stream())); }
-            }
-            GPP_HIP(hipStreamSynchronize(stream()));
-            if(q_on_device) check_q(nq == 1 ? reinterpret_cast<const float*>(g_nb.h_pin + 1) : hq.data());
-            if(g_nb.h_pin[0] != 0) { g_nb.spec_nt = -1; g_nb.spec_U = -1; continue; }   // other thresholds than the last call's: once more, the slow way
-        }
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
-    }
-    g_nb.pad_ptr = nullptr;   // (the unfused path below uses the same buffer)
-    float* planes = g_nb.planes.get((size_t)nt * C);
-    float* stats = g_nb.tmp2.get((size_t)nt * C);
-    member_pass(in.d, C, ne, 1, 0, th.d, nt, planes);                 // fractions per threshold (:453-472)
-    // stats[t] = neighbourhood(temp, hw, Mean) (:473) with the yarray epilogue (:494-506) fused into the column pass
-    box_stat(planes, ny, nx, nt, halfwidth, GPP_MEAN, stats, is3d ? ne : 1);
-    hipLaunchKernelGGL(k_qf_interp, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    c.bind_fields();
+    if(nt == 0) return c.all_missing();
+    c.bind_quantile();
+    // Two rounds at most.  The first may be speculative: the table's head and the quantile are read back once, behind the box pass.  A table that turns out
+    // different stops the passes on the device, and the second round does what every call did until round 5 -- wait for the table, then launch.
+    const bool held = c.may_speculate() && c.round(true);   // the speculative round
+    if(!held) c.round(false);                                // the plain round
+    return c.done();
     GPP_CATCH
 }
 
@@ -1576,15 +1594,12 @@ extern "C" int gpp_calc_statistic(const float* array, long rows, int len, int st
     if(statistic == GPP_QUANTILE || statistic == GPP_RANDOMCHOICE) runtime("Internal error. Cannot compute statistic");
     if(rows <= 0) return GPP_OK;
     ensure_device();
-    InField in; OutField o;
-    in.bind(array, (size_t)rows * len, mem);
-    o.bind(out, rows, mem);
-    if(len <= MEMBER_EC && statistic != GPP_MEDIAN && len > 0) member_pass(in.d, rows, len, 0, statistic, nullptr, 0, o.d);
-    else hipLaunchKernelGGL(k_rows_statistic, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), in.d, rows, len, statistic, o.d);
+    Fields f;
+    f.bind(array, (size_t)rows * len, out, rows, mem);
+    if(len <= MEMBER_EC && statistic != GPP_MEDIAN && len > 0) member_pass(f.in.d, rows, len, 0, statistic, nullptr, 0, f.o.d);
+    else hipLaunchKernelGGL(k_rows_statistic, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), f.in.d, rows, len, statistic, f.o.d);
     GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return f.done();
     GPP_CATCH
 }
 // gridpp::calc_quantile(vec, q) / (vec2, q) / (vec3, vec2 q) (util.cpp:111-207): nq == 1 or nq == rows
@@ -1598,15 +1613,12 @@ extern "C" int gpp_calc_quantile(const float* array, long rows, int len, const f
     else memcpy(hq.data(), quantile, sizeof(float) * nq);
     for(long i = 0; i < nq; i++)
         if(hq[i] < 0 || hq[i] > 1) invalid("calc_quantile: Quantile must be between 0 and 1 inclusive");   // util.cpp:113-115 (NaN passes)
-    InField in, q; OutField o;
-    in.bind(array, (size_t)rows * len, mem);
+    Fields f; InField q;
+    f.bind(array, (size_t)rows * len, out, rows, mem);
     q.bind(quantile, nq, mem);
-    o.bind(out, rows, mem);
-    hipLaunchKernelGGL(k_rows_quantile, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), in.d, rows, len, q.d, nq == 1 ? 0 : 1, o.d);
+    hipLaunchKernelGGL(k_rows_quantile, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), f.in.d, rows, len, q.d, nq == 1 ? 0 : 1, f.o.d);
     GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return f.done();
     GPP_CATCH
 }
 

@@ -128,3 +128,25 @@ def test_banded_neighbourhood_host_path_is_bit_identical(shape, monkeypatch):
     monkeypatch.setenv("GPP_NBH_NO_BANDS", "1")
     ref = np.array(gridpp.neighbourhood(f, 7, gridpp.Mean))
     assert (out.view(np.uint32) == ref.view(np.uint32)).all()
+
+
+@pytest.mark.parametrize("shape", [(128, 8200), (160, 8200)])
+def test_banded_neighbourhood_host_path_with_fewer_than_six_bands(shape, monkeypatch):
+    """Wide, low planes just over the 2^20 cells at which the bands start: 4 and 5 row segments of 32 rows for Mean / Count and for Min / Max up to
+    halfwidth 16 (four- and five-band plans, every band clamped to at least one segment), 4 segments for Max with halfwidth 32 on the first shape and 3
+    on the second, which declines the bands.  With 32-row segments the last chunk of every band reaches past the band's last window: those rows are
+    uploaded with the band.  Same bits as one upload / the kernel / one download (GPP_NBH_NO_BANDS), from float32 and float64 arrays."""
+    import gridpp_amd as gridpp
+    rng = np.random.default_rng(shape[0])
+    Y, X = shape
+    f = rng.uniform(-5, 10, (Y, X)).astype(np.float32)
+    f[rng.random((Y, X)) < 0.003] = np.nan                      # scattered missing values
+    f[Y // 2:Y // 2 + 40, X // 3:X // 3 + 50] = np.nan          # and a block of them (the counted chunks of the box kernel)
+    for stat, hw in [(gridpp.Mean, 0), (gridpp.Mean, 16), (gridpp.Count, 5), (gridpp.Min, 1), (gridpp.Max, 32)]:
+        monkeypatch.setenv("GPP_NBH_NO_BANDS", "1")
+        ref = np.array(gridpp.neighbourhood(f, hw, stat))
+        monkeypatch.delenv("GPP_NBH_NO_BANDS")
+        for arr in (f, f.astype(np.float64)):
+            out = np.array(gridpp.neighbourhood(arr, hw, stat))
+            assert out.dtype == np.float32 and out.shape == ref.shape
+            assert (out.view(np.uint32) == ref.view(np.uint32)).all(), (stat, hw, arr.dtype, int((out.view(np.uint32) != ref.view(np.uint32)).sum()))
