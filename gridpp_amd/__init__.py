@@ -834,6 +834,13 @@ def oi_last_stats():
                 union_kernel_ms=s.union_kernel_ms, fallback_subtiles=s.fallback_subtiles, big_cells=s.big_cells)
 
 
+def obs_index_axes(points):
+    """Diagnostics: the two coordinate axes (0 = x, 1 = y, 2 = z) the observation index of `points` is binned on."""
+    a, b = C.c_int(-1), C.c_int(-1)
+    check(lib().gpp_debug_obs_axes(points._h, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
 # ---- nearest (src/api/nearest.cpp:124-144) ----------------------------------------------------------
 def nearest(igrid, opoints, values):
     """All eight overloads of src/api/nearest.cpp: Grid|Points -> Grid|Points, with or without a leading time dimension."""

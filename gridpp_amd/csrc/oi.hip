@@ -1288,6 +1288,18 @@ extern "C" int gpp_oi_last_stats(gpp_oi_stats* s) {
     GPP_CATCH
 }
 
+// the two coordinate axes (0 = x, 1 = y, 2 = z) the observation index of a point set is binned on -- the index is built if it is not there yet
+extern "C" int gpp_debug_obs_axes(gpp_points* points, int* axis_a, int* axis_b) {
+    GPP_TRY
+    if(!points || !axis_a || !axis_b) invalid("points / axis_a / axis_b is NULL");
+    if(points->n <= 0) invalid("the point set is empty");
+    ensure_device();
+    const gpp_obs_index* const ix = gpp_build_obs_index(points);
+    *axis_a = ix->axis_a; *axis_b = ix->axis_b;
+    return GPP_OK;
+    GPP_CATCH
+}
+
 // ---- structure functions, host side (float semantics of the C++ overloads the reference gets) -------------------
 static float st_localization(int kind, float h, float min_rho) {
     switch(kind) {
@@ -2205,6 +2217,7 @@ struct OiCall {
 #ifdef GPP_UNION_STATS
         fprintf(stderr, "[gpp] union: fallback reasons: slots %llu, union>40 %llu, extras>12 %llu, layout %llu, per-cell extras>6 %llu; per tile: insertions %.1f, evictions %.1f, candidates evaluated outside the bulk disc %.1f, records loaded in phase 2 %.1f\n",
                                 counters[4], counters[5], counters[6], counters[7], counters[8], counters[9] / (double)a.ntiles, counters[10] / (double)a.ntiles, counters[11] / (double)a.ntiles, counters[12] / (double)a.ntiles);
+        fprintf(stderr, "[gpp] union: tiles whose slot-ownership masks disagree with the slots: %llu\n", counters[13]);
 #endif
         if(timing_env("GPP_SCAN_STATS")) { fprintf(stderr, "[gpp] wave-level insertions per tile histogram:"); for(int i = 0; i < 70; i++) fprintf(stderr, " %d:%llu", i, counters[4 + i]); fprintf(stderr, "\n"); }
     }

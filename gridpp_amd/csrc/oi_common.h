@@ -345,6 +345,23 @@ __device__ __forceinline__ float wave_max(float v) {
     GPP_DPP_RED("v_max_f32_dpp");
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+// OR / AND of a 64-bit mask over the 64 lanes: the same six steps on each half (k_oi_union: which slots the cells of a tile hold)
+__device__ __forceinline__ unsigned long long wave_or64(const unsigned long long m) {
+    unsigned v = (unsigned)m, w = (unsigned)(m >> 32);
+    GPP_DPP_RED("v_or_b32_dpp");
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+    v = w;
+    GPP_DPP_RED("v_or_b32_dpp");
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 63) << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long wave_and64(const unsigned long long m) {
+    unsigned v = (unsigned)m, w = (unsigned)(m >> 32);
+    GPP_DPP_RED("v_and_b32_dpp");
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+    v = w;
+    GPP_DPP_RED("v_and_b32_dpp");
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 63) << 32) | lo;
+}
 #undef GPP_DPP_RED
 
 // maximum of a double over the 64 lanes (DPP moves of its two halves; every lane must hold a value >= -1.0, the identity)

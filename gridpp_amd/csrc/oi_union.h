@@ -289,6 +289,8 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         }
     }
     int cnt = 0;
+    unsigned long long mine = 0ull;    // bit s: this cell holds slot s, i.e. L.rho[s][lane] < inf -- kept at every store and eviction, so that nobody has to read
+                                       // the slots back from LDS to learn it (live_mask, the classification)
     unsigned long long alloc = 0ull;   // allocated slots (wave-uniform)
     bool fb = false;                   // wave-uniform: this tile goes to k_oi
     constexpr unsigned long long FULL = U_WCAP >= 64 ? ~0ull : ((1ull << (U_WCAP & 63)) - 1ull);
@@ -296,15 +298,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
     // slot LDS reads issue back to back (ds_read2st64) instead of one latency per slot
 #pragma unroll
     for(int w = 0; w < U_WCAP; ++w) L.rho[w][lane] = INFINITY;
-    auto live_mask = [&]() {   // slots some cell still holds
-        unsigned long long live = 0ull;
-        float rv[U_WCAP];
-#pragma unroll
-        for(int w = 0; w < U_WCAP; ++w) rv[w] = L.rho[w][lane];
-#pragma unroll
-        for(int w = 0; w < U_WCAP; ++w) live |= ((wave_ballot(rv[w] < INFINITY) != 0ull) ? 1ull : 0ull) << w;
-        return live;
-    };
+    auto live_mask = [&]() { return wave_or64(mine); };   // slots some cell still holds
     // The worst kept entry of this lane: smallest rho r0, a slot s0 that holds it, and whether more than one slot does.  Two levels --
     // minima of groups of eight slots, then the eight values of the group that holds the minimum, read again from LDS (its index is
     // the lane's own): ~70 instructions.  One flat pass (compare, select, count for each of the 40 slots, each triple with a wait
@@ -501,6 +495,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                     alloc |= 1ull << slot;
                     if(lane == 0) { L.wpos[slot] = __builtin_amdgcn_readlane(posv, c); L.worig[slot] = (int)orig; }
                     L.rho[slot][lane] = want ? rho : INFINITY;
+                    mine |= want ? (1ull << slot) : 0ull;
                     if(want) {
                         if(cnt < K) {
                             if(cnt == 0 || rho < wr || (rho == wr && orig > wo)) { wr = rho; ws = slot; wo = orig; }
@@ -508,6 +503,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                         }
                         else {
                             L.rho[ws][lane] = INFINITY;
+                            mine &= ~(1ull << ws);
                             float r0;
                             int s0;
                             bool multi;
@@ -673,6 +669,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                                         if(q < n) {
                                             const bool ok = rho[q] > 0.0f;   // oi.cpp:253
                                             L.rho[nb][lane] = ok ? rho[q] : INFINITY;
+                                            mine |= ok ? (1ull << nb) : 0ull;
                                             cnt += ok ? 1 : 0;
                                             nb++;
                                         }
@@ -685,6 +682,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                                 const float rho = eval(rec, met, c);
                                 const bool ok = rho > 0.0f;   // oi.cpp:253
                                 L.rho[nb][lane] = ok ? rho : INFINITY;
+                                mine |= ok ? (1ull << nb) : 0ull;
                                 cnt += ok ? 1 : 0;
                                 nb++;
                             }
@@ -770,17 +768,17 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
     int m = 0;             // this cell's extras: count and their indices (4 bits each)
     unsigned elist = 0u;
     if(!fb && upd != 0ull) {
-        float rv[U_WCAP];
-#pragma unroll
-        for(int w = 0; w < U_WCAP; ++w) rv[w] = L.rho[w][lane];
-        // (selects, not branches: written with `if` this loop compiled to two scalar branches per slot -- eighty instruction-buffer
-        //  refills per tile)
-#pragma unroll
-        for(int w = 0; w < U_WCAP; ++w) {
-            const unsigned long long mk = wave_ballot(rv[w] < INFINITY) & upd;
-            const unsigned long long isc = (mk == upd) ? 1ull : 0ull, ise = (mk != 0ull) ? (isc ^ 1ull) : 0ull;
-            coreM |= isc << w;
-            extM |= ise << w;
+        // Round 7: from the masks -- union: slots some updating cell holds; core: slots every updating cell holds (a cell that does not update holds
+        // none: it adds nothing to the OR and counts as all-ones in the AND).  Two 64-bit wave reductions (24 DPP steps) where every slot of every
+        // lane used to be read back from LDS, compared and balloted (40 of each, with their scalar follow-ups).
+        const bool up = cnt > 0;
+        const unsigned long long unionM = wave_or64(up ? mine : 0ull);
+        coreM = wave_and64(up ? mine : ~0ull);
+        extM = unionM & ~coreM;
+        if constexpr(UNION_STATS) {   // (diagnostic build: the mask against the slots themselves; counters[13] counts tiles where they disagree)
+            unsigned long long held = 0ull;
+            for(int w = 0; w < U_WCAP; ++w) held |= (L.rho[w][lane] < INFINITY ? 1ull : 0ull) << w;
+            if(wave_ballot(held != mine) != 0ull && lane == 0) atomicAdd(&a.counters[13], 1ull);
         }
     }
     // row i of the shared factorisation = lane i: the slot of THIS wave that holds its observation (-1: no cell of this tile selected it;
@@ -861,8 +859,8 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         else {
             int ai = 0;
             for(unsigned long long mm = extM; mm; mm &= mm - 1ull, ++ai) {
-                const int w = __builtin_ctzll(mm);
-                if(L.rho[w][lane] < INFINITY) { elist |= (unsigned)ai << (4 * (m & 7)); m++; }
+                const int w = __builtin_ctzll(mm);   // (ascending slot order: extras row ai = popcount(extM below slot w), as the finish expects)
+                if((mine >> w) & 1ull) { elist |= (unsigned)ai << (4 * (m & 7)); m++; }
             }
             if(wave_ballot(m > U_MAXM) != 0ull) { fb = true; if(UNION_STATS && lane == 0) atomicAdd(&a.counters[8], 1ull); }
         }
