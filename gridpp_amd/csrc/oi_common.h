@@ -146,6 +146,44 @@ __device__ __forceinline__ double d_exp_core(double x) {   // -110 <= x <= 0 (no
     p = __builtin_fma(t, p, t);
     return ldexp(p, k >> 7);
 }
+// one double operation with its constant as the scalar operand the encoding allows (a 64-bit constant is no literal on gfx950: left to the
+// compiler it is copied into a vector register pair in front of every group of evaluations)
+__device__ __forceinline__ double d_mul_sc(double a, double c) {
+    double o;
+    asm("v_mul_f64 %0, %1, %2" : "=v"(o) : "v"(a), "s"(c));
+    return o;
+}
+__device__ __forceinline__ double d_fma_sc(double a, double c, double b) {   // a * c + b
+    double o;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(a), "s"(c), "v"(b));
+    return o;
+}
+__device__ __forceinline__ double d_fma_step_sc(double p, double r, double c) {   // p * r + c
+    double o;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(p), "v"(r), "s"(c));
+    return o;
+}
+// exp(-t / 2) for 0 <= t <= 225: the very double d_exp_core(-0.5 * t) returns, without the multiplication by -0.5.  The factor is folded into
+// the constants: kf is the same integer (t * (-64 / ln2) is the old product exactly: -64 / ln2 is the old constant times -1/2), the reduced
+// argument comes out as r' = -2 r, and the Horner value behind coefficient i is the old one times -1/32, 1/16, -1/8, 1/4, -1/2 -- every
+// intermediate is the old one times a power of two (nothing near the underflow range: a non-zero |r| is >= 2^-300), so every rounding falls
+// the same way and the last product p' r' IS the old p r.  tools/ubench/exp_half_sq.c restates both forms for the CPU;
+// tests/test_exp_half_sq.py compares them bit by bit.
+__device__ __forceinline__ double d_exp_half_neg(double t) {
+    const double kf = rint(d_mul_sc(t, -184.66496523378730813 / 2.0));     // -64 / ln2
+    double r = d_fma_sc(kf, 6.93147180369123816490e-01 / 64.0, t);
+    r = d_fma_sc(kf, 1.90821492927058770002e-10 / 64.0, r);                // r' = -2 r
+    const int k = (int)kf;
+    const double tb = d_exptab()[k & 127];
+    double p = -8.33333333333333333333e-03 / 32.0;
+    p = d_fma_step_sc(p, r, 4.16666666666666666667e-02 / 16.0);
+    p = d_fma_step_sc(p, r, -1.66666666666666666667e-01 / 8.0);
+    p = d_fma_step_sc(p, r, 0.125);
+    p = __builtin_fma(p, r, -0.5);
+    p = p * r;
+    p = __builtin_fma(tb, p, tb);
+    return ldexp(p, k >> 7);
+}
 __device__ __forceinline__ double d_exp_nonpos(double x) {
     if(x < -110.0) return 0.0;   // (float)exp(x) == 0 below -103.98
     const double kf = rint(x * 1.4426950408889634074);
@@ -174,14 +212,13 @@ __device__ __forceinline__ double d_exp_nonpos(double x) {
 __device__ __forceinline__ float d_div_by(float dist, double rlen) { return (float)((double)dist * rlen); }
 // d_barnes_rho for a valid, non-zero length, without divergent branches.  Same values for every valid dist.  A NaN dist gives exp(-112.5) = 0
 // (fminf drops the NaN) -- what the reference returns for !is_valid(dist) (structure.cpp:28-29) -- and not NaN: callers that need to
-// know about a missing coordinate test d_valid() themselves (d_barnes_corr_flat does for the elevation / laf factors).  d_exp_core is
-// called down to -112.5 here (tests/test_exp_table.py checks [-112.5, -110] too).
+// know about a missing coordinate test d_valid() themselves (d_barnes_corr_flat does for the elevation / laf factors).  The exponential
+// goes down to exp(-112.5) here (tests/test_exp_table.py checks [-112.5, -110] too; d_exp_half_neg returns d_exp_core's doubles).
 __device__ __forceinline__ float d_barnes_rho_flat(float dist, double rlen) {
     // (|v| cut at 15: exp(-112.5) = 1e-49 is 0 in float32 like everything below exp(-103.98) -- one float32 minimum instead of a double
     //  maximum in front of the exp and a compare + select behind it)
     const float v = fminf(fabsf(d_div_by(dist, rlen)), 15.0f);
-    const double e = -0.5 * (double)v * (double)v;
-    return (float)d_exp_core(e);
+    return (float)d_exp_half_neg((double)v * (double)v);   // (v^2 is exact in double)
 }
 __device__ __forceinline__ float d_barnes_rho(float dist, float length) {
     if(!d_valid(length) || length == 0) return 1.0f;

@@ -395,7 +395,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             // |gz| + R) gives |ox - gx| <= dist (1 + 2^-22) < R - 2^-24 (|gx| + R) <= the distance of either rounded corner, on every axis.
             // The six compares are made only when some cell of the wave holds a candidate that close to R (pruning by the worst kept rho
             // keeps the candidates far inside: never on the headline workload).
-            if(wave_ballot(ok && dist > near_r) != 0ull) ok = ok && ox > lox && ox < hix && oy > loy && oy < hiy && oz > loz && oz < hiz;
+            if((wave_ballot(ok) & wave_ballot(dist > near_r)) != 0ull) ok = ok && ox > lox && ox < hix && oy > loy && oy < hiy && oz > loz && oz < hiz;
             float rho = 0.0f;
             if constexpr(PLAIN) {
                 rho = hh ? d_barnes_rho_flat(dist, rh) : 1.0f;
@@ -430,7 +430,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         auto eval_n = [&](const float4& rec, const float2& met, const int (&cc)[EV], float (&rho)[EV]) {
             float dist[EV];
             bool ok[EV];
-            bool anynear = false;
+            unsigned long long anynear = 0ull;   // (wave-uniform: the lanes' compare masks, combined and tested by scalar instructions)
 #pragma unroll
             for(int q = 0; q < EV; ++q) {
                 const float ox = readlane_f(rec.x, cc[q]), oy = readlane_f(rec.y, cc[q]), oz = readlane_f(rec.z, cc[q]);
@@ -439,9 +439,9 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 d2 = d2 + dz * dz;
                 dist[q] = d_sqrt_cr(d2);
                 ok[q] = d2 <= thr2 && dist[q] <= R;
-                anynear = anynear || (ok[q] && dist[q] > near_r);
+                anynear |= wave_ballot(ok[q]) & wave_ballot(dist[q] > near_r);
             }
-            if(wave_ballot(anynear) != 0ull) {   // (see eval: the strictly-inside box of the radius query, only for candidates within ulps of R)
+            if(anynear != 0ull) {   // (see eval: the strictly-inside box of the radius query, only for candidates within ulps of R)
 #pragma unroll
                 for(int q = 0; q < EV; ++q) {
                     const float ox = readlane_f(rec.x, cc[q]), oy = readlane_f(rec.y, cc[q]), oz = readlane_f(rec.z, cc[q]);
@@ -480,8 +480,17 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             while(mask != 0ull && !fb) {
                 const int c = __builtin_ctzll(mask);
                 mask &= mask - 1ull;
+                if(UNION_STATS && lane == 0) atomicAdd(&a.counters[11], 1ull);   // candidates behind the wave-level prune
+                if constexpr(!SP) {   // no cell inside its threshold: `ok` of eval is false in every lane, rho is 0 and nobody can want the candidate --
+                    // leave before the root, the quotient and the exponential (headline: 10.7 candidates per tile get here, 3.0 are wanted).  Not on the
+                    // spatially varying form: it sits at its 168 registers, and the early test costs it 8 bytes of scratch.
+                    const float ox = readlane_f(rec.x, c), oy = readlane_f(rec.y, c), oz = readlane_f(rec.z, c);
+                    const float dx = ox - gx, dy = oy - gy, dz = oz - gz;
+                    float d2 = dx * dx + dy * dy;
+                    d2 = d2 + dz * dz;
+                    if(wave_ballot(d2 <= thr2) == 0ull) continue;
+                }
                 const float rho = eval(rec, met, c);
-                if(UNION_STATS && lane == 0) atomicAdd(&a.counters[11], 1ull);   // candidates evaluated behind the wave-level prune
                 {
                 const unsigned orig = (unsigned)__builtin_amdgcn_readlane(__float_as_int(met.y), c);
                 // oi.cpp:253 (rho > 0) and :262-273 (keep the max_points largest, ties -> lower observation index)
@@ -1303,6 +1312,11 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         }
         UPROF(8);   // row load + elimination
         // export: L_C rows packed, B rows (stride bs), L_C^-1 d, Schur complement, d'
+        // (the export and the finish compare against copies of c and u the optimiser cannot see through, like st.h above: it otherwise keeps
+        //  the `j < c` results of the unrolled elimination for them -- parked in the lanes of a vector register, a v_writelane there and a
+        //  v_readlane here for each, where doing the scalar compare again costs nothing)
+        int ce = c, ue = u;
+        asm("" : "+s"(ce), "+s"(ue));
         const int ea = lane - c;   // extras row index of this lane
         {   // one masked store per column: every lane has a last column and two bases (columns below c / from c on); written
             // with nested ifs this loop compiled to ~60 mostly scalar instructions and a dozen branches per column
@@ -1312,11 +1326,11 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             else if(lane == 63) { maxp = u - 1; baseLo = oZ; baseHi = oD - c; }
 #pragma unroll
             for(int p = 0; p < NC; ++p) {
-                const int bse = (p < c) ? baseLo : baseHi;
+                const int bse = (p < ce) ? baseLo : baseHi;
                 if(p <= maxp) sv[bse + p] = row[p];
             }
         }
-        if(U_MAXU > NC && u > NC && !GPP_DBG(a, 16)) {   // Schur complement / d' of the late columns: entry - (row of B or L_C^-1 d) . (row p of B)
+        if(U_MAXU > NC && ue > NC && !GPP_DBG(a, 16)) {   // Schur complement / d' of the late columns: entry - (row of B or L_C^-1 d) . (row p of B)
             // (row p of B has just been exported: it comes back as LDS broadcasts, one read per two multiply-adds, instead of a
             //  v_readlane pair per multiply-add; columns c.. of the padded row are multiplied by zeros)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1325,12 +1339,12 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
 #pragma unroll
             for(int b = 0; b < 8; ++b) {
                 const int p = NC + b;
-                if(p < u) {
+                if(p < ue) {
                     const bool mine = (lane >= p && lane < u) || lane == 63;
                     double acc = mine ? L.late[b][lidx] : 0.0;
                     const double* const bp = sv + oB + (p - c) * bs;
 #pragma unroll
-                    for(int k = 0; k < NC; ++k) if(k < c) acc = __builtin_fma(-row[k], bp[k], acc);
+                    for(int k = 0; k < NC; ++k) if(k < ce) acc = __builtin_fma(-row[k], bp[k], acc);
                     if(lane >= p && lane < u) sv[oS + ea * nE + (p - c)] = acc;
                     else if(lane == 63) sv[oD + (p - c)] = acc;
                 }
@@ -1444,11 +1458,13 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         }
         else {
         // ============= per cell (lane): forward substitution of G against L_C, then its own extras ==================
+        int cf = c;   // (see the export)
+        asm("" : "+s"(cf));
         double z[NC];
 #pragma unroll
         for(int k = 0; k < NC; ++k) {
             double zk = 0.0;
-            if(k < c && !GPP_DBG(a, 32)) {
+            if(k < cf && !GPP_DBG(a, 32)) {
                 const double gk = (double)gf[k];
                 double acc0 = 0.0, acc1 = 0.0;
                 const double* lrow = sv + oL + k * (k + 1) / 2;
@@ -1459,9 +1475,14 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 }
                 zk = (gk - (acc0 + acc1)) * sv[oI + k];
                 inc = __builtin_fma(zk, sv[oZ + k], inc);
-                a00 = __builtin_fma(zk, zk, a00);
             }
             z[k] = zk;
+        }
+        // 1 - K G^T only when a variance is asked for (wave-uniform; the entries z[k], k >= c, are zeros: they leave the sum as it is)
+        const bool want_var = a.out_var != nullptr;
+        if(want_var) {
+#pragma unroll
+            for(int k = 0; k < NC; ++k) a00 = __builtin_fma(z[k], z[k], a00);
         }
         if(mmax > 0 && !GPP_DBG(a, 64)) {
             double ll[U_MAXM * (U_MAXM + 1) / 2], qv[U_MAXM], tv[U_MAXM], il[U_MAXM];
@@ -1475,7 +1496,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                     double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
                     for(int j0 = 0; j0 < NC; j0 += 4) {
-                        if(j0 < c) {   // reads at most 3 elements past the row (multiplied by z = 0; written data: the next row, the Schur complement, d', three zeros)
+                        if(j0 < cf) {   // reads at most 3 elements past the row (multiplied by z = 0; written data: the next row, the Schur complement, d', three zeros)
                             acc0 = __builtin_fma(brow[j0], z[j0], acc0);
                             acc1 = __builtin_fma(brow[j0 + 1], z[j0 + 1], acc1);
                             acc0 = __builtin_fma(brow[j0 + 2], z[j0 + 2], acc0);
@@ -1504,7 +1525,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                     tv[i] = dq * rs;
                     if(valid) {
                         inc = __builtin_fma(qv[i], tv[i], inc);
-                        a00 = __builtin_fma(qv[i], qv[i], a00);
+                        if(want_var) a00 = __builtin_fma(qv[i], qv[i], a00);
                         if(!a.allow_extrap) {
                             const float de = __int_as_float(LS.worig[ai]);
                             maxInc = fmaxf(maxInc, de); minInc = fminf(minInc, de);
