@@ -1625,6 +1625,191 @@ def window(array, length, statistic, before=False, keep_missing=False, missing_e
     return out
 
 
+# ---- weather diagnostics (include/gridpp.h:49-67,1249-1367; src/api/humidity.cpp, pressure.cpp, qnh.cpp, wind.cpp) ------------------
+# the `static const float` constants of include/gridpp.h:51-67, as SWIG hands them out: the float32 value as a Python float
+MV_CML = -999.0
+pi = float(np.float32(3.14159265))
+lapse_rate = float(np.float32(0.0065))
+standard_surface_temperature = float(np.float32(288.15))
+gravit = float(np.float32(9.80665))
+molar_mass = float(np.float32(0.0289644))
+gas_constant_mol = float(np.float32(8.31447))
+gas_constant_si = float(np.float32(287.05))
+
+
+def _pointwise(entry, which, args, names, size_checks):
+    """One diagnostic: every argument a scalar -> the host-only scalar form (a Python float back); otherwise 1-D arrays of one length
+    (host, or all torch CUDA tensors) through the kernel.  size_checks: (i, j, message) in the reference's order."""
+    if all(_ndim(a) == 0 for a in args):
+        vals = (C.c_float * len(args))(*[float(a) for a in args])
+        out = C.c_float(np.nan)
+        check(lib().gpp_diagnostic_scalar(which, vals, len(args), C.byref(out)))
+        return out.value
+    mem = _mem(*args)
+    f64 = mem == _capi.MEM_HOST and _wants_f64(*args)
+    arrs = [_vec(a, 1, n) if _is_dev(a) else _vec(a, 1, n, np.float64 if f64 else np.float32) for a, n in zip(args, names)]
+    for i, j, message in size_checks:
+        if _shape(arrs[i]) != _shape(arrs[j]):
+            raise ValueError(message)
+    n = _shape(arrs[0])[0]
+    if n == 0:
+        return _empty_like_field((0,), arrs[0]) if mem == _capi.MEM_DEVICE else np.zeros(0, np.float32)
+    _sync_if_dev(mem)
+    out = _empty_like_field((n,), arrs[0])
+    check(entry(*[_ptr(a) for a in arrs], n, _ptr(out), mem | (_capi.HOST_F64 if f64 else 0)))
+    return out
+
+
+def dewpoint(temperature, relative_humidity):
+    """src/api/humidity.cpp:5-32: dewpoint temperature [K] from temperature [K] and relative humidity [1]; never above the temperature
+    (a relative humidity <= 0 returns the temperature).  Scalars or 1-D arrays."""
+    return _pointwise(lib().gpp_dewpoint, _capi.DIAG_DEWPOINT, (temperature, relative_humidity), ("temperature", "relative_humidity"),
+                      [(0, 1, "Temperature and relative_humidity vectors are not the same size")])
+
+
+def relative_humidity(temperature, dewpoint):
+    """src/api/humidity.cpp:33-90: relative humidity [1] from temperature and dewpoint temperature [K], by the saturation pressure
+    table between 173.16 K and 368.16 K (clamped outside); 1 where temperature <= dewpoint.  Scalars or 1-D arrays."""
+    return _pointwise(lib().gpp_relative_humidity, _capi.DIAG_RELATIVE_HUMIDITY, (temperature, dewpoint), ("temperature", "dewpoint"),
+                      [(0, 1, "Temperature and dewpoint vectors are not the same size")])
+
+
+def wetbulb(temperature, pressure, relative_humidity):
+    """src/api/humidity.cpp:91-122: wetbulb temperature [K] from temperature [K], pressure [Pa] and relative humidity [1]; NaN for a
+    relative humidity <= 0.  Scalars or 1-D arrays."""
+    return _pointwise(lib().gpp_wetbulb, _capi.DIAG_WETBULB, (temperature, pressure, relative_humidity),
+                      ("temperature", "pressure", "relative_humidity"),
+                      [(0, 1, "Temperature and pressure vectors are not the same size"),
+                       (0, 2, "Temperature and relative_humidity vectors are not the same size")])
+
+
+def pressure(ielev, oelev, ipressure, itemperature=288.15):
+    """src/api/pressure.cpp:5-26: the pressure [Pa] at elevation oelev [m] from the pressure at ielev and the temperature [K] there.
+    Scalars (itemperature defaults to 288.15) or four 1-D arrays."""
+    message = "pressure: Input arguments must be of the same size"
+    return _pointwise(lib().gpp_pressure, _capi.DIAG_PRESSURE, (ielev, oelev, ipressure, itemperature),
+                      ("ielev", "oelev", "ipressure", "itemperature"), [(0, 1, message), (0, 2, message), (0, 3, message)])
+
+
+def sea_level_pressure(ps, altitude, temperature, rh=MV, dewpoint=MV):
+    """src/api/pressure.cpp:28-93: surface pressure [Pa] reduced to sea level from the altitude [m], the 2 m temperature [K] and the
+    relative humidity [1] or else the dewpoint temperature [K] (both NaN: dewpoint = temperature - 3).  Scalars (rh and dewpoint default
+    to MV) or five 1-D arrays.  RuntimeError for a NaN altitude, a NaN temperature and unphysical values, tested in that order; the array
+    form raises for the lowest offending index."""
+    message = "slp: Input arguments must be of the same size"
+    return _pointwise(lib().gpp_sea_level_pressure, _capi.DIAG_SEA_LEVEL_PRESSURE, (ps, altitude, temperature, rh, dewpoint),
+                      ("ps", "altitude", "temperature", "rh", "dewpoint"), [(0, 1, message), (0, 2, message), (0, 3, message), (0, 4, message)])
+
+
+def qnh(pressure, altitude):
+    """src/api/qnh.cpp:6-41: QNH [Pa] from pressure [Pa] and altitude [m]; 0 for a pressure of 0.  Scalars or 1-D arrays."""
+    return _pointwise(lib().gpp_qnh, _capi.DIAG_QNH, (pressure, altitude), ("pressure", "altitude"),
+                      [(0, 1, "Pressure and altitude vectors are not the same size")])
+
+
+def wind_speed(xwind, ywind):
+    """src/api/wind.cpp:6-19.  No validity test: NaN propagates.  Scalars or 1-D arrays."""
+    return _pointwise(lib().gpp_wind_speed, _capi.DIAG_WIND_SPEED, (xwind, ywind), ("xwind", "ywind"),
+                      [(0, 1, "xwind and ywind must be of the same size")])
+
+
+def wind_direction(xwind, ywind):
+    """src/api/wind.cpp:20-37: the direction the wind comes from [degrees], 180 for (0, 0).  Scalars or 1-D arrays."""
+    return _pointwise(lib().gpp_wind_direction, _capi.DIAG_WIND_DIRECTION, (xwind, ywind), ("xwind", "ywind"),
+                      [(0, 1, "xwind and ywind must be of the same size")])
+
+
+# ---- value transforms (include/gridpp.h:2345-2435, src/api/transform.cpp) -------------------------------------------------------------
+def _typemap_shape(shape):
+    """The shape the reference's output typemaps give an empty nested vector (swig/vector.i:332-339,515-525): every extent behind the
+    first 0 is 0 -- (0, 1) -> (0, 0), (2, 0) -> (2, 0), (3, 3, 0) -> (3, 3, 0), (0, 3, 3) -> (0, 0, 0)."""
+    out, dead = [], False
+    for s in shape:
+        out.append(0 if dead else s)
+        dead = dead or s == 0
+    return tuple(out)
+
+
+class Transform:
+    """include/gridpp.h:2345-2388: forward / backward of a scalar (host arithmetic, a Python float back) or of a 1-, 2- or 3-D array or
+    torch CUDA tensor (one kernel, the same shape back as float32).  The base class's scalar forms return -1 (transform.cpp:7-12)."""
+    _kind = None
+
+    def _params(self):
+        return 0.0, 0.0
+
+    def forward(self, input):
+        return self._apply(input, 0)
+
+    def backward(self, input):
+        return self._apply(input, 1)
+
+    def _apply(self, value, backward):
+        nd = _ndim(value)
+        p0, p1 = self._params()
+        if nd == 0:
+            if self._kind is None:
+                return -1.0
+            out = C.c_float(np.nan)
+            check(lib().gpp_transform_scalar(float(value), self._kind, backward, p0, p1, C.byref(out)))
+            return out.value
+        if nd > 3:
+            raise RuntimeError("input must be a scalar or have 1, 2 or 3 dimensions, got %d" % nd)
+        dev = _is_dev(value)
+        v = _vec(value, nd, "input") if dev else _vec(value, nd, "input", np.float64 if _wants_f64(value) else np.float32)
+        shp = _shape(v)
+        n = int(np.prod(shp))
+        if n == 0:
+            return _empty_like_field(_typemap_shape(shp), v) if dev else np.zeros(_typemap_shape(shp), np.float32)
+        out = _empty_like_field(shp, v)
+        if self._kind is None:   # the vector forms call the virtual scalar one: -1 everywhere
+            out[...] = -1
+            return out
+        mem = _mem(v)
+        _sync_if_dev(mem)
+        if not dev and v.dtype == np.float64:
+            mem |= _capi.HOST_F64
+        check(lib().gpp_transform(_ptr(v), n, self._kind, backward, p0, p1, _ptr(out), mem))
+        return out
+
+
+class Identity(Transform):
+    """transform.cpp:180-185"""
+    _kind = _capi.TRANSFORM_IDENTITY
+
+
+class Log(Transform):
+    """transform.cpp:85-96: log / exp of a valid value (forward(0) = -inf, a negative input gives NaN)"""
+    _kind = _capi.TRANSFORM_LOG
+
+
+class BoxCox(Transform):
+    """transform.cpp:97-125: (value^threshold - 1) / threshold, log for threshold 0; inputs <= 0 count as 0.  The threshold is not
+    validated."""
+    _kind = _capi.TRANSFORM_BOXCOX
+
+    def __init__(self, threshold):
+        self._threshold = float(np.float32(threshold))
+
+    def _params(self):
+        return self._threshold, 0.0
+
+
+class StartedBoxCox(Transform):
+    """transform.cpp:126-154: no transformation between 0 and scaling_factor, a Box-Cox-like one with parameter threshold above."""
+    _kind = _capi.TRANSFORM_STARTED_BOXCOX
+
+    def __init__(self, threshold, scaling_factor):
+        if not is_valid(threshold) or np.float32(threshold) <= 0:
+            raise ValueError("threshold parameter must be > 0 in the started Box-Cox distribution")
+        if not is_valid(scaling_factor) or np.float32(scaling_factor) <= 0:
+            raise ValueError("Scaling factor parameter must be > 0 in the started Box-Cox distribution")
+        self._threshold, self._scaling = float(np.float32(threshold)), float(np.float32(scaling_factor))
+
+    def _params(self):
+        return self._threshold, self._scaling
+
+
 # ---- verification scores (include/gridpp.h:103-110; src/api/metric_optimizer.cpp:185-244, neighbourhood_score.cpp) ----
 Ets, Ts, Kss, Pc, Bias, Hss = 0, 1, 20, 30, 40, 50
 _METRICS = (Ets, Ts, Kss, Pc, Bias, Hss)

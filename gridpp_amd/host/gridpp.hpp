@@ -18,6 +18,9 @@
 //   fill, fill_missing, doping_square/circle, neighbourhood_search, calc_gradient
 //   calc_statistic / calc_quantile             :1454-1482
 //   Metric, calc_score (three overloads), neighbourhood_score  :103-110
+//   MV_CML, pi and the constants of the standard atmosphere    :51-67
+//   dewpoint, relative_humidity, wetbulb, pressure, sea_level_pressure, qnh, wind_speed, wind_direction (scalar and vector)  :1249-1367
+//   Transform, Identity, Log, BoxCox, StartedBoxCox            :2345-2435
 // Nested vectors are flattened once, handed to the C-ABI as host buffers (GPP_MEM_HOST) and un-flattened,
 // exactly where the reference flattens them itself (src/api/oi.cpp:69-86).  Errors: GPP_EINVAL ->
 // std::invalid_argument, everything else -> std::runtime_error (swig/gridpp.i:21-40 maps these to python).
@@ -26,6 +29,7 @@
 #include <cmath>
 #include <memory>
 #include <stdexcept>
+#include <initializer_list>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -39,6 +43,15 @@ typedef std::vector<int> ivec;
 typedef std::vector<ivec> ivec2;
 static const float MV = NAN;
 static const double radius_earth = 6.378137e6;
+// include/gridpp.h:51-67
+static const float MV_CML = -999;
+static const float pi = 3.14159265;
+static const float lapse_rate = 0.0065;
+static const float standard_surface_temperature = 288.15;
+static const float gravit = 9.80665;
+static const float molar_mass = 0.0289644;
+static const float gas_constant_mol = 8.31447;
+static const float gas_constant_si = 287.05;
 
 enum Statistic { Mean = 0, Min = 10, Median = 20, Max = 30, Quantile = 40, Std = 50, Variance = 60, Sum = 70, Count = 80, RandomChoice = 90, Unknown = -1 };
 enum CoordinateType { Geodetic = 0, Cartesian = 1 };
@@ -1061,6 +1074,168 @@ inline vec2 neighbourhood_score(const Grid& grid, const Points& points, const ve
     detail::check(gpp_neighbourhood_score(grid.handle(), points.handle(), f.data(), ref.data(), half_width, (int)metric, threshold, out.data(), GPP_MEM_HOST));
     return detail::unflatten(out, Y, X);
 }
+
+// ---- weather diagnostics (include/gridpp.h:1249-1367) -----------------------------------------------------------------------------
+// The scalar overloads are host arithmetic (the per-value source of the kernels); the vector overloads run one kernel over host buffers.
+// std::invalid_argument with the reference's texts for vectors of different sizes; sea_level_pressure throws std::runtime_error as
+// pressure.cpp:32-38 does (the vector overload for the lowest offending index).
+namespace detail {
+inline float diagnostic(int which, std::initializer_list<float> args) {
+    float out = MV;
+    check(gpp_diagnostic_scalar(which, args.begin(), (int)args.size(), &out));
+    return out;
+}
+}   // namespace detail
+inline float dewpoint(float temperature, float relative_humidity) { return detail::diagnostic(GPP_DIAG_DEWPOINT, {temperature, relative_humidity}); }
+inline vec dewpoint(const vec& temperature, const vec& relative_humidity) {
+    if(temperature.size() != relative_humidity.size()) throw std::invalid_argument("Temperature and relative_humidity vectors are not the same size");
+    vec out(temperature.size(), MV);
+    detail::check(gpp_dewpoint(temperature.data(), relative_humidity.data(), (long long)out.size(), out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline float relative_humidity(float temperature, float dewpoint) { return detail::diagnostic(GPP_DIAG_RELATIVE_HUMIDITY, {temperature, dewpoint}); }
+inline vec relative_humidity(const vec& temperature, const vec& dewpoint) {
+    if(temperature.size() != dewpoint.size()) throw std::invalid_argument("Temperature and dewpoint vectors are not the same size");
+    vec out(temperature.size(), MV);
+    detail::check(gpp_relative_humidity(temperature.data(), dewpoint.data(), (long long)out.size(), out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline float wetbulb(float temperature, float pressure, float relative_humidity) {
+    return detail::diagnostic(GPP_DIAG_WETBULB, {temperature, pressure, relative_humidity});
+}
+inline vec wetbulb(const vec& temperature, const vec& pressure, const vec& relative_humidity) {
+    if(temperature.size() != pressure.size()) throw std::invalid_argument("Temperature and pressure vectors are not the same size");
+    if(temperature.size() != relative_humidity.size()) throw std::invalid_argument("Temperature and relative_humidity vectors are not the same size");
+    vec out(temperature.size(), MV);
+    detail::check(gpp_wetbulb(temperature.data(), pressure.data(), relative_humidity.data(), (long long)out.size(), out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline float pressure(float ielev, float oelev, float ipressure, float itemperature = 288.15) {
+    return detail::diagnostic(GPP_DIAG_PRESSURE, {ielev, oelev, ipressure, itemperature});
+}
+inline vec pressure(const vec& ielev, const vec& oelev, const vec& ipressure, const vec& itemperature) {
+    const size_t N = ielev.size();
+    if(oelev.size() != N || ipressure.size() != N || itemperature.size() != N) throw std::invalid_argument("pressure: Input arguments must be of the same size");
+    vec out(N, MV);
+    detail::check(gpp_pressure(ielev.data(), oelev.data(), ipressure.data(), itemperature.data(), (long long)N, out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline float sea_level_pressure(float ps, float altitude, float temperature, float rh = MV, float dewpoint = MV) {
+    return detail::diagnostic(GPP_DIAG_SEA_LEVEL_PRESSURE, {ps, altitude, temperature, rh, dewpoint});
+}
+inline vec sea_level_pressure(const vec& ps, const vec& altitude, const vec& temperature, const vec& rh, const vec& dewpoint) {
+    const size_t N = ps.size();
+    if(altitude.size() != N || temperature.size() != N || rh.size() != N || dewpoint.size() != N)
+        throw std::invalid_argument("slp: Input arguments must be of the same size");
+    vec out(N, MV);
+    detail::check(gpp_sea_level_pressure(ps.data(), altitude.data(), temperature.data(), rh.data(), dewpoint.data(), (long long)N, out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline float qnh(float pressure, float altitude) { return detail::diagnostic(GPP_DIAG_QNH, {pressure, altitude}); }
+inline vec qnh(const vec& pressure, const vec& altitude) {
+    if(pressure.size() != altitude.size()) throw std::invalid_argument("Pressure and altitude vectors are not the same size");
+    vec out(pressure.size(), MV);
+    detail::check(gpp_qnh(pressure.data(), altitude.data(), (long long)out.size(), out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline float wind_speed(float xwind, float ywind) { return detail::diagnostic(GPP_DIAG_WIND_SPEED, {xwind, ywind}); }
+inline vec wind_speed(const vec& xwind, const vec& ywind) {
+    if(xwind.size() != ywind.size()) throw std::invalid_argument("xwind and ywind must be of the same size");
+    vec out(xwind.size(), MV);
+    detail::check(gpp_wind_speed(xwind.data(), ywind.data(), (long long)out.size(), out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline float wind_direction(float xwind, float ywind) { return detail::diagnostic(GPP_DIAG_WIND_DIRECTION, {xwind, ywind}); }
+inline vec wind_direction(const vec& xwind, const vec& ywind) {
+    if(xwind.size() != ywind.size()) throw std::invalid_argument("xwind and ywind must be of the same size");
+    vec out(xwind.size(), MV);
+    detail::check(gpp_wind_direction(xwind.data(), ywind.data(), (long long)out.size(), out.data(), GPP_MEM_HOST));
+    return out;
+}
+
+// ---- value transforms (include/gridpp.h:2345-2435, src/api/transform.cpp) -----------------------------------------------------------
+// The scalar forms are host arithmetic; the vec / vec2 / vec3 forms flatten their input (rows may differ in length, as in the
+// reference's loops), run one kernel and restore the nesting.  The base class's scalar forms return -1 (transform.cpp:7-12), and so
+// do its vector forms element by element.
+class Transform {
+    public:
+        Transform() : m_kind(-1), m_p0(0), m_p1(0) {}
+        virtual ~Transform() {}
+        virtual float forward(float value) const { return scalar(value, 0); }
+        virtual float backward(float value) const { return scalar(value, 1); }
+        vec forward(const vec& input) const { return apply(input, 0); }
+        vec backward(const vec& input) const { return apply(input, 1); }
+        vec2 forward(const vec2& input) const { return apply(input, 0); }
+        vec2 backward(const vec2& input) const { return apply(input, 1); }
+        vec3 forward(const vec3& input) const { return apply(input, 0); }
+        vec3 backward(const vec3& input) const { return apply(input, 1); }
+    protected:
+        Transform(int kind, float p0, float p1 = 0) : m_kind(kind), m_p0(p0), m_p1(p1) {}
+    private:
+        int m_kind;   // GPP_TRANSFORM_*, -1: the base class
+        float m_p0, m_p1;
+        float scalar(float value, int backward) const {
+            if(m_kind < 0) return -1;
+            float out = MV;
+            detail::check(gpp_transform_scalar(value, m_kind, backward, m_p0, m_p1, &out));
+            return out;
+        }
+        vec apply(const vec& input, int backward) const {
+            vec out(input.size(), MV);
+            if(m_kind < 0) std::fill(out.begin(), out.end(), -1.0f);
+            else detail::check(gpp_transform(input.data(), (long long)input.size(), m_kind, backward, m_p0, m_p1, out.data(), GPP_MEM_HOST));
+            return out;
+        }
+        vec2 apply(const vec2& input, int backward) const {
+            vec flat;
+            for(const auto& r : input) flat.insert(flat.end(), r.begin(), r.end());
+            const vec out = apply(flat, backward);
+            vec2 o(input.size());
+            size_t at = 0;
+            for(size_t y = 0; y < input.size(); y++) { o[y].assign(out.begin() + at, out.begin() + at + input[y].size()); at += input[y].size(); }
+            return o;
+        }
+        vec3 apply(const vec3& input, int backward) const {
+            vec flat;
+            for(const auto& r : input) for(const auto& c : r) flat.insert(flat.end(), c.begin(), c.end());
+            const vec out = apply(flat, backward);
+            vec3 o(input.size());
+            size_t at = 0;
+            for(size_t y = 0; y < input.size(); y++) {
+                o[y].resize(input[y].size());
+                for(size_t x = 0; x < input[y].size(); x++) { o[y][x].assign(out.begin() + at, out.begin() + at + input[y][x].size()); at += input[y][x].size(); }
+            }
+            return o;
+        }
+};
+class Identity : public Transform {
+    public:
+        Identity() : Transform(GPP_TRANSFORM_IDENTITY, 0) {}
+        using Transform::forward;
+        using Transform::backward;
+};
+class Log : public Transform {
+    public:
+        Log() : Transform(GPP_TRANSFORM_LOG, 0) {}
+        using Transform::forward;
+        using Transform::backward;
+};
+class BoxCox : public Transform {
+    public:
+        BoxCox(float threshold) : Transform(GPP_TRANSFORM_BOXCOX, threshold) {}   // transform.cpp:97-99: no validation
+        using Transform::forward;
+        using Transform::backward;
+};
+class StartedBoxCox : public Transform {
+    public:
+        StartedBoxCox(float threshold, float scaling_factor) : Transform(GPP_TRANSFORM_STARTED_BOXCOX, threshold, scaling_factor) {   // transform.cpp:126-132
+            if(!is_valid(threshold) || threshold <= 0) throw std::invalid_argument("threshold parameter must be > 0 in the started Box-Cox distribution");
+            if(!is_valid(scaling_factor) || scaling_factor <= 0)
+                throw std::invalid_argument("Scaling factor parameter must be > 0 in the started Box-Cox distribution");
+        }
+        using Transform::forward;
+        using Transform::backward;
+};
 
 // ---- util (include/gridpp.h:1454-1482) -----------------------------------------------------------------------------
 inline float calc_statistic(const vec& array, Statistic statistic) {

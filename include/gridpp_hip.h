@@ -53,7 +53,9 @@ extern "C" {
  * gpp_full_gradient, gpp_downscale_probability, gpp_mask_threshold_downscale (the cubes and the threshold) and gpp_smart
  * (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
  * (their float fields), by gpp_neighbourhood_quantile_fast for `input` only, by gpp_apply_curve and gpp_interpolate for the values
- * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs, by gpp_window for `array` and by gpp_neighbourhood_score for `fcst`. */
+ * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs, by gpp_window for `array`, by gpp_neighbourhood_score for `fcst`,
+ * by gpp_dewpoint, gpp_relative_humidity, gpp_wetbulb, gpp_pressure, gpp_sea_level_pressure, gpp_qnh, gpp_wind_speed and
+ * gpp_wind_direction for all their inputs and by gpp_transform for `in`. */
 #define GPP_HOST_F64 4
 
 /* include/gridpp.h:120-123 */
@@ -490,6 +492,61 @@ int gpp_calc_score(const float* ref, const float* fcst, long long n, float thres
 #define GPP_SCORE_FUSED_MAXHW 16    /* the ring of the fused kernel holds 32 + 2 * 16 rows; (2 * 16 + 1)^2 = 1089 < 65536 */
 int gpp_neighbourhood_score(gpp_points* grid, gpp_points* points, const float* fcst, const float* ref, int half_width, int metric,
                             float threshold, float* out, int mem);
+
+/* ---- weather diagnostics and value transforms (include/gridpp.h:1249-1367,2345-2435) ----------------------------------------------
+ * Element-wise over n values: every input array and `out` hold n floats and follow `mem` (GPP_MEM_HOST or GPP_MEM_DEVICE;
+ * GPP_HOST_F64 honoured for ALL inputs of a call: they are then `const double*` and are rounded to float32 on the device as the first
+ * operation).  The per-value arithmetic is gridpp_amd/csrc/pointwise.h (the reference's float / double promotions operation by
+ * operation, transcendentals evaluated in double), shared with the host-only scalar forms below.  n == 0 returns GPP_OK and writes
+ * nothing; n < 0 and a NULL array are GPP_EINVAL.  The sizes of the arrays are the caller's to compare (the reference's
+ * std::invalid_argument texts are raised by the mirrors).  One streaming kernel: GPP_POINTWISE_BLOCK lanes per workgroup, at most
+ * GPP_POINTWISE_MAX_BLOCKS workgroups walking the values with a grid stride, four values per lane and step through 16-byte loads
+ * and stores where every pointer is 16-byte aligned (one value per lane otherwise, and for the n mod 4 tail). */
+#define GPP_POINTWISE_BLOCK 256
+#define GPP_POINTWISE_MAX_BLOCKS 2048
+/* gridpp::dewpoint (src/api/humidity.cpp:5-32) */
+int gpp_dewpoint(const float* temperature, const float* relative_humidity, long long n, float* out, int mem);
+/* gridpp::relative_humidity (src/api/humidity.cpp:33-90) */
+int gpp_relative_humidity(const float* temperature, const float* dewpoint, long long n, float* out, int mem);
+/* gridpp::wetbulb (src/api/humidity.cpp:91-122) */
+int gpp_wetbulb(const float* temperature, const float* pressure, const float* relative_humidity, long long n, float* out, int mem);
+/* gridpp::pressure (src/api/pressure.cpp:5-26) */
+int gpp_pressure(const float* ielev, const float* oelev, const float* ipressure, const float* itemperature, long long n, float* out, int mem);
+/* gridpp::sea_level_pressure (src/api/pressure.cpp:28-93).  Where the reference throws for an element ("sea_level_pressure: altitude
+ * is NAN", "sea_level_pressure: temperature is NAN", "sea_level_pressure: unphysical values in input", tested in that order) the call
+ * returns GPP_ERUNTIME with the message of the LOWEST offending index (the reference throws inside an OpenMP loop); `out` is then
+ * written all the same, with NaN at the offending elements. */
+int gpp_sea_level_pressure(const float* ps, const float* altitude, const float* temperature, const float* rh, const float* dewpoint,
+                           long long n, float* out, int mem);
+/* gridpp::qnh (src/api/qnh.cpp:6-41) */
+int gpp_qnh(const float* pressure, const float* altitude, long long n, float* out, int mem);
+/* gridpp::wind_speed / wind_direction (src/api/wind.cpp:6-37) */
+int gpp_wind_speed(const float* xwind, const float* ywind, long long n, float* out, int mem);
+int gpp_wind_direction(const float* xwind, const float* ywind, long long n, float* out, int mem);
+/* gridpp::Identity / Log / BoxCox / StartedBoxCox ::forward and ::backward over n values (src/api/transform.cpp:13-84 over :85-154,
+ * 180-185).  p0 = threshold (BoxCox, StartedBoxCox), p1 = scaling_factor (StartedBoxCox); ignored otherwise.  GPP_EINVAL for a kind
+ * that is none of the four, and for StartedBoxCox with the texts of its constructor (transform.cpp:128-131): "threshold parameter
+ * must be > 0 in the started Box-Cox distribution", "Scaling factor parameter must be > 0 in the started Box-Cox distribution". */
+#define GPP_TRANSFORM_IDENTITY 0
+#define GPP_TRANSFORM_LOG 1
+#define GPP_TRANSFORM_BOXCOX 2
+#define GPP_TRANSFORM_STARTED_BOXCOX 3
+int gpp_transform(const float* in, long long n, int kind, int backward, float p0, float p1, float* out, int mem);
+/* Host-only forms (no GPU needed); they run the per-value source of the kernels.
+ * The scalar overloads of the eight diagnostics (humidity.cpp:5-21,33-79,91-109, pressure.cpp:5-13,28-80, qnh.cpp:6-30, wind.cpp:6-8,
+ * 20-26): args holds the nargs arguments in the reference's order; GPP_EINVAL for an unknown `which` or a wrong nargs;
+ * GPP_DIAG_SEA_LEVEL_PRESSURE returns GPP_ERUNTIME with the three messages above. */
+#define GPP_DIAG_DEWPOINT 0
+#define GPP_DIAG_RELATIVE_HUMIDITY 1
+#define GPP_DIAG_WETBULB 2
+#define GPP_DIAG_PRESSURE 3
+#define GPP_DIAG_SEA_LEVEL_PRESSURE 4
+#define GPP_DIAG_QNH 5
+#define GPP_DIAG_WIND_SPEED 6
+#define GPP_DIAG_WIND_DIRECTION 7
+int gpp_diagnostic_scalar(int which, const float* args, int nargs, float* out);
+/* Transform::forward(float) / backward(float) of the four kinds (transform.cpp:85-154,180-185); errors as gpp_transform. */
+int gpp_transform_scalar(float value, int kind, int backward, float p0, float p1, float* out);
 
 /* per-call statistics of the last OI call on this thread (diagnostics / bench) */
 typedef struct gpp_oi_stats {
