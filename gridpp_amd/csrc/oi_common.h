@@ -158,6 +158,11 @@ __device__ __forceinline__ double d_fma_sc(double a, double c, double b) {   // 
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(a), "s"(c), "v"(b));
     return o;
 }
+__device__ __forceinline__ unsigned d_and_or_sc(unsigned m, unsigned c, unsigned b) {   // (m & c) | b
+    unsigned o;
+    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(o) : "v"(m), "s"(c), "v"(b));
+    return o;
+}
 __device__ __forceinline__ double d_fma_step_sc(double p, double r, double c) {   // p * r + c
     double o;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(p), "v"(r), "s"(c));

@@ -299,6 +299,16 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
 #pragma unroll
     for(int w = 0; w < U_WCAP; ++w) L.rho[w][lane] = INFINITY;
     auto live_mask = [&]() { return wave_or64(mine); };   // slots some cell still holds
+    // bulk disc: this cell takes slot s (wave-uniform) if ok.  Round 9: the lane's condition as an all-ones / zero word: each half of the
+    // mask is then ONE and-or with the scalar half of 1 << s, and the count a subtraction -- a select cannot read a scalar operand beside
+    // its scalar condition, so the plain form moves both halves of the bit into vector registers first: seven vector instructions per
+    // candidate where this has four.
+    auto bulk_own = [&](const bool ok, const int s) {
+        const unsigned okm = ok ? ~0u : 0u;
+        const unsigned long long bit = 1ull << s;
+        mine = ((unsigned long long)d_and_or_sc(okm, (unsigned)(bit >> 32), (unsigned)(mine >> 32)) << 32) | d_and_or_sc(okm, (unsigned)bit, (unsigned)mine);
+        cnt -= (int)okm;
+    };
     // The worst kept entry of this lane: smallest rho r0, a slot s0 that holds it, and whether more than one slot does.  Two levels --
     // minima of groups of eight slots, then the eight values of the group that holds the minimum, read again from LDS (its index is
     // the lane's own): ~70 instructions.  One flat pass (compare, select, count for each of the 40 slots, each triple with a wait
@@ -678,8 +688,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                                         if(q < n) {
                                             const bool ok = rho[q] > 0.0f;   // oi.cpp:253
                                             L.rho[nb][lane] = ok ? rho[q] : INFINITY;
-                                            mine |= ok ? (1ull << nb) : 0ull;
-                                            cnt += ok ? 1 : 0;
+                                            bulk_own(ok, nb);
                                             nb++;
                                         }
                                     }
@@ -691,8 +700,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                                 const float rho = eval(rec, met, c);
                                 const bool ok = rho > 0.0f;   // oi.cpp:253
                                 L.rho[nb][lane] = ok ? rho : INFINITY;
-                                mine |= ok ? (1ull << nb) : 0ull;
-                                cnt += ok ? 1 : 0;
+                                bulk_own(ok, nb);
                                 nb++;
                             }
                         }
@@ -1306,8 +1314,22 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 // column j of the factor goes through LDS: one write, then broadcast reads (two values per ds_read) feed
                 // the rank-1 update -- half the instructions of a v_readlane pair per multiply-add
                 colL[lane] = cj;
+                // (round 9: an odd first column alone, then 16-byte aligned pairs -- a ds_read_b128 reaches colL with its immediate offset;
+                //  left to itself every second column pairs from its odd first entry, 8-byte aligned: ds_read2_b64, whose offsets end at
+                //  2 040 bytes, i.e. an address addition per pair)
+                {
+                    static_assert(NC % 2 == 0 && (U_SOLVE - 64) % 2 == 0, "colL and its pairs are 16-byte aligned");
+                    const int pe = (j + 2) & ~1;   // the first even column behind j
+                    if(pe != j + 1) row[j + 1] = __builtin_fma(-cj, colL[j + 1], row[j + 1]);
+                    typedef double d2v __attribute__((ext_vector_type(2)));   // (HIP's double2 is a struct: read as two doubles, paired again from the odd entry)
+                    const d2v* const colL2 = reinterpret_cast<const d2v*>(colL);
 #pragma unroll
-                for(int p = j + 1; p < NC; ++p) row[p] = __builtin_fma(-cj, colL[p], row[p]);
+                    for(int p = pe; p < NC; p += 2) {
+                        const d2v v = colL2[p >> 1];
+                        row[p] = __builtin_fma(-cj, v.x, row[p]);
+                        row[p + 1] = __builtin_fma(-cj, v.y, row[p + 1]);
+                    }
+                }
             }
         }
         UPROF(8);   // row load + elimination
@@ -1343,8 +1365,24 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                     const bool mine = (lane >= p && lane < u) || lane == 63;
                     double acc = mine ? L.late[b][lidx] : 0.0;
                     const double* const bp = sv + oB + (p - c) * bs;
+                    // (round 9: four columns behind one test while whole groups lie below c, the reads of a group issued together; the
+                    //  group that holds column c - 1 one by one -- the registers behind it hold the Schur complement, not zeros, so nothing
+                    //  may be read past the row here as the per-cell finish does)
 #pragma unroll
-                    for(int k = 0; k < NC; ++k) if(k < ce) acc = __builtin_fma(-row[k], bp[k], acc);
+                    for(int k = 0; k < NC; k += 4) {
+                        if(k + 3 < ce) {
+                            const double b0 = bp[k], b1 = bp[k + 1], b2 = bp[k + 2], b3 = bp[k + 3];
+                            acc = __builtin_fma(-row[k], b0, acc);
+                            acc = __builtin_fma(-row[k + 1], b1, acc);
+                            acc = __builtin_fma(-row[k + 2], b2, acc);
+                            acc = __builtin_fma(-row[k + 3], b3, acc);
+                        }
+                        else if(k < ce) {
+                            acc = __builtin_fma(-row[k], bp[k], acc);
+                            if(k + 1 < ce) acc = __builtin_fma(-row[k + 1], bp[k + 1], acc);
+                            if(k + 2 < ce) acc = __builtin_fma(-row[k + 2], bp[k + 2], acc);
+                        }
+                    }
                     if(lane >= p && lane < u) sv[oS + ea * nE + (p - c)] = acc;
                     else if(lane == 63) sv[oD + (p - c)] = acc;
                 }
