@@ -1318,6 +1318,57 @@ def smart(igrid, ogrid, ivalues, num, structure):
     return out
 
 
+# ---- local_distribution_correction (include/gridpp.h:467-512) ---------------------------------------------------------------
+def local_distribution_correction(bgrid, background, points, pobs, pbackground, structure, min_quantile, max_quantile, min_points=0):
+    """src/api/local_distribution_correction.cpp:18-203: per grid cell, the valid non-negative (pobs, pbackground) pairs of the
+    stations within the structure's localization distance, weighted by rho = corr_background(cell, station), form two
+    cumulative-rho curves between min_quantile and max_quantile; the cell's background is mapped from the one to the other.
+    pobs and pbackground are both 1-D (S) or both 2-D (T, S).  Cells with an invalid background or fewer than min_points pairs
+    keep their background.
+
+    Both curves are sorted by value and, where values tie, by rho ascending.  The reference sorts by value alone with an
+    unstable sort: on tied values (zeros of precipitation) its result depends on the order its R-tree returns the stations in;
+    on tie-free data the two agree.  Shapes the reference would read out of bounds with are refused."""
+    if not isinstance(bgrid, Grid) or not isinstance(points, Points):
+        raise TypeError("local_distribution_correction: bgrid must be a Grid, points a Points")
+    st = _structure(structure)
+    fields = (background, pobs, pbackground)
+    dev = all(_is_dev(a) for a in fields)
+    f64 = not dev and all(isinstance(a, np.ndarray) and a.dtype == np.float64 for a in fields)
+    dt = np.float64 if f64 else np.float32
+    nd = _ndim(pobs)
+    if nd not in (1, 2) or _ndim(pbackground) != nd:
+        raise ValueError("pobs and pbackground must both be 1-D (points) or both 2-D (times, points)")
+    background = _vec(background, 2, "background", dt)
+    pobs, pbackground = _vec(pobs, nd, "pobs", dt), _vec(pbackground, nd, "pbackground", dt)
+    mem = _mem(background, pobs, pbackground)
+    if nd == 1:
+        pobs, pbackground = pobs.reshape(1, -1), pbackground.reshape(1, -1)   # :27-31
+    so, sb = _shape(pobs), _shape(pbackground)
+    if so[0] != sb[0]:   # :50-54
+        raise ValueError("pobs (%d,%d) is not the same size as pbackground (%d,%d)" % (so + sb))
+    if so != sb:
+        raise ValueError("pobs (%d,%d) is not the same shape as pbackground (%d,%d)" % (so + sb))
+    if _shape(background) != tuple(bgrid.size()):
+        raise ValueError("input field %s is not the same size as the grid %s" % (_shape(background), tuple(bgrid.size())))
+    if so[1] != points.size():
+        raise ValueError("pobs (%d) and points (%d) size mismatch" % (so[1], points.size()))
+    if bgrid.get_coordinate_type() != points.get_coordinate_type():
+        raise ValueError("Both background grid and observations points must be of same coordinate type (lat/lon or x/y)")
+    min_quantile, max_quantile = float(min_quantile), float(max_quantile)
+    if not (np.isfinite(min_quantile) and np.isfinite(max_quantile) and 0 <= min_quantile <= max_quantile <= 1):
+        raise ValueError("min_quantile and max_quantile must be finite with 0 <= min_quantile <= max_quantile <= 1")
+    out = _empty_like_field(tuple(bgrid.size()), background)
+    if bgrid._n == 0:
+        return out
+    _sync_if_dev(mem)
+    if f64 and mem == _capi.MEM_HOST:
+        mem |= _capi.HOST_F64
+    check(lib().gpp_local_distribution_correction(bgrid._h, _ptr(background), points._h, _ptr(pobs), _ptr(pbackground), so[0], st,
+                                                  min_quantile, max_quantile, int(min_points), _ptr(out), mem))
+    return out
+
+
 # ---- calibration by a curve (include/gridpp.h:79-85,731-789,1549-1557) -----------------------------------------------------
 OneToOne, MeanSlope, NearestSlope, Zero, Unchanged = 0, 10, 20, 30, 40   # include/gridpp.h:79-85
 _POLICIES = (OneToOne, MeanSlope, NearestSlope, Zero, Unchanged)

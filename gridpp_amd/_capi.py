@@ -80,6 +80,7 @@ SIGNATURES = {
     "gpp_downscale_probability": [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int],
     "gpp_mask_threshold_downscale": [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int],
     "gpp_smart": [vp, vp, vp, C.c_int, C.POINTER(gpp_structure), vp, C.c_int],
+    "gpp_local_distribution_correction": [vp, vp, vp, vp, vp, C.c_int, C.POINTER(gpp_structure), C.c_float, C.c_float, C.c_int, vp, C.c_int],
     "gpp_apply_curve": [vp, C.c_longlong, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int],
     "gpp_apply_curve_field": [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
     "gpp_interpolate": [vp, C.c_longlong, vp, C.c_int, vp, C.c_int, vp, C.c_int],

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <sstream>
 #include <stdexcept>
 #include <initializer_list>
 #include <iostream>
@@ -955,6 +956,46 @@ inline vec2 smart(const Grid& igrid, const Grid& ogrid, const vec2& ivalues, int
     vec out(oy * ox, MV);
     detail::check(gpp_smart(igrid.handle(), ogrid.handle(), v.data(), num, structure.c_struct(), out.data(), GPP_MEM_HOST));
     return detail::unflatten(out, oy, ox);
+}
+
+// ---- local_distribution_correction (include/gridpp.h:467-512) ----------------------------------------------------------------
+// src/api/local_distribution_correction.cpp:33-203.  Ties in value are ordered by rho ascending (the reference leaves them to an
+// unstable sort); shapes the reference would read out of bounds with are refused.
+inline vec2 local_distribution_correction(const Grid& bgrid, const vec2& background, const Points& points, const vec2& pobs, const vec2& pbackground,
+                                          const StructureFunction& structure, float min_quantile, float max_quantile, int min_points = 0) {
+    size_t Y, X, T, S, T2, S2;
+    vec b = detail::flatten(background, Y, X), po = detail::flatten(pobs, T, S), pb = detail::flatten(pbackground, T2, S2);
+    if(pobs.size() != pbackground.size()) {   // :50-54
+        std::stringstream ss;
+        ss << "pobs (" << pobs.size() << "," << S << ") is not the same size as pbackground (" << pbackground.size() << "," << S2 << ")";
+        throw std::invalid_argument(ss.str());
+    }
+    if(S != S2 || po.size() != pb.size()) {
+        std::stringstream ss;
+        ss << "pobs (" << pobs.size() << "," << S << ") is not the same shape as pbackground (" << pbackground.size() << "," << S2 << ")";
+        throw std::invalid_argument(ss.str());
+    }
+    if(!((detail::cells(bgrid) == 0 && b.empty()) || detail::fits(bgrid, Y, X))) throw std::invalid_argument(detail::GRID_MISMATCH);
+    if(!pobs.empty() && S != (size_t)points.size()) {
+        std::stringstream ss;
+        ss << "pobs (" << S << ") and points (" << points.size() << ") size mismatch";
+        throw std::invalid_argument(ss.str());
+    }
+    if(bgrid.get_coordinate_type() != points.get_coordinate_type())
+        throw std::invalid_argument("Both background grid and observations points must be of same coordinate type (lat/lon or x/y)");
+    if(!(std::isfinite(min_quantile) && std::isfinite(max_quantile) && 0 <= min_quantile && min_quantile <= max_quantile && max_quantile <= 1))
+        throw std::invalid_argument("min_quantile and max_quantile must be finite with 0 <= min_quantile <= max_quantile <= 1");
+    size_t oy = bgrid.size()[0], ox = bgrid.size()[1];
+    vec out(oy * ox, MV);
+    detail::check(gpp_local_distribution_correction(bgrid.handle(), b.data(), points.handle(), po.data(), pb.data(), (int)pobs.size(),
+                                                    structure.c_struct(), min_quantile, max_quantile, min_points, out.data(), GPP_MEM_HOST));
+    return detail::unflatten(out, oy, ox);
+}
+// :18-32
+inline vec2 local_distribution_correction(const Grid& bgrid, const vec2& background, const Points& points, const vec& pobs, const vec& pbackground,
+                                          const StructureFunction& structure, float min_quantile, float max_quantile, int min_points = 0) {
+    return local_distribution_correction(bgrid, background, points, vec2(1, pobs), vec2(1, pbackground), structure, min_quantile, max_quantile,
+                                         min_points);
 }
 
 // ---- calibration by a curve (include/gridpp.h:79-85,731-789,1549-1557) ---------------------------------------------------

@@ -50,7 +50,7 @@ extern "C" {
  * they are and cast to float32 on the device -- the rounding the reference's typemap applies on the host
  * (swig/vector.i:42-55).  Outputs stay float32.  Honoured by gpp_optimal_interpolation_full,
  * gpp_optimal_interpolation_ensi, gpp_neighbourhood, gpp_nearest(_levels), gpp_bilinear, gpp_simple_gradient,
- * gpp_full_gradient, gpp_downscale_probability, gpp_mask_threshold_downscale (the cubes and the threshold) and gpp_smart
+ * gpp_full_gradient, gpp_downscale_probability, gpp_mask_threshold_downscale (the cubes and the threshold), gpp_smart and gpp_local_distribution_correction
  * (every `const float*` argument of these that follows `mem` is then a `const double*`), by gpp_fill_missing, gpp_neighbourhood_search and gpp_calc_gradient
  * (their float fields), by gpp_neighbourhood_quantile_fast for `input` only, by gpp_apply_curve and gpp_interpolate for the values
  * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs, by gpp_window for `array`, by gpp_neighbourhood_score for `fcst`,
@@ -343,6 +343,19 @@ int gpp_staticcorr_points(gpp_points* points, gpp_points* knots, const gpp_struc
  * (rho descending, ties -> lower index of the input grid; cells with rho = 0 take part).  No validity test on the values;
  * NaN where n = 0 or num <= 0.  Scalar structure functions.  values / out follow `mem` (GPP_HOST_F64 honoured). */
 int gpp_smart(gpp_points* igrid, gpp_points* ogrid, const float* values, int num, const gpp_structure* structure, float* out, int mem);
+
+/* gridpp::local_distribution_correction (src/api/local_distribution_correction.cpp:18-203; the vec form :18-32 is nT = 1):
+ * out [ny][nx] of grid = `background` mapped through the two cumulative-rho curves of the valid, non-negative
+ * (pobs, pbackground) pairs ([nT][size of points] each) of the stations within the structure's localization distance, rho =
+ * corr_background(cell, station); stations with rho = 0 take part.  Both curves are sorted by value and, where values tie,
+ * by rho ascending -- the reference leaves the order of tied values to an unstable sort and to its R-tree;
+ * on tie-free data this is the reference's result.  A cell with an invalid background or fewer than min_points pairs keeps
+ * its background; an empty point set returns the background.  EINVAL: different coordinate types, nT < 0, quantiles not
+ * finite or not 0 <= min_quantile <= max_quantile <= 1.  Scalar structure functions.  `out` must not overlap an input.
+ * background / pobs / pbackground / out follow `mem` (GPP_HOST_F64 honoured). */
+int gpp_local_distribution_correction(gpp_points* grid, const float* background, gpp_points* points, const float* pobs,
+                                      const float* pbackground, int nT, const gpp_structure* structure, float min_quantile,
+                                      float max_quantile, int min_points, float* out, int mem);
 
 /* ---- optimal interpolation ------------------------------------------------
  * replaces gridpp::optimal_interpolation_full (src/api/oi.cpp:138-341, Points
