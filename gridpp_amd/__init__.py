@@ -1033,7 +1033,7 @@ def neighbourhood_search(array, search_array, halfwidth, search_target_min, sear
     if halfwidth < 0:
         raise ValueError("halfwidth must be positive")
     ap = None
-    if apply_array is not None and np.size(apply_array) > 0:
+    if apply_array is not None and (apply_array.numel() if _is_dev(apply_array) else np.size(apply_array)) > 0:
         if _is_dev(apply_array):
             import torch
             ap = apply_array.contiguous().to(torch.int32)
