@@ -31,7 +31,9 @@ else:
     # The alias carries the surface the suite pins for it (tests/test_pointwise_api.py lists the names a script must not find here).
     # local_distribution_correction orders tied values by rho where the reference leaves them to an unstable sort:
     # a script written for the reference asks for it by its own name, gridpp_amd.local_distribution_correction.
-    for _name in ("local_distribution_correction",):
+    # Gamma and gamma_inv return IEEE values (NaN, -inf, +inf) at the edges where the reference raises through Boost's error policies
+    # (DESIGN.md 4.12): they too are asked for by their own names, gridpp_amd.Gamma and gridpp_amd.gamma_inv.
+    for _name in ("local_distribution_correction", "Gamma", "gamma_inv"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

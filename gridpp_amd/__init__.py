@@ -1797,12 +1797,11 @@ class Transform:
 
     def _apply(self, value, backward):
         nd = _ndim(value)
-        p0, p1 = self._params()
         if nd == 0:
             if self._kind is None:
                 return -1.0
             out = C.c_float(np.nan)
-            check(lib().gpp_transform_scalar(float(value), self._kind, backward, p0, p1, C.byref(out)))
+            check(self._scalar_entry(float(value), backward, C.byref(out)))
             return out.value
         if nd > 3:
             raise RuntimeError("input must be a scalar or have 1, 2 or 3 dimensions, got %d" % nd)
@@ -1820,8 +1819,17 @@ class Transform:
         _sync_if_dev(mem)
         if not dev and v.dtype == np.float64:
             mem |= _capi.HOST_F64
-        check(lib().gpp_transform(_ptr(v), n, self._kind, backward, p0, p1, _ptr(out), mem))
+        check(self._vector_entry(_ptr(v), n, backward, _ptr(out), mem))
         return out
+
+    # the two C-ABI calls of _apply (a transform with other parameters than (p0, p1) overrides them)
+    def _scalar_entry(self, value, backward, out):
+        p0, p1 = self._params()
+        return lib().gpp_transform_scalar(value, self._kind, backward, p0, p1, out)
+
+    def _vector_entry(self, src, n, backward, dst, mem):
+        p0, p1 = self._params()
+        return lib().gpp_transform(src, n, self._kind, backward, p0, p1, dst, mem)
 
 
 class Identity(Transform):
@@ -1859,6 +1867,55 @@ class StartedBoxCox(Transform):
 
     def _params(self):
         return self._threshold, self._scaling
+
+
+class Gamma(Transform):
+    """transform.cpp:155-179: the cdf of the gamma distribution (shape, scale) at value + tolerance, rounded to float32, mapped to the
+    standard normal quantile; backward the other way round, minus the tolerance.  Where the reference raises through Boost's error
+    policies this returns IEEE values: forward gives NaN for value + tolerance < 0 and -inf / +inf where the float32
+    cdf is 0 / 1, backward gives +inf where the float32 normal cdf is 1 (inputs above about 5.4).  Not part of the `gridpp` alias."""
+    _kind = "gamma"   # not a GPP_TRANSFORM_* kind: the two entries below are its own
+
+    def __init__(self, shape, scale, tolerance=0.01):
+        if not is_valid(shape) or np.float32(shape) <= 0:
+            raise ValueError("Shape parameter must be > 0 in the gamma distribution")
+        if not is_valid(scale) or np.float32(scale) <= 0:
+            raise ValueError("Scale parameter must be > 0 in the gamma distribution")
+        if not is_valid(tolerance) or np.float32(tolerance) < 0:
+            raise ValueError("Tolerance must be >= 0 in the gamma distribution")
+        self._shape, self._scale, self._tolerance = (float(np.float32(v)) for v in (shape, scale, tolerance))
+
+    def _scalar_entry(self, value, backward, out):
+        return lib().gpp_gamma_transform_scalar(value, backward, self._shape, self._scale, self._tolerance, out)
+
+    def _vector_entry(self, src, n, backward, dst, mem):
+        return lib().gpp_gamma_transform(src, n, backward, self._shape, self._scale, self._tolerance, dst, mem)
+
+
+def gamma_inv(levels, shape, scale):
+    """src/api/distribution.cpp:5-33: the quantiles `levels` of gamma distributions, element by element: scale * x with
+    P(shape, x) = level.  Three 1-D arrays (lists, numpy arrays, or all torch CUDA tensors: the result is then a tensor on that device)
+    or three scalars (host arithmetic, a Python float back).  Level 0 gives 0; level 1 gives +inf, where the reference raises through
+    Boost's overflow policy.  ValueError with the reference's texts for the lowest index with a level outside [0, 1],
+    else a shape <= 0, else a scale <= 0 (NaN and infinities included).  The reference reads levels[i] and scale[i] up to len(shape)
+    without comparing the lengths; here unequal lengths are a ValueError.  Not part of the `gridpp` alias."""
+    args = (levels, shape, scale)
+    if all(_ndim(a) == 0 for a in args):
+        out = C.c_float(np.nan)
+        check(lib().gpp_gamma_inv_scalar(float(levels), float(shape), float(scale), C.byref(out)))
+        return out.value
+    mem = _mem(*args)
+    f64 = mem == _capi.MEM_HOST and _wants_f64(*args)
+    arrs = [_vec(a, 1, n) if _is_dev(a) else _vec(a, 1, n, np.float64 if f64 else np.float32) for a, n in zip(args, ("levels", "shape", "scale"))]
+    if not (_shape(arrs[0]) == _shape(arrs[1]) == _shape(arrs[2])):
+        raise ValueError("gamma_inv: levels, shape and scale must be of the same size")
+    n = _shape(arrs[0])[0]
+    if n == 0:
+        return _empty_like_field((0,), arrs[0]) if mem == _capi.MEM_DEVICE else np.zeros(0, np.float32)
+    _sync_if_dev(mem)
+    out = _empty_like_field((n,), arrs[0])
+    check(lib().gpp_gamma_inv(*[_ptr(a) for a in arrs], n, _ptr(out), mem | (_capi.HOST_F64 if f64 else 0)))
+    return out
 
 
 # ---- verification scores (include/gridpp.h:103-110; src/api/metric_optimizer.cpp:185-244, neighbourhood_score.cpp) ----

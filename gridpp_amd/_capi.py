@@ -15,6 +15,7 @@ ENSEMBLE_ROW_CAP = 1024   # GPP_ENSEMBLE_ROW_CAP of include/gridpp_hip.h
 WINDOW_TILE_ROWS, WINDOW_TILE_COLS, WINDOW_FUSED_SPAN = 64, 32, 31   # GPP_WINDOW_* of include/gridpp_hip.h
 SCORE_TILE_COLS, SCORE_TILE_ROWS, SCORE_FUSED_MAXHW = 64, 32, 16   # GPP_SCORE_* of include/gridpp_hip.h
 POINTWISE_BLOCK, POINTWISE_MAX_BLOCKS = 256, 2048   # GPP_POINTWISE_* of include/gridpp_hip.h
+GAMMA_BLOCK, GAMMA_MAX_BLOCKS = 256, 2048   # GPP_GAMMA_* of include/gridpp_hip.h
 TRANSFORM_IDENTITY, TRANSFORM_LOG, TRANSFORM_BOXCOX, TRANSFORM_STARTED_BOXCOX = 0, 1, 2, 3   # GPP_TRANSFORM_* of include/gridpp_hip.h
 (DIAG_DEWPOINT, DIAG_RELATIVE_HUMIDITY, DIAG_WETBULB, DIAG_PRESSURE, DIAG_SEA_LEVEL_PRESSURE, DIAG_QNH, DIAG_WIND_SPEED,
  DIAG_WIND_DIRECTION) = range(8)   # GPP_DIAG_* of include/gridpp_hip.h
@@ -135,6 +136,10 @@ SIGNATURES = {
     "gpp_transform": [vp, C.c_longlong, C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int],
     "gpp_diagnostic_scalar": [C.c_int, fp, C.c_int, fp],
     "gpp_transform_scalar": [C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, fp],
+    "gpp_gamma_inv": [vp, vp, vp, C.c_longlong, vp, C.c_int],
+    "gpp_gamma_transform": [vp, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, vp, C.c_int],
+    "gpp_gamma_inv_scalar": [C.c_float, C.c_float, C.c_float, fp],
+    "gpp_gamma_transform_scalar": [C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, fp],
 }
 STRING_GETTERS = ("gpp_last_error", "gpp_version")
 

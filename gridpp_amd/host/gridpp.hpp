@@ -1212,6 +1212,13 @@ class Transform {
         vec3 backward(const vec3& input) const { return apply(input, 1); }
     protected:
         Transform(int kind, float p0, float p1 = 0) : m_kind(kind), m_p0(p0), m_p1(p1) {}
+        // the one kernel call behind the six vector forms: a transform defined outside this header overrides it (and the scalar forms)
+        virtual vec apply(const vec& input, int backward) const {
+            vec out(input.size(), MV);
+            if(m_kind < 0) std::fill(out.begin(), out.end(), -1.0f);
+            else detail::check(gpp_transform(input.data(), (long long)input.size(), m_kind, backward, m_p0, m_p1, out.data(), GPP_MEM_HOST));
+            return out;
+        }
     private:
         int m_kind;   // GPP_TRANSFORM_*, -1: the base class
         float m_p0, m_p1;
@@ -1219,12 +1226,6 @@ class Transform {
             if(m_kind < 0) return -1;
             float out = MV;
             detail::check(gpp_transform_scalar(value, m_kind, backward, m_p0, m_p1, &out));
-            return out;
-        }
-        vec apply(const vec& input, int backward) const {
-            vec out(input.size(), MV);
-            if(m_kind < 0) std::fill(out.begin(), out.end(), -1.0f);
-            else detail::check(gpp_transform(input.data(), (long long)input.size(), m_kind, backward, m_p0, m_p1, out.data(), GPP_MEM_HOST));
             return out;
         }
         vec2 apply(const vec2& input, int backward) const {

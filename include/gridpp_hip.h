@@ -55,7 +55,7 @@ extern "C" {
  * (their float fields), by gpp_neighbourhood_quantile_fast for `input` only, by gpp_apply_curve and gpp_interpolate for the values
  * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs, by gpp_window for `array`, by gpp_neighbourhood_score for `fcst`,
  * by gpp_dewpoint, gpp_relative_humidity, gpp_wetbulb, gpp_pressure, gpp_sea_level_pressure, gpp_qnh, gpp_wind_speed and
- * gpp_wind_direction for all their inputs and by gpp_transform for `in`. */
+ * gpp_wind_direction for all their inputs, by gpp_transform and gpp_gamma_transform for `in` and by gpp_gamma_inv for its three inputs. */
 #define GPP_HOST_F64 4
 
 /* include/gridpp.h:120-123 */
@@ -560,6 +560,30 @@ int gpp_transform(const float* in, long long n, int kind, int backward, float p0
 int gpp_diagnostic_scalar(int which, const float* args, int nargs, float* out);
 /* Transform::forward(float) / backward(float) of the four kinds (transform.cpp:85-154,180-185); errors as gpp_transform. */
 int gpp_transform_scalar(float value, int kind, int backward, float p0, float p1, float* out);
+
+/* ---- the gamma distribution (include/gridpp.h:573,2438-2455) -----------------------------------------------------------------------
+ * Element-wise over n values like the entries above (`mem`, GPP_HOST_F64, n == 0, n < 0 and NULL as there).  The per-value arithmetic is
+ * gridpp_amd/csrc/gamma_fn.h: the regularised incomplete gamma function, its inverse and the normal quantile in double, every loop
+ * with a compile-time bound, shared with the host-only scalar forms below.  Where the reference raises through Boost's error policies
+ * the entries return IEEE values, so they are no part of the reference-compatible surface.  One value per lane:
+ * GPP_GAMMA_BLOCK lanes per workgroup, at most GPP_GAMMA_MAX_BLOCKS workgroups walking the values with a grid stride. */
+#define GPP_GAMMA_BLOCK 256
+#define GPP_GAMMA_MAX_BLOCKS 2048
+/* gridpp::gamma_inv (src/api/distribution.cpp:5-33): out[i] = (float)(scale[i] * x) with P(shape[i], x) = levels[i]; 0 for level 0, +inf
+ * for level 1.  GPP_EINVAL with the reference's texts for the lowest offending index, level before shape before scale: "Invalid level
+ * '<v>'. Levels must be on the interval [0, 1].", "Invalid shape '<v>'. Shapes must be > 0.", "Invalid scale '<v>'. Scale must be > 0."
+ * (<v> as an ostream prints a float).  The three arrays hold n values each: that is the caller's to make sure. */
+int gpp_gamma_inv(const float* levels, const float* shape, const float* scale, long long n, float* out, int mem);
+/* gridpp::Gamma::forward / backward over n values (src/api/transform.cpp:155-179 over :13-84).  forward: NaN for an invalid value and
+ * for value + tolerance < 0, -inf / +inf where the float32 cdf is 0 / 1; backward: NaN for an invalid value, +inf where the float32
+ * normal cdf is 1.  GPP_EINVAL with the texts of the constructor (transform.cpp:158-163): "Shape parameter must be > 0 in the gamma
+ * distribution", "Scale parameter must be > 0 in the gamma distribution", "Tolerance must be >= 0 in the gamma distribution". */
+int gpp_gamma_transform(const float* in, long long n, int backward, float shape, float scale, float tolerance, float* out, int mem);
+/* Host-only forms (no GPU needed); they run the per-value source of the kernels.
+ * gridpp::gamma_inv for one element (src/api/distribution.cpp:5-33); errors as gpp_gamma_inv. */
+int gpp_gamma_inv_scalar(float level, float shape, float scale, float* out);
+/* Gamma::forward(float) / backward(float) (src/api/transform.cpp:166-179); errors as gpp_gamma_transform. */
+int gpp_gamma_transform_scalar(float value, int backward, float shape, float scale, float tolerance, float* out);
 
 /* per-call statistics of the last OI call on this thread (diagnostics / bench) */
 typedef struct gpp_oi_stats {
