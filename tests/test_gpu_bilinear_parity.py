@@ -15,13 +15,22 @@ def _regular(Y, X, lat0=50.0, lat1=52.0, lon0=5.0, lon1=8.0):
 
 
 def _warped(Y, X, seed):
-    """A rotated, sheared and mildly curved mesh: boxes are general quadrilaterals."""
+    """A rotated, sheared and mildly curved mesh.  Its cells are 0.02 x 0.015 degrees and the curvature terms 2e-5 / 1e-5, so both
+    cross products of every box stay below the weights' absolute 1e-4 (the largest is 3.3e-7): what this mesh tests is the
+    parallelogram formula on rotated and sheared boxes.  The general-quadrilateral solve is tested on the meshes of
+    tests/bilinear_cases.py (tests/test_gpu_bilinear_general.py)."""
     rng = np.random.default_rng(seed)
     j, i = np.meshgrid(np.arange(Y, dtype=float), np.arange(X, dtype=float), indexing="ij")
     a = np.deg2rad(rng.uniform(-30, 30))
     u = 0.02 * (i * np.cos(a) - j * np.sin(a)) + 2e-5 * i * j
     v = 0.015 * (i * np.sin(a) + j * np.cos(a)) + 1e-5 * i * i
     return 55 + v, 8 + u
+
+
+def _all_parallelogram(lats, lons):
+    from tests.bilinear_cases import classify
+    cl = classify(lats, lons)
+    return cl["parallelogram"] == cl["boxes"] > 0
 
 
 def _field(Y, X, seed, nan_frac=0.0, T=None):
@@ -62,6 +71,7 @@ def test_grid_to_points_matches_oracle(mesh, nan_frac):
         lats, lons = _regular(Y, X)
     elif mesh == "warped":
         lats, lons = _warped(Y, X, 3)
+        assert _all_parallelogram(lats, lons)
     else:
         lats, lons = np.meshgrid(np.linspace(0, 60000, Y), np.linspace(-1000, 90000, X), indexing="ij")
     vals = _field(Y, X, 11, nan_frac)
@@ -79,6 +89,7 @@ def test_time_levels_and_grid_output_match_oracle():
     from oracle import oracle as O
     Y, X, T = 40, 50, 7
     lats, lons = _warped(Y, X, 8)
+    assert _all_parallelogram(lats, lons)
     olats, olons = _regular(33, 47, lats.min(), lats.max(), lons.min(), lons.max())
     vals = _field(Y, X, 2, 0.03, T)
     igrid, ogrid = gridpp.Grid(lats, lons), gridpp.Grid(olats, olons)
@@ -110,6 +121,7 @@ def test_get_box_matches_oracle():
     from oracle import oracle as O
     Y, X = 25, 31
     lats, lons = _warped(Y, X, 21)
+    assert _all_parallelogram(lats, lons)
     grid = gridpp.Grid(lats, lons)
     og = O.Pts(lats.ravel(), lons.ravel())
     qlat, qlon = _queries(lats, lons, 300, 2)

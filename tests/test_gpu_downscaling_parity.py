@@ -54,7 +54,7 @@ def test_known_answer_shapes_cover_all_four_overloads():
 def _mesh(kind, Y, X):
     if kind == "regular":
         return np.meshgrid(np.linspace(50.0, 52.0, Y), np.linspace(5.0, 8.0, X), indexing="ij")
-    if kind == "warped":   # rotated, sheared, mildly curved: boxes are general quadrilaterals
+    if kind == "warped":   # rotated, sheared, mildly curved: the parallelogram formula on rotated and sheared boxes (see below)
         j, i = np.meshgrid(np.arange(Y, dtype=float), np.arange(X, dtype=float), indexing="ij")
         a = np.deg2rad(17.0)
         return 55 + 0.015 * (i * np.sin(a) + j * np.cos(a)) + 1e-5 * i * i, 8 + 0.02 * (i * np.cos(a) - j * np.sin(a)) + 2e-5 * i * j
@@ -71,11 +71,16 @@ def _spoil(rng, a, frac=0.03, inf=True):
 
 
 class Case:
-    def __init__(self, mesh, out_kind, T, seed, Y=41, X=53):
+    def __init__(self, mesh, out_kind, T, seed, Y=41, X=53, ctype=None):
         import gridpp_amd as gridpp
         rng = np.random.default_rng(seed)
-        self.ctype = gridpp.Cartesian if mesh == "cartesian" else gridpp.Geodetic
-        self.lats, self.lons = _mesh(mesh, Y, X)
+        if isinstance(mesh, str):
+            self.ctype = gridpp.Cartesian if mesh == "cartesian" else gridpp.Geodetic
+            self.lats, self.lons = _mesh(mesh, Y, X)
+        else:   # the mesh itself: (lats, lons) arrays and the coordinate type (tests/test_gpu_bilinear_general.py)
+            self.ctype = gridpp.Geodetic if ctype is None else ctype
+            self.lats, self.lons = (np.asarray(a) for a in mesh)
+            Y, X = self.lats.shape
         self.ielevs = _spoil(rng, rng.uniform(0, 1500, (Y, X)), 0.02, False)
         self.ilafs = _spoil(rng, rng.uniform(0, 1, (Y, X)), 0.02, False)
         lead = (T,) if T else ()
@@ -170,6 +175,10 @@ def test_nearest_is_bit_exact_against_oracle_composition(mesh, out_kind, T):
 def test_bilinear_matches_both_compositions(mesh, out_kind, T):
     import gridpp_amd as gridpp
     c = Case(mesh, out_kind, T, seed=200 + (T or 0))
+    if mesh == "warped":   # millidegree cells: every box passes the weights' absolute 1e-4 and takes the parallelogram formula
+        from tests.bilinear_cases import classify
+        cl = classify(c.lats, c.lons)
+        assert cl["parallelogram"] == cl["boxes"] > 0
     fused = gridpp.full_gradient(c.igrid, c.out, c.values, c.egrad, c.lgrad, gridpp.Bilinear)
     same_bits(fused, c.full(c.d_device(1)))
     ref = c.full(c.d_oracle(1))
