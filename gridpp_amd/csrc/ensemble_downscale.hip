@@ -15,7 +15,9 @@
 //                       their two order statistics with all lanes of the group (rank counting over the staged row) and join
 //                       them with quantile_from_order.
 //   k_ens_mask_rows +   rows longer than GPP_ENSEMBLE_ROW_CAP members are not staged: the masked rows go to an HBM scratch
-//   k_ens_rows_result   slab and one thread per cell runs the same row functions on its row from memory.
+//   k_ens_rows_result   slab and one thread per cell runs the same row functions on its row from memory.  A slab holds 2^26
+//                       masked members; GPP_ENSEMBLE_SLAB (a path override) sets another number, so that the tests run
+//                       several slabs, a ragged last one included, on a grid of a hundred cells.
 #include "common.h"
 #include "row_stats.h"
 #include <algorithm>
@@ -209,6 +211,13 @@ void nearest_index(gpp_points* igrid, gpp_points* ogrid, DevBuf<int>& idx) {
     gpp_nearest_device(igrid, ogrid->d_x.p, ogrid->d_y.p, ogrid->d_z.p, ogrid->n, 1, idx.p);
 }
 
+// masked members per scratch slab (2^26 = 256 MiB; GPP_ENSEMBLE_SLAB overrides it so that the tests can reach the loop over slabs)
+long long slab_members() {
+    const char* e = path_env("GPP_ENSEMBLE_SLAB");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? v : (1ll << 26);
+}
+
 unsigned g_seed = 0x9e3779b9u;   // RandomChoice: a different draw every call (under the API lock)
 
 }   // namespace
@@ -295,7 +304,7 @@ extern "C" int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid
         GPP_HIP(hipGetLastError());
     }
     else {   // slabs of at most 2^26 masked members (256 MiB)
-        const int slab = (int)std::max<long long>(1, std::min<long long>(nq, (1ll << 26) / ne));
+        const int slab = (int)std::max<long long>(1, std::min<long long>(nq, slab_members() / ne));
         DevBuf<float> scratch;
         scratch.get((size_t)slab * ne);
         for(int q0 = 0; q0 < nq; q0 += slab) {

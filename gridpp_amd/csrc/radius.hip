@@ -7,6 +7,8 @@
 // axes and applies the reference's test to every point in them -- strictly inside the box, then chord length <= radius
 // in float32.  Variable-length results go through a CSR layout: a counting pass, a device-wide exclusive scan (rocPRIM),
 // a filling pass.  Statistics of a location's values are the sequential float loops of util.cpp:19-178 (row_stats.h).
+// Scratch that grows with the number of locations is filled in passes: GPP_CSR_CAP (radius_csr.h) sets the entries of a CSR
+// filling pass and GPP_KNN_SLAB those of a slab of gpp_distance's candidate lists, both 2^28 unless a path override says otherwise.
 #include "common.h"
 #include "oi_common.h"
 #include "row_stats.h"
@@ -577,8 +579,10 @@ extern "C" int gpp_distance(gpp_points* from, gpp_points* to, int num, int query
         gpp_obs_index* ix = gpp_build_obs_index(from);
         DevBuf<float> skey;
         DevBuf<int> sidx;
-        // scratch of k entries per location, in slabs of at most 2^28 entries
-        const int slab = (int)std::max<long long>(1, std::min<long long>(nq, (1ll << 28) / k));
+        // scratch of k entries per location, in slabs of at most 2^28 entries (GPP_KNN_SLAB: another number, so that the tests reach the loop)
+        const char* const e = path_env("GPP_KNN_SLAB");
+        const long long entries = e && atoll(e) > 0 ? atoll(e) : (1ll << 28);
+        const int slab = (int)std::max<long long>(1, std::min<long long>(nq, entries / k));
         skey.get((size_t)slab * k); sidx.get((size_t)slab * k);
         for(int q0 = 0; q0 < nq; q0 += slab) {
             const int m = std::min(slab, nq - q0);

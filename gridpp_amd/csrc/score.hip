@@ -16,7 +16,9 @@
 //                       LDS: the chunk's rows have a pitch of 25 words and the ring's rows one of 65 double words, and in the row pass
 //                       the 32 lanes of a half wavefront hold 32 rows of one eight-column segment: their byte reads fall into 32
 //                       different banks and the 8-byte ring writes of 16 lanes cover all 32 once.  The column pass reads the ring along
-//                       a row: consecutive words.  36 480 bytes per workgroup, four workgroups per CU.
+//                       a row: consecutive words.  36 480 bytes per workgroup, four workgroups per CU.  GPP_SCORE_FILL (a path override)
+//                       replaces the 1024 workgroups the launch aims for: with 1 a workgroup marches down all rows of its strip, as it
+//                       does on fields of millions of cells, and the tests reach the wrapping ring on small grids.
 //   k_score_rows /      the general path, any half width (the host clamps it to the longer side of the field, which changes no window):
 //   k_score_cols        a separable pair with 32-bit counters, four per cell in a workspace plane, sliding along runs of SC_RUN cells;
 //                       the column kernel ends in the same finish step.  GPP_SCORE_GENERAL (a path override) forces it.
@@ -286,7 +288,8 @@ extern "C" int gpp_neighbourhood_score(gpp_points* grid, gpp_points* points, con
     GPP_HIP(hipGetLastError());
     if(half_width <= SC_MAXHW && !path_env("GPP_SCORE_GENERAL")) {
         const int strips = (X + SC_W - 1) / SC_W;
-        const int segs = std::max(1, std::min((1024 + strips - 1) / strips, (Y + SC_C - 1) / SC_C));   // about a thousand workgroups where the field has them
+        const long fill = path_env("GPP_SCORE_FILL") ? std::max(1, atoi(path_env("GPP_SCORE_FILL"))) : 1024;   // (tests: workgroups the launch aims for)
+        const int segs = (int)std::max(1L, std::min((fill + strips - 1) / strips, (long)(Y + SC_C - 1) / SC_C));   // about a thousand workgroups where the field has them
         int SH = ((Y + segs - 1) / segs + SC_C - 1) / SC_C * SC_C;
         while((Y + SH - 1) / SH > 65535) SH += SC_C;
         hipLaunchKernelGGL(k_score_march, dim3(strips, (Y + SH - 1) / SH), dim3(SC_THREADS), 0, stream(), (const unsigned char*)cat.p, Y, X, half_width,

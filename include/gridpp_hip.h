@@ -158,7 +158,9 @@ int gpp_count(gpp_points* from, gpp_points* to, float radius, float* out, int me
 /* gridpp::distance (src/api/distance.cpp:6-120, all four overloads): out[i] = the largest KDTree::calc_distance
  * (src/api/kdtree.cpp:107-133) between location i of `to` and its `num` nearest points of `from`.  query_first = 1 for
  * the overloads whose output is a Points (they call calc_distance(location, neighbour)), 0 for those whose output is a
- * Grid (calc_distance(neighbour, location)).  GPP_EINVAL if the coordinate types differ. */
+ * Grid (calc_distance(neighbour, location)).  GPP_EINVAL if the coordinate types differ.  The candidate lists (min(num, size of
+ * `from`) entries per location) live in an HBM scratch filled in slabs of 2^28 entries (at least one location); the path override
+ * GPP_KNN_SLAB = n (n > 0) sets another number of entries per slab.  The result does not depend on it. */
 int gpp_distance(gpp_points* from, gpp_points* to, int num, int query_first, float* out, int mem);
 /* gridpp::gridding (src/api/gridding.cpp:6-63): statistic of the values of the points of `from` within `radius` of every
  * location of `to`; NaN where fewer than min_num (> 0) points are found.  GPP_EINVAL for radius < 0 / NaN, min_num < 0.
@@ -243,7 +245,9 @@ int gpp_downscale_probability(gpp_points* igrid, gpp_points* ogrid, const float*
  * a cell's masked row is NaN where threshold_values is not valid, ivalues_true where threshold_values OP threshold, else
  * ivalues_false; out = calc_statistic(row, statistic), or calc_quantile(row, quantile) for GPP_QUANTILE (the _quantile
  * form; _consensus passes quantile 0).  GPP_ERUNTIME "Internal error. Cannot compute statistic" for an unknown statistic,
- * GPP_EINVAL for a quantile outside [0, 1] (a NaN quantile gives NaN).  GPP_RANDOMCHOICE: some valid member of the row. */
+ * GPP_EINVAL for a quantile outside [0, 1] (a NaN quantile gives NaN).  GPP_RANDOMCHOICE: some valid member of the row.
+ * Rows longer than GPP_ENSEMBLE_ROW_CAP go through an HBM scratch in slabs of 2^26 masked members (at least one cell); the path
+ * override GPP_ENSEMBLE_SLAB = n (n > 0) sets another number of members per slab.  The result does not depend on it. */
 int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid, const float* ivalues_true, const float* ivalues_false,
                                  const float* threshold_values, int ne, const float* threshold, int comparison_operator,
                                  int statistic, float quantile, float* out, int mem);
@@ -499,7 +503,9 @@ int gpp_calc_score(const float* ref, const float* fcst, long long n, float thres
  * than 0", then "Unknown metric".  The sizes of fcst and ref are the caller's to check (the reference's first and last check).  An empty
  * grid returns GPP_OK and writes nothing.  Half widths up to GPP_SCORE_FUSED_MAXHW take one fused kernel (row and column pass over one
  * byte per cell, the four counts packed in 16-bit lanes, which holds while (2 half_width + 1)^2 < 65536); wider ones, and every call
- * under the path override GPP_SCORE_GENERAL, a separable pair with 32-bit counters.  Both give the same bits. */
+ * under the path override GPP_SCORE_GENERAL, a separable pair with 32-bit counters.  Both give the same bits.  The fused launch cuts the
+ * rows into segments so that about 1024 workgroups exist; the path override GPP_SCORE_FILL = n (n >= 1) sets another number, n = 1 giving
+ * one workgroup per strip that marches down every row, as on fields of millions of cells.  The result does not depend on it. */
 #define GPP_SCORE_TILE_COLS 64      /* output columns of a strip of the fused kernel */
 #define GPP_SCORE_TILE_ROWS 32      /* rows of a chunk of the strip */
 #define GPP_SCORE_FUSED_MAXHW 16    /* the ring of the fused kernel holds 32 + 2 * 16 rows; (2 * 16 + 1)^2 = 1089 < 65536 */
