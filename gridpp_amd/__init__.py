@@ -841,6 +841,17 @@ def obs_index_axes(points):
     return a.value, b.value
 
 
+def obs_index_layout(points):
+    """Diagnostics: the bin layout of the observation index of `points`: nbx, nby, amin, bmin, inv_s, bin_start [nbx * nby + 1] and
+    whether the index was built on the device."""
+    dims, geom = np.zeros(3, np.int32), np.zeros(3, np.float32)
+    check(lib().gpp_debug_obs_index(points._h, _ptr(dims), _ptr(geom), None, 0))
+    start = np.zeros(int(dims[0]) * int(dims[1]) + 1, np.int32)
+    check(lib().gpp_debug_obs_index(points._h, _ptr(dims), _ptr(geom), _ptr(start), start.size))
+    return {"nbx": int(dims[0]), "nby": int(dims[1]), "amin": geom[0], "bmin": geom[1], "inv_s": geom[2], "bin_start": start,
+            "device_built": bool(dims[2])}
+
+
 # ---- nearest (src/api/nearest.cpp:124-144) ----------------------------------------------------------
 def nearest(igrid, opoints, values):
     """All eight overloads of src/api/nearest.cpp: Grid|Points -> Grid|Points, with or without a leading time dimension."""

@@ -97,6 +97,7 @@ SIGNATURES = {
     "gpp_optimal_interpolation_full": [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(gpp_structure), C.c_int, C.c_int, vp, vp, C.c_int],
     "gpp_oi_last_stats": [C.POINTER(gpp_oi_stats)],
     "gpp_debug_obs_axes": [vp, ip, ip],
+    "gpp_debug_obs_index": [vp, vp, vp, vp, C.c_int],
     "gpp_wait": [],
     "gpp_pending": [ip],
     "gpp_optimal_interpolation_ensi": [vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(gpp_structure), C.c_int, C.c_int, vp, C.c_int],

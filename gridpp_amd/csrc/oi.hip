@@ -66,6 +66,7 @@ static gpp_obs_index* build_obs_index_device(gpp_points* pts) {
     std::unique_ptr<gpp_obs_index> ix(new gpp_obs_index);
     const int S = pts->n;
     ix->S = S;
+    ix->device_built = true;
     pts->to_device();
     const float* dax[3] = {pts->d_x.p, pts->d_y.p, pts->d_z.p};
     // extents of the three axes
@@ -1296,6 +1297,27 @@ extern "C" int gpp_debug_obs_axes(gpp_points* points, int* axis_a, int* axis_b) 
     ensure_device();
     const gpp_obs_index* const ix = gpp_build_obs_index(points);
     *axis_a = ix->axis_a; *axis_b = ix->axis_b;
+    return GPP_OK;
+    GPP_CATCH
+}
+
+// the bin layout of that index (built if it is not there yet): dims = {nbx, nby, 1 if it was built on the device}, geom = {amin, bmin, inv_s},
+// and the first min(cap, nbx * nby + 1) entries of bin_start (bin_start may be NULL) -- what a test needs to know which bins and row segments
+// a query walks.  Reads only: no result and no launch of any other call depends on it.
+extern "C" int gpp_debug_obs_index(gpp_points* points, int* dims, float* geom, int* bin_start, int cap) {
+    GPP_TRY
+    if(!points || !dims || !geom) invalid("points / dims / geom is NULL");
+    if(points->n <= 0) invalid("the point set is empty");
+    if(cap < 0) invalid("cap < 0");
+    ensure_device();
+    const gpp_obs_index* const ix = gpp_build_obs_index(points);
+    dims[0] = ix->nbx; dims[1] = ix->nby; dims[2] = ix->device_built ? 1 : 0;
+    geom[0] = ix->amin; geom[1] = ix->bmin; geom[2] = ix->inv_s;
+    const int n = std::min(cap, ix->nbx * ix->nby + 1);
+    if(bin_start && n > 0) {
+        GPP_HIP(hipMemcpyAsync(bin_start, ix->d_bin_start.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, stream()));
+        GPP_HIP(hipStreamSynchronize(stream()));
+    }
     return GPP_OK;
     GPP_CATCH
 }

@@ -14,6 +14,7 @@ struct gpp_obs_index {
     int axis_a = 0, axis_b = 1;
     float amin = 0, bmin = 0, inv_s = 0;
     int nbx = 1, nby = 1;
+    bool device_built = false;   // (diagnostics: which of the two builds made it)
     DevBuf<int> d_bin_start;   // [nbx*nby+1]
     DevBuf<int> d_pos;         // orig -> sorted position
     DevBuf<float4> d_sgeo;     // sorted: x,y,z,elev

@@ -608,6 +608,9 @@ int gpp_oi_last_stats(gpp_oi_stats* stats);
 /* diagnostics: the two coordinate axes (0 = x, 1 = y, 2 = z; the two of largest extent) on which the observation index of `points` is binned --
  * the axes along which optimal_interpolation's tile kernels take a tile's extent.  Builds the index when the set has none yet. */
 int gpp_debug_obs_axes(gpp_points* points, int* axis_a, int* axis_b);
+/* Diagnostics: the bin layout of that index: dims[3] = {nbx, nby, 1 if the index was built on the device}, geom[3] = {amin, bmin, inv_s}, and
+ * the first min(cap, nbx * nby + 1) entries of its bin_start (bin_start may be NULL). */
+int gpp_debug_obs_index(gpp_points* points, int* dims, float* geom, int* bin_start, int cap);
 
 /* Asynchronous optimal interpolation (no counterpart in the reference, whose calls return their result; this is for a caller that streams
  * analyses -- one per observation set -- through one GPU, e.g. a rank of the multi-GPU tiling, src/api/oi.cpp:221-338 has no state between
