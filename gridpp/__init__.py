@@ -33,7 +33,9 @@ else:
     # a script written for the reference asks for it by its own name, gridpp_amd.local_distribution_correction.
     # Gamma and gamma_inv return IEEE values (NaN, -inf, +inf) at the edges where the reference raises through Boost's error policies
     # (DESIGN.md 4.12): they too are asked for by their own names, gridpp_amd.Gamma and gridpp_amd.gamma_inv.
-    for _name in ("local_distribution_correction", "Gamma", "gamma_inv"):
+    # get_optimal_threshold and metric_optimizer_curve return the exact optimum over the plateaus of the score where the reference returns
+    # wherever Boost's brent_find_minima ends: gridpp_amd.get_optimal_threshold, gridpp_amd.metric_optimizer_curve.
+    for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

@@ -2013,6 +2013,58 @@ def neighbourhood_score(grid, points, fcst, ref, half_width, metric, threshold):
     return out
 
 
+# ---- the optimal forecast threshold (src/api/metric_optimizer.cpp:105-184) ----
+def _optimizer_vectors(ref, fcst):
+    """-> ref, fcst, mem: numpy arrays (float64 ones of 2**20 values and more are cast on the device) or torch CUDA tensors"""
+    mem = _mem(ref, fcst)
+    dtype = np.float64 if mem == _capi.MEM_HOST and _wants_f64(ref, fcst) else np.float32
+    ref = _score_vector(ref, "ref") if _is_dev(ref) else _vec(ref, 1, "ref", dtype)
+    fcst = _score_vector(fcst, "fcst") if _is_dev(fcst) else _vec(fcst, 1, "fcst", dtype)
+    return ref, fcst, mem | (_capi.HOST_F64 if dtype == np.float64 else 0)
+
+
+def get_optimal_threshold(ref, fcst, threshold, metric):
+    """The forecast threshold x that maximises calc_score(ref, fcst, threshold, x, metric), as DESIGN.md 4.13 defines it: the score is
+    constant between two neighbouring values of fcst, so every plateau [u_k, u_k+1) of the distinct finite values u_0 < ... < u_m-1 is
+    evaluated (one sort and one sweep on the GPU) and the result is the midpoint of the lowest run of plateaus with the largest valid
+    score (its lower end where the midpoint would round up to the next plateau).  NaN with the reference's filters
+    (src/api/metric_optimizer.cpp:165-182): no valid score, a best score <= 0.0001, or one within 0.001 of the score at u_0 or u_m-1; also
+    for empty vectors (no GPU needed) and without a finite fcst.  The reference minimises with Boost's brent_find_minima, which ends
+    somewhere on whichever plateau it reaches: this result is never worse and is defined, but it is not the reference's number, so the
+    name is not part of the `gridpp` alias.  ref, fcst: numpy arrays or torch CUDA tensors; a float comes back.  ValueError("Unknown
+    metric"); a ref shorter than fcst is ValueError("ref and fcst not the same size"), as for calc_score."""
+    metric = _metric(metric)
+    ref, fcst, mem = _optimizer_vectors(ref, fcst)
+    n = _shape(fcst)[0]
+    if _shape(ref)[0] < n:
+        raise ValueError("ref and fcst not the same size")
+    out = C.c_float(np.nan)
+    if n:
+        _sync_if_dev(mem)
+    check(lib().gpp_get_optimal_threshold(_ptr(ref), _ptr(fcst), n, float(threshold), metric, C.byref(out), mem if n else _capi.MEM_HOST))
+    return out.value
+
+
+def metric_optimizer_curve(ref, fcst, thresholds, metric):
+    """src/api/metric_optimizer.cpp:105-127 on get_optimal_threshold above: -> (curve_ref, curve_fcst), two float32 numpy arrays.  For
+    every threshold t, in order, whose optimal forecast threshold x is valid, x goes to curve_ref and t to curve_fcst (the reference's
+    naming).  One sort serves all thresholds.  ValueError("ref and fcst not the same size") unless both have the same length; empty
+    thresholds give two empty arrays and need no GPU.  Not part of the `gridpp` alias."""
+    metric = _metric(metric)
+    ref, fcst, mem = _optimizer_vectors(ref, fcst)
+    n = _shape(fcst)[0]
+    if _shape(ref)[0] != n:
+        raise ValueError("ref and fcst not the same size")
+    thresholds = _vec(thresholds.cpu().numpy() if _is_dev(thresholds) else thresholds, 1, "thresholds")   # a host vector whatever ref and fcst are
+    T = thresholds.shape[0]
+    curve_ref, curve_fcst, count = np.empty(T, np.float32), np.empty(T, np.float32), C.c_int(0)
+    if T and n:
+        _sync_if_dev(mem)
+        check(lib().gpp_metric_optimizer_curve(_ptr(ref), _ptr(fcst), n, _ptr(thresholds), T, metric, _ptr(curve_ref), _ptr(curve_fcst),
+                                               C.byref(count), mem))
+    return curve_ref[:count.value].copy(), curve_fcst[:count.value].copy()
+
+
 # ---- util (include/gridpp.h:1454-1482, src/api/util.cpp) ---------------------------------------------
 def calc_statistic(array, statistic):
     """gridpp::calc_statistic for a vector (-> float) or a 2-D array (-> one value per row)."""

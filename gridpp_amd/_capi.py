@@ -16,6 +16,7 @@ WINDOW_TILE_ROWS, WINDOW_TILE_COLS, WINDOW_FUSED_SPAN = 64, 32, 31   # GPP_WINDO
 SCORE_TILE_COLS, SCORE_TILE_ROWS, SCORE_FUSED_MAXHW = 64, 32, 16   # GPP_SCORE_* of include/gridpp_hip.h
 POINTWISE_BLOCK, POINTWISE_MAX_BLOCKS = 256, 2048   # GPP_POINTWISE_* of include/gridpp_hip.h
 GAMMA_BLOCK, GAMMA_MAX_BLOCKS = 256, 2048   # GPP_GAMMA_* of include/gridpp_hip.h
+MO_TILE_ITEMS, MO_GROUP = 2048, 4   # GPP_MO_* of include/gridpp_hip.h
 TRANSFORM_IDENTITY, TRANSFORM_LOG, TRANSFORM_BOXCOX, TRANSFORM_STARTED_BOXCOX = 0, 1, 2, 3   # GPP_TRANSFORM_* of include/gridpp_hip.h
 (DIAG_DEWPOINT, DIAG_RELATIVE_HUMIDITY, DIAG_WETBULB, DIAG_PRESSURE, DIAG_SEA_LEVEL_PRESSURE, DIAG_QNH, DIAG_WIND_SPEED,
  DIAG_WIND_DIRECTION) = range(8)   # GPP_DIAG_* of include/gridpp_hip.h
@@ -126,6 +127,8 @@ SIGNATURES = {
     "gpp_calc_score_table": [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp],
     "gpp_calc_score": [vp, vp, C.c_longlong, C.c_float, C.c_float, C.c_int, fp, C.c_int],
     "gpp_neighbourhood_score": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int],
+    "gpp_get_optimal_threshold": [vp, vp, C.c_longlong, C.c_float, C.c_int, fp, C.c_int],
+    "gpp_metric_optimizer_curve": [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp, ip, C.c_int],
     "gpp_dewpoint": [vp, vp, C.c_longlong, vp, C.c_int],
     "gpp_relative_humidity": [vp, vp, C.c_longlong, vp, C.c_int],
     "gpp_wetbulb": [vp, vp, vp, C.c_longlong, vp, C.c_int],

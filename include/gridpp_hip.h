@@ -55,7 +55,8 @@ extern "C" {
  * (their float fields), by gpp_neighbourhood_quantile_fast for `input` only, by gpp_apply_curve and gpp_interpolate for the values
  * (their curves are host float32 arrays), by gpp_apply_curve_field for the values and both curve slabs, by gpp_window for `array`, by gpp_neighbourhood_score for `fcst`,
  * by gpp_dewpoint, gpp_relative_humidity, gpp_wetbulb, gpp_pressure, gpp_sea_level_pressure, gpp_qnh, gpp_wind_speed and
- * gpp_wind_direction for all their inputs, by gpp_transform and gpp_gamma_transform for `in` and by gpp_gamma_inv for its three inputs. */
+ * gpp_wind_direction for all their inputs, by gpp_transform and gpp_gamma_transform for `in` and by gpp_gamma_inv for its three inputs,
+ * by gpp_get_optimal_threshold and gpp_metric_optimizer_curve for `ref` and `fcst` (the thresholds are host float32 values). */
 #define GPP_HOST_F64 4
 
 /* include/gridpp.h:120-123 */
@@ -511,6 +512,29 @@ int gpp_calc_score(const float* ref, const float* fcst, long long n, float thres
 #define GPP_SCORE_FUSED_MAXHW 16    /* the ring of the fused kernel holds 32 + 2 * 16 rows; (2 * 16 + 1)^2 = 1089 < 65536 */
 int gpp_neighbourhood_score(gpp_points* grid, gpp_points* points, const float* fcst, const float* ref, int half_width, int metric,
                             float threshold, float* out, int mem);
+
+/* ---- the optimal forecast threshold (include/gridpp.h, src/api/metric_optimizer.cpp:105-184) ----------------------------------------
+ * NOT the reference's result: the reference minimises with Boost's brent_find_minima, which ends on an arbitrary point of whichever
+ * plateau of the piecewise-constant score it reaches.  These entries return the exact optimum over all plateaus, so
+ * they are no part of the reference-compatible surface.
+ * s(x) = gpp_calc_score(ref, fcst, n, threshold, x, metric), with its counting rules and its cap of 2^24 per count.  u_0 < ... < u_{m-1}
+ * are the distinct finite values of fcst (-0 counts as +0); s is constant on [u_k, u_{k+1}) and at u_{m-1}.  best = the largest score
+ * over these plateaus that is neither NaN nor infinite; [lo, hi) = the lowest run of adjacent plateaus whose score equals best (hi =
+ * u_{m-1} when the run reaches the top); *out = (float)(((double)lo + (double)hi) / 2), or lo where hi > lo and that rounds to hi.  NaN
+ * when no plateau has a valid score, when best <= 0.0001f, and when |best - s(u_0)| < 0.001f or |best - s(u_{m-1})| < 0.001f (the
+ * reference's filters, metric_optimizer.cpp:165-182); also for n == 0 (no device needed) and without a finite fcst.  GPP_EINVAL "Unknown
+ * metric".  The caller makes sure that ref holds n elements.  ref / fcst follow `mem` (GPP_HOST_F64 honoured for both); *out is host
+ * memory.  One radix sort of the (fcst, ref) pairs, then one sweep over the sorted order; up to 2^31 values.  The path override
+ * GPP_MO_TILE = k (1 <= k <= GPP_MO_TILE_ITEMS) sets the elements a workgroup of the sweep takes; the result does not depend on it. */
+#define GPP_MO_TILE_ITEMS 2048   /* elements of a workgroup of the sweep: 256 lanes with 8 each */
+#define GPP_MO_GROUP 4           /* thresholds a workgroup of the sweep carries in registers */
+int gpp_get_optimal_threshold(const float* ref, const float* fcst, long long n, float threshold, int metric, float* out, int mem);
+/* gridpp::metric_optimizer_curve (metric_optimizer.cpp:105-127): the rule above for each of the num_thresholds thresholds, in order, with
+ * ONE sort and the thresholds swept GPP_MO_GROUP to a workgroup; where the result x is valid, out_ref[k] = x and out_fcst[k] = the
+ * threshold (the reference's naming), k counting the valid ones; *out_count = their number.  thresholds, out_ref, out_fcst (room for
+ * num_thresholds values each) and out_count are host memory; ref / fcst follow `mem`.  num_thresholds == 0 and n == 0 need no device. */
+int gpp_metric_optimizer_curve(const float* ref, const float* fcst, long long n, const float* thresholds, int num_thresholds, int metric,
+                               float* out_ref, float* out_fcst, int* out_count, int mem);
 
 /* ---- weather diagnostics and value transforms (include/gridpp.h:1249-1367,2345-2435) ----------------------------------------------
  * Element-wise over n values: every input array and `out` hold n floats and follow `mem` (GPP_MEM_HOST or GPP_MEM_DEVICE;
