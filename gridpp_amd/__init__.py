@@ -2066,40 +2066,73 @@ def metric_optimizer_curve(ref, fcst, thresholds, metric):
 
 
 # ---- util (include/gridpp.h:1454-1482, src/api/util.cpp) ---------------------------------------------
-def calc_statistic(array, statistic):
-    """gridpp::calc_statistic for a vector (-> float) or a 2-D array (-> one value per row)."""
+def _rows_array(array, maxdim):
+    """calc_statistic / calc_quantile input: a host array or a torch CUDA tensor -> C-contiguous float32 of 1 .. maxdim dimensions"""
+    nd = _ndim(array) if _is_dev(array) else np.ndim(array)
+    if _is_dev(array):
+        if not 1 <= nd <= maxdim:
+            raise RuntimeError("array must have %s dimensions" % ("1 or 2" if maxdim == 2 else "1, 2 or 3"))
+        return _vec(array, nd)
     a = np.ascontiguousarray(np.asarray(array), dtype=np.float32)
-    if a.ndim not in (1, 2):
-        raise RuntimeError("array must have 1 or 2 dimensions")
-    rows = 1 if a.ndim == 1 else a.shape[0]
-    length = a.shape[-1]
-    out = np.empty(rows, np.float32)
+    if not 1 <= a.ndim <= maxdim:
+        raise RuntimeError("array must have %s dimensions" % ("1 or 2" if maxdim == 2 else "1, 2 or 3"))
+    return a
+
+
+def _rows_result(out, a):
+    """1-D input -> a Python float; otherwise the per-row result where the input lives"""
+    if len(_shape(a)) != 1:
+        return out
+    return float(out[0].item()) if _is_dev(out) else float(out[0])
+
+
+def calc_statistic(array, statistic):
+    """gridpp::calc_statistic for a vector (-> float) or a 2-D array (-> one value per row); host arrays or torch CUDA tensors."""
+    a = _rows_array(array, 2)
+    shp = _shape(a)
+    rows = 1 if len(shp) == 1 else shp[0]
+    length = shp[-1]
+    mem = _mem(a)
+    _sync_if_dev(mem)
+    out = _empty_like_field((rows,), a) if _is_dev(a) else np.empty(rows, np.float32)
     if rows:
-        check(lib().gpp_calc_statistic(_ptr(a), rows, length, int(statistic), _ptr(out), _capi.MEM_HOST))
-    return float(out[0]) if a.ndim == 1 else out
+        check(lib().gpp_calc_statistic(_ptr(a), rows, length, int(statistic), _ptr(out), mem))
+    return _rows_result(out, a)
 
 
 def calc_quantile(array, quantile):
-    """gridpp::calc_quantile: (vec, q) -> float, (vec2, q) -> vec, (vec3, vec2 q) -> vec2."""
-    a = np.ascontiguousarray(np.asarray(array), dtype=np.float32)
-    q = np.ascontiguousarray(np.asarray(quantile), dtype=np.float32)
-    if a.ndim == 3:
-        if q.shape != a.shape[:2]:
+    """gridpp::calc_quantile: (vec, q) -> float, (vec2, q) -> vec, (vec3, vec2 q) -> vec2; host arrays or torch CUDA tensors (a
+    quantile field beside a device-resident cube may be either and is uploaded when it is a host array)."""
+    a = _rows_array(array, 3)
+    shp = _shape(a)
+    dev = _is_dev(a)
+    if dev:
+        import torch
+        if _is_dev(quantile):
+            q = quantile.contiguous().to(torch.float32)
+        else:
+            q = torch.from_numpy(np.ascontiguousarray(np.asarray(quantile), dtype=np.float32)).to(a.device)
+    else:
+        _mem(a, quantile)   # (a device-resident quantile beside a host array: _mem's error)
+        q = np.ascontiguousarray(np.asarray(quantile), dtype=np.float32)
+    mem = _mem(a, q)
+    if len(shp) == 3:
+        if _shape(q) != shp[:2]:
             raise ValueError("Dimension mismatch between array and quantile")
-        if a.shape[0] * a.shape[1] == 0:
+        if shp[0] * shp[1] == 0:
             return np.zeros((0, 0), np.float32)
-        rows, length = a.shape[0] * a.shape[1], a.shape[2]
-        out = np.empty(rows, np.float32)
-        check(lib().gpp_calc_quantile(_ptr(a), rows, length, _ptr(q), rows, _ptr(out), _capi.MEM_HOST))
-        return out.reshape(a.shape[:2])
-    if a.ndim not in (1, 2):
-        raise RuntimeError("array must have 1, 2 or 3 dimensions")
-    rows = 1 if a.ndim == 1 else a.shape[0]
-    out = np.empty(rows, np.float32)
+        rows, length = shp[0] * shp[1], shp[2]
+        _sync_if_dev(mem)
+        out = _empty_like_field((rows,), a) if dev else np.empty(rows, np.float32)
+        check(lib().gpp_calc_quantile(_ptr(a), rows, length, _ptr(q), rows, _ptr(out), mem))
+        return out.reshape(shp[:2])
+    rows = 1 if len(shp) == 1 else shp[0]
+    out = _empty_like_field((rows,), a) if dev else np.empty(rows, np.float32)
     qq = q.reshape(1)
     if rows:
-        check(lib().gpp_calc_quantile(_ptr(a), rows, a.shape[-1], _ptr(qq), 1, _ptr(out), _capi.MEM_HOST))
-    return float(out[0]) if a.ndim == 1 else out
+        _sync_if_dev(mem)
+        check(lib().gpp_calc_quantile(_ptr(a), rows, shp[-1], _ptr(qq), 1, _ptr(out), mem))
+    return _rows_result(out, a)
 
 
 def _even_quantiles(values, num, only_valid):

@@ -30,6 +30,7 @@ using namespace gpp;
 
 #include "row_stats.h"
 #include "qf_box.h"
+#include "rows_select.h"
 
 // -------------------------------------------------------------------------------------------
 // member pass
@@ -451,12 +452,6 @@ __global__ __launch_bounds__(64) void k_qf_count(const float* __restrict__ in, l
         const long cell = nfull * 64 + lane;
         if(cell < C) member_row_work<2>(in + cell * E, E, false, 0, thr, T, reinterpret_cast<float*>(out8), C, cell, g);
     }
-}
-
-// Median / exact quantile over the members of each cell (rare path; one lane per cell from memory)
-__global__ void k_member_quantile(const float* __restrict__ in, long C, int E, float q, float* __restrict__ out) {
-    long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(c < C) out[c] = row_quantile(in + c * E, E, q);
 }
 
 // -------------------------------------------------------------------------------------------
@@ -1403,7 +1398,7 @@ struct NbhCall : Fields {
     }
     void member_statistic() {   // 3-D form: member statistic first (:12-27), into ws.flat
         float* flat = ws.flat.get(C);
-        if(statistic == GPP_MEDIAN) hipLaunchKernelGGL(k_member_quantile, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), in.d, C, ne, 0.5f, flat);
+        if(statistic == GPP_MEDIAN) rows_quantile(in.d, C, ne, nullptr, 0, flat);   // (rows_select.hip)
         else if(statistic == GPP_RANDOMCHOICE) brute(in.d, ny, nx, ne, 0, GPP_RANDOMCHOICE, 0, flat);
         else member_pass(in.d, C, ne, 0, statistic, nullptr, 0, flat);
     }
@@ -1576,15 +1571,9 @@ extern "C" int gpp_neighbourhood_quantile_fast(const float* input, int ny, int n
 // -------------------------------------------------------------------------------------------
 // util: calc_statistic / calc_quantile on rows, calc_even_quantiles / get_neighbourhood_thresholds
 // -------------------------------------------------------------------------------------------
-__global__ void k_rows_quantile(const float* __restrict__ in, long rows, int len, const float* __restrict__ q, int qfield, float* __restrict__ out) {
-    long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(r < rows) out[r] = row_quantile(in + r * len, len, qfield ? q[r] : q[0]);
-}
 __global__ void k_rows_statistic(const float* __restrict__ in, long rows, int len, int statistic, float* __restrict__ out) {
     long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(r >= rows) return;
-    if(statistic == GPP_MEDIAN) out[r] = row_quantile(in + r * len, len, 0.5f);
-    else out[r] = row_statistic(in + r * len, len, statistic);
+    if(r < rows) out[r] = row_statistic(in + r * len, len, statistic);
 }
 
 // gridpp::calc_statistic(vec2, statistic) (util.cpp:19-110,208-215): one value per row
@@ -1596,7 +1585,8 @@ extern "C" int gpp_calc_statistic(const float* array, long rows, int len, int st
     ensure_device();
     Fields f;
     f.bind(array, (size_t)rows * len, out, rows, mem);
-    if(len <= MEMBER_EC && statistic != GPP_MEDIAN && len > 0) member_pass(f.in.d, rows, len, 0, statistic, nullptr, 0, f.o.d);
+    if(statistic == GPP_MEDIAN) rows_quantile(f.in.d, rows, len, nullptr, 0, f.o.d);
+    else if(len <= MEMBER_EC && len > 0) member_pass(f.in.d, rows, len, 0, statistic, nullptr, 0, f.o.d);
     else hipLaunchKernelGGL(k_rows_statistic, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), f.in.d, rows, len, statistic, f.o.d);
     GPP_HIP(hipGetLastError());
     return f.done();
@@ -1608,16 +1598,14 @@ extern "C" int gpp_calc_quantile(const float* array, long rows, int len, const f
     if(nq != 1 && nq != rows) invalid("Dimension mismatch between array and quantile");
     if(rows <= 0) return GPP_OK;
     ensure_device();
-    std::vector<float> hq(nq);
-    if(mem & GPP_MEM_DEVICE) { GPP_HIP(hipMemcpyAsync(hq.data(), quantile, sizeof(float) * nq, hipMemcpyDeviceToHost, stream())); GPP_HIP(hipStreamSynchronize(stream())); }
-    else memcpy(hq.data(), quantile, sizeof(float) * nq);
-    for(long i = 0; i < nq; i++)
-        if(hq[i] < 0 || hq[i] > 1) invalid("calc_quantile: Quantile must be between 0 and 1 inclusive");   // util.cpp:113-115 (NaN passes)
+    bool bad = false;   // util.cpp:113-115 (NaN passes); a device-resident field is checked where it is
+    if(mem & GPP_MEM_DEVICE) bad = quantile_out_of_range(quantile, nq);
+    else for(long i = 0; i < nq; i++) bad = bad || quantile[i] < 0 || quantile[i] > 1;
+    if(bad) invalid("calc_quantile: Quantile must be between 0 and 1 inclusive");
     Fields f; InField q;
     f.bind(array, (size_t)rows * len, out, rows, mem);
     q.bind(quantile, nq, mem);
-    hipLaunchKernelGGL(k_rows_quantile, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), f.in.d, rows, len, q.d, nq == 1 ? 0 : 1, f.o.d);
-    GPP_HIP(hipGetLastError());
+    rows_quantile(f.in.d, rows, len, q.d, nq == 1 ? 0 : 1, f.o.d);
     return f.done();
     GPP_CATCH
 }

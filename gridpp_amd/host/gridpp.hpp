@@ -1290,4 +1290,41 @@ inline float calc_quantile(const vec& array, float quantile) {
     detail::check(gpp_calc_quantile(array.data(), 1, (int)array.size(), &quantile, 1, &out, GPP_MEM_HOST));
     return out;
 }
+namespace detail {
+// The rows of the reference's vec2 may differ in length: each is padded with NaN to the longest.  Every statistic skips invalid
+// values, so the results are the reference's; an empty row gives what an empty vec gives.
+inline vec pad_rows(const vec2& a, size_t& len) {
+    len = 0;
+    for(const auto& r : a) len = std::max(len, r.size());
+    vec f(a.size() * len, MV);
+    for(size_t n = 0; n < a.size(); n++) std::copy(a[n].begin(), a[n].end(), f.begin() + n * len);
+    return f;
+}
+}   // namespace detail
+inline vec calc_statistic(const vec2& array, Statistic statistic) {   // util.cpp:209-216
+    size_t len;
+    const vec f = detail::pad_rows(array, len);
+    vec out(array.size(), MV);
+    detail::check(gpp_calc_statistic(f.data(), (long)array.size(), (int)len, (int)statistic, out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline vec calc_quantile(const vec2& array, float quantile = MV) {   // util.cpp:179-186
+    size_t len;
+    const vec f = detail::pad_rows(array, len);
+    vec out(array.size(), MV);
+    detail::check(gpp_calc_quantile(f.data(), (long)array.size(), (int)len, &quantile, 1, out.data(), GPP_MEM_HOST));
+    return out;
+}
+inline vec2 calc_quantile(const vec3& array, const vec2& quantile) {   // util.cpp:187-208
+    if(quantile.size() != array.size() || (array.size() && quantile[0].size() != array[0].size()))   // compatible_size(vec2, vec3), util.cpp:448-461
+        throw std::invalid_argument("Dimension mismatch between array and quantile");
+    size_t Y, X, E, qy, qx;
+    const vec f = detail::flatten(array, Y, X, E);
+    if(Y == 0 || X == 0) return vec2();
+    if(E == 0) return vec2(Y, vec(X, MV));
+    const vec q = detail::flatten(quantile, qy, qx);
+    vec out(Y * X, MV);
+    detail::check(gpp_calc_quantile(f.data(), (long)(Y * X), (int)E, q.data(), (long)(Y * X), out.data(), GPP_MEM_HOST));
+    return detail::unflatten(out, Y, X);
+}
 }   // namespace gridpp

@@ -453,7 +453,11 @@ int gpp_neighbourhood_quantile_fast(const float* input, int ny, int nx, int ne, 
  * array is [rows][len]; one result per row. */
 /* gridpp::calc_statistic(vec|vec2, statistic) (util.cpp:19-110,208-215) */
 int gpp_calc_statistic(const float* array, long rows, int len, int statistic, float* out, int mem);
-/* gridpp::calc_quantile(vec|vec2, q) and (vec3, vec2 q) (util.cpp:111-207): nq == 1 or nq == rows */
+/* gridpp::calc_quantile(vec|vec2, q) and (vec3, vec2 q) (util.cpp:111-207): nq == 1 or nq == rows, else GPP_EINVAL ("Dimension mismatch between
+ * array and quantile"); then a level below 0 or above 1 is GPP_EINVAL (NaN passes and gives NaN).  `quantile` lives where `array` does: with
+ * GPP_MEM_DEVICE its range is checked on the device and one flag is read back.  Exact order statistics, rows of any length and any number
+ * (csrc/rows_select.hip: selection by keys out of LDS for rows of up to 160 values, a radix select per row beyond, several workgroups per row
+ * for few long rows); the result does not depend on the path. */
 int gpp_calc_quantile(const float* array, long rows, int len, const float* quantile, long nq, float* out, int mem);
 /* gridpp::calc_even_quantiles (util.cpp:261-338) and, with only_valid = 1,
  * gridpp::get_neighbourhood_thresholds (neighbourhood.cpp:243-295) over the n
