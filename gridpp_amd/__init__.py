@@ -13,13 +13,13 @@ library) or torch CUDA tensors (device path: the kernels read/write the tensors'
 HBM directly and a torch tensor is returned).
 """
 import ctypes as C
-import os
-import weakref
 
 import numpy as np
 
 from . import _capi
+from . import _marshal as _m
 from ._capi import check, lib
+from ._marshal import _empty_like_field, _host_empty, _is_dev, _mem, _ndim, _out_shape, _ptr, _shape, _vec, _wants_f64
 
 __version__ = "0.8.0.dev1+mi355x.r1"
 
@@ -110,100 +110,6 @@ def clock():
     return time.time()
 
 
-# ---- argument conversion (the SWIG typemaps of swig/vector.i) ---------------------------------
-def _is_dev(a):
-    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
-
-
-def _wants_f64(*fields):
-    """The large field arrays of a call are float64 numpy arrays: hand every input over as float64 (GPP_HOST_F64, cast on the
-    device) instead of paying numpy's astype on them."""
-    big = [a for a in fields if isinstance(a, np.ndarray) and a.size >= (1 << 20)]
-    return bool(big) and all(a.dtype == np.float64 for a in big)
-
-
-def _vec(a, ndim, name="array", dtype=np.float32):
-    """Any dtype -> C-contiguous float32 (float64 in a GPP_HOST_F64 call); wrong ndim raises like the typemap (swig/vector.i:39-41)."""
-    if _is_dev(a):
-        import torch
-        if a.dim() != ndim:
-            raise RuntimeError("%s must have %d dimensions" % (name, ndim))
-        return a.contiguous().to(torch.float32)
-    arr = np.ascontiguousarray(np.asarray(a), dtype=dtype)
-    if arr.ndim != ndim:
-        if arr.size == 0 and arr.ndim <= ndim:   # e.g. [] or [[]]
-            return arr.reshape((0,) * ndim)
-        raise RuntimeError("%s must have %d dimensions, got %d" % (name, ndim, arr.ndim))
-    return arr
-
-
-def _ptr(a):
-    if a is None:
-        return None
-    if _is_dev(a):
-        return C.c_void_p(a.data_ptr())
-    return C.c_void_p(a.ctypes.data)
-
-
-def _shape(a):
-    return tuple(a.shape)
-
-
-class _PinnedPool:
-    """Result arrays of 1 MiB and more live in page-locked host memory (gpp_host_alloc): the device-to-host copy is then one
-    DMA transfer.  Buffers return to a free list when their numpy array dies (up to 2 GiB are kept for reuse)."""
-    MIN_BYTES, KEEP_BYTES = 1 << 20, 2 << 30
-
-    def __init__(self):
-        self.free, self.kept = {}, 0
-
-    def take(self, nbytes):
-        lst = self.free.get(nbytes)
-        if lst:
-            self.kept -= nbytes
-            return lst.pop()
-        ptr = C.c_void_p()
-        if lib().gpp_host_alloc(nbytes, C.byref(ptr)) != _capi.GPP_OK or not ptr.value:
-            return None
-        return ptr.value
-
-    def give(self, ptr, nbytes):
-        if self.kept + nbytes <= self.KEEP_BYTES:
-            self.free.setdefault(nbytes, []).append(ptr)
-            self.kept += nbytes
-        else:
-            lib().gpp_host_free(C.c_void_p(ptr))
-
-
-_pinned = _PinnedPool()
-
-
-def _host_empty(shape):
-    n = int(np.prod(shape))
-    if 4 * n < _PinnedPool.MIN_BYTES or os.environ.get("GPP_PAGEABLE_RESULTS"):
-        return np.empty(shape, dtype=np.float32)
-    ptr = _pinned.take(4 * n)
-    if ptr is None:
-        return np.empty(shape, dtype=np.float32)
-    buf = (C.c_float * n).from_address(ptr)
-    weakref.finalize(buf, _pinned.give, ptr, 4 * n)
-    return np.frombuffer(buf, dtype=np.float32).reshape(shape)     # the array keeps `buf` alive
-
-
-def _empty_like_field(shape, like):
-    if _is_dev(like):
-        import torch
-        return torch.empty(shape, dtype=torch.float32, device=like.device)
-    return _host_empty(shape)
-
-
-def _mem(*arrays):
-    dev = [_is_dev(a) for a in arrays if a is not None]
-    if any(dev) and not all(dev):
-        raise ValueError("either all field arguments are torch CUDA tensors or none is")
-    return _capi.MEM_DEVICE if dev and all(dev) else _capi.MEM_HOST
-
-
 # ---- Point / KDTree / Points / Grid -----------------------------------------------------------
 class Point:
     """include/gridpp.h:1713-1743, src/api/point.cpp:5-26"""
@@ -240,15 +146,6 @@ def _is_big_f64(*arrays):
     """float64 numpy coordinate arrays of a large set: handed to the C-ABI as they are and cast to float32 on the device
     (numpy's astype on 16 M doubles takes longer than building the whole Grid)"""
     return all(isinstance(a, np.ndarray) and a.dtype == np.float64 for a in arrays) and arrays[0].size >= (1 << 16)
-
-
-def _vec64(a, ndim, name):
-    arr = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
-    if arr.ndim != ndim:
-        if arr.size == 0 and arr.ndim <= ndim:
-            return arr.reshape((0,) * ndim)
-        raise RuntimeError("%s must have %d dimensions, got %d" % (name, ndim, arr.ndim))
-    return arr
 
 
 class _PointSet:
@@ -302,9 +199,8 @@ class Points(_PointSet):
 
     def __init__(self, lats=(), lons=(), elevs=(), lafs=(), type=Geodetic):
         f64 = _is_big_f64(lats, lons)
-        vec = _vec64 if f64 else _vec
-        lats, lons = vec(lats, 1, "lats"), vec(lons, 1, "lons")
-        elevs, lafs = vec(elevs, 1, "elevs"), vec(lafs, 1, "lafs")
+        lats, lons = _m.field(lats, 1, "lats", f64), _m.field(lons, 1, "lons", f64)
+        elevs, lafs = _m.field(elevs, 1, "elevs", f64), _m.field(lafs, 1, "lafs", f64)
         n = lats.size
         if lons.size != n:
             raise ValueError("Cannot create points with unequal lat and lon sizes")
@@ -438,6 +334,7 @@ class KDTree(Points):
         return float(np.float32(6.378137e6 * np.sqrt(np.float64(dx2 + dy2))))
 
 
+# SWIG's flat names of the static KDTree methods (the reference's tests use them: tests/test_kdtree.py:56-58,111-112)
 KDTree_calc_distance = KDTree.calc_distance
 KDTree_calc_distance_fast = KDTree.calc_distance_fast
 KDTree_calc_straight_distance = KDTree.calc_straight_distance
@@ -450,9 +347,8 @@ class Grid(_PointSet):
 
     def __init__(self, lats=((),), lons=((),), elevs=((),), lafs=((),), type=Geodetic):
         f64 = _is_big_f64(lats, lons)
-        vec = _vec64 if f64 else _vec
-        lats, lons = vec(lats, 2, "lats"), vec(lons, 2, "lons")
-        elevs, lafs = vec(elevs, 2, "elevs"), vec(lafs, 2, "lafs")
+        lats, lons = _m.field(lats, 2, "lats", f64), _m.field(lons, 2, "lons", f64)
+        elevs, lafs = _m.field(elevs, 2, "elevs", f64), _m.field(lafs, 2, "lafs", f64)
         if lats.shape != lons.shape:
             raise ValueError("lats and lons must have the same shape")
         ny, nx = lats.shape
@@ -518,14 +414,6 @@ class Grid(_PointSet):
 
     def to_points(self):   # grid.cpp:131-145
         return Points(self._field(0), self._field(1), self._field(2), self._field(3), self._type)
-
-
-# SWIG's flat names of the static KDTree methods (the reference's tests use them: tests/test_kdtree.py:56-58,111-112)
-KDTree_calc_distance = KDTree.calc_distance
-KDTree_calc_distance_fast = KDTree.calc_distance_fast
-KDTree_calc_straight_distance = KDTree.calc_straight_distance
-KDTree_deg2rad = KDTree.deg2rad
-KDTree_rad2deg = KDTree.rad2deg
 
 
 # ---- structure functions (include/gridpp.h:2069-2343, src/api/structure.cpp) -----------------------
@@ -600,7 +488,7 @@ def _scalar_structure(obj, kind, h, v, w, hmax):
 
 
 def _spatial_structure(obj, kind, grid, h, v, w, min_rho):
-    h, v, w = _vec(h, 2, "h"), _vec(v, 2, "v"), _vec(w, 2, "w")
+    h, v, w = _m.field(h, 2, "h"), _m.field(v, 2, "v"), _m.field(w, 2, "w")
     if h.shape == (1, 1) and v.shape == (1, 1) and w.shape == (1, 1):   # not spatial (structure.cpp:174-176)
         obj._s = _capi.gpp_structure(kind, float(h[0, 0]), float(v[0, 0]), float(w[0, 0]), float(min_rho), 0, 0, 0.0, 0.0, 0, None)
         return
@@ -711,30 +599,23 @@ def _oi_common(bg, background, bvariance, points, pobs, obs_variance, pbackgroun
         raise ValueError("Both background and observations points must be of same coordinate type (lat/lon or x/y)")
     nd = 2 if isinstance(bg, Grid) else 1
     f64 = _wants_f64(background, bvariance)
-    dt = np.float64 if f64 else np.float32
-    background = _vec(background, nd, "background", dt)
-    shape = tuple(bg.size()) if nd == 2 else (bg.size(),)
+    background = _m.field(background, nd, "background", f64)
+    shape = _out_shape(bg)
     if _shape(background) != shape:
         raise ValueError("input field %s is not the same size as the grid %s" % (_shape(background), shape))
-    if bvariance is not None:
-        bvariance = _vec(bvariance, nd, "bvariance", dt)
-        if _shape(bvariance) != shape:
-            raise ValueError("Input bvariance is not the same size as the grid")
+    bvariance = _m.field(bvariance, nd, "bvariance", f64)
+    if bvariance is not None and _shape(bvariance) != shape:
+        raise ValueError("Input bvariance is not the same size as the grid")
     S = points.size()
-    pobs, obs_variance, pbackground = _vec(pobs, 1, "obs", dt), _vec(obs_variance, 1, "variance", dt), _vec(pbackground, 1, "background_at_points", dt)
+    pobs, obs_variance = _m.field(pobs, 1, "obs", f64), _m.field(obs_variance, 1, "variance", f64)
+    pbackground = _m.field(pbackground, 1, "background_at_points", f64)
     for name, a in (("Observations", pobs), ("Ratios", obs_variance), ("Background", pbackground)):
         if _shape(a)[0] != S:
             raise ValueError("%s (%d) and points (%d) size mismatch" % (name, _shape(a)[0], S))
-    if bvariance_at_points is not None:
-        bvariance_at_points = _vec(bvariance_at_points, 1, "bvariance_at_points", dt)
-        if _shape(bvariance_at_points)[0] != S:
-            raise ValueError("Background variance and points size mismatch")
-    mem = _mem(background, bvariance, pobs, obs_variance, pbackground, bvariance_at_points)
-    if mem == _capi.MEM_DEVICE:
-        import torch
-        torch.cuda.current_stream().synchronize()   # producers of the inputs ran on torch's stream
-    elif f64:
-        mem |= _capi.HOST_F64
+    bvariance_at_points = _m.field(bvariance_at_points, 1, "bvariance_at_points", f64)
+    if bvariance_at_points is not None and _shape(bvariance_at_points)[0] != S:
+        raise ValueError("Background variance and points size mismatch")
+    mem = _m.flags(f64, background, bvariance, pobs, obs_variance, pbackground, bvariance_at_points)
     out = _empty_like_field(shape, background)
     var = _empty_like_field(shape, background) if want_variance else None
     if deferred:
@@ -853,48 +734,40 @@ def obs_index_layout(points):
 
 
 # ---- nearest (src/api/nearest.cpp:124-144) ----------------------------------------------------------
-def nearest(igrid, opoints, values):
-    """All eight overloads of src/api/nearest.cpp: Grid|Points -> Grid|Points, with or without a leading time dimension."""
+def _interpolate_levels(entry, igrid, opoints, values, rank_message, pad_empty):
+    """The body nearest and bilinear share: values on igrid, with or without a leading time dimension -> the same on opoints.
+    pad_empty: an empty host array of too few dimensions counts as one of the right number ([] on a Grid is (0, 0))."""
     nd = 2 if isinstance(igrid, Grid) else 1
-    if _is_dev(values):
-        import torch
-        values = values.contiguous().to(torch.float32)
-    else:
-        values = np.ascontiguousarray(np.asarray(values), dtype=np.float64 if _wants_f64(values) else np.float32)
-        if values.size == 0 and values.ndim < nd:
-            values = values.reshape((0,) * nd)
+    f64 = _wants_f64(values)
+    values = _m.field(values, f64=f64)
+    if pad_empty and not _is_dev(values) and values.size == 0 and values.ndim < nd:
+        values = values.reshape((0,) * nd)
     shp = _shape(values)
     if len(shp) not in (nd, nd + 1):
-        raise RuntimeError("values must have %d or %d dimensions" % (nd, nd + 1))
+        raise RuntimeError(rank_message)
     levels = len(shp) == nd + 1
-    ishape = tuple(igrid.size()) if nd == 2 else (igrid.size(),)
-    if nd == 2:    # src/api/util.cpp:427-432
+    if nd == 2:    # src/api/util.cpp:427-432: no rows (2-D) / no time levels or no rows (3-D) passes the size check
         empty = shp[0] == 0 or (levels and shp[1] == 0)
     else:          # util.cpp:433-438: a vec2 with no time levels passes, a vec must match
         empty = levels and shp[0] == 0
-    if not empty and tuple(shp[-nd:]) != ishape:
+    if not empty and tuple(shp[-nd:]) != _out_shape(igrid):
         raise ValueError("Grid size is not the same as values" if nd == 2 else "Points size is not the same as values")
-    oshape = tuple(opoints.size()) if isinstance(opoints, Grid) else (opoints.size(),)
     nt = shp[0] if levels else 1
-    lead = (nt,) if levels else ()
-    out = _empty_like_field(lead + oshape, values)
-    if int(np.prod(lead + oshape)) == 0:
-        return out
+    oshape = ((nt,) if levels else ()) + _out_shape(opoints)
+    if int(np.prod(oshape)) == 0:
+        return _empty_like_field(oshape, values)
     if igrid._n and empty:
-        raise ValueError("Grid size is not the same as values")
-    mem = _mem(values)
-    _sync_if_dev(mem)
-    if not _is_dev(values) and values.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    check(lib().gpp_nearest_levels(igrid._h, opoints._h, _ptr(values), nt, _ptr(out), mem))
-    return out
+        raise ValueError("Grid size is not the same as values")   # nothing to read from (the reference would index past the end)
+    return _m.run(entry, igrid._h, opoints._h, _ptr(values), nt, out_shape=oshape, like=values, mem=_m.flags(f64, values))
+
+
+def nearest(igrid, opoints, values):
+    """All eight overloads of src/api/nearest.cpp: Grid|Points -> Grid|Points, with or without a leading time dimension."""
+    nd = 2 if isinstance(igrid, Grid) else 1
+    return _interpolate_levels(lib().gpp_nearest_levels, igrid, opoints, values, "values must have %d or %d dimensions" % (nd, nd + 1), True)
 
 
 # ---- count / gridding (include/gridpp.h:938-1010, src/api/count.cpp, src/api/gridding.cpp) -------------
-def _out_shape(o):
-    return tuple(o.size()) if isinstance(o, Grid) else (o.size(),)
-
-
 def count(ipoints, opoints, radius):
     """Number of points of `ipoints` (Grid or Points) within `radius` of every location of `opoints` (count.cpp:6-66)."""
     out = np.empty(_out_shape(opoints), np.float32)
@@ -926,13 +799,7 @@ def staticcorr_points(points, knots, structure, max_points):
 
 
 def _point_values(ipoints, values):
-    if _is_dev(values):
-        import torch
-        values = values.contiguous().to(torch.float32)
-        if values.dim() != 1:
-            raise RuntimeError("values must have 1 dimension")
-    else:
-        values = _vec(values, 1, "values")
+    values = _m.field(values, 1, "values", dev_message="values must have 1 dimension")
     if _shape(values)[0] != ipoints.size():
         raise ValueError("Points size is not the same as values")
     return values
@@ -945,12 +812,10 @@ def gridding(grid, points, values, radius, min_num, statistic):
         raise ValueError("radius must be >= 0")
     if min_num < 0:
         raise ValueError("min_num must be >= 0")
-    out = _empty_like_field(_out_shape(grid), values)
-    if int(np.prod(_out_shape(grid))):
-        mem = _mem(values)
-        _sync_if_dev(mem)
-        check(lib().gpp_gridding(grid._h, points._h, _ptr(values), float(radius), int(min_num), int(statistic), _ptr(out), mem))
-    return out
+    if int(np.prod(_out_shape(grid))) == 0:
+        return _empty_like_field(_out_shape(grid), values)
+    return _m.run(lib().gpp_gridding, grid._h, points._h, _ptr(values), float(radius), int(min_num), int(statistic),
+                  out_shape=_out_shape(grid), like=values, mem=_m.flags(False, values))
 
 
 def gridding_nearest(grid, points, values, min_num, statistic):
@@ -958,12 +823,10 @@ def gridding_nearest(grid, points, values, min_num, statistic):
     values = _point_values(points, values)
     if min_num < 0:
         raise ValueError("min_num must be >= 0")
-    out = _empty_like_field(_out_shape(grid), values)
-    if int(np.prod(_out_shape(grid))) or points.size():
-        mem = _mem(values)
-        _sync_if_dev(mem)
-        check(lib().gpp_gridding_nearest(grid._h, points._h, _ptr(values), int(min_num), int(statistic), _ptr(out), mem))
-    return out
+    if int(np.prod(_out_shape(grid))) == 0 and not points.size():
+        return _empty_like_field(_out_shape(grid), values)
+    return _m.run(lib().gpp_gridding_nearest, grid._h, points._h, _ptr(values), int(min_num), int(statistic),
+                  out_shape=_out_shape(grid), like=values, mem=_m.flags(False, values))
 
 
 # ---- fill / doping / neighbourhood_search / calc_gradient -----------------------------------------------
@@ -971,7 +834,7 @@ MinMax, LinearRegression = 0, 10   # include/gridpp.h:126-129
 
 
 def _grid_field(igrid, values, what="values"):
-    values = _vec(values, 2, what)
+    values = _m.field(values, 2, what)
     shp = _shape(values)
     if shp[0] != 0 and tuple(shp) != tuple(igrid.size()):       # src/api/util.cpp:427-429
         raise ValueError("Grid size is not the same as " + what)
@@ -984,42 +847,34 @@ def fill(igrid, input, points, radii, value, outside):
     radii = np.ascontiguousarray(np.asarray(radii, np.float32).ravel())
     if radii.size != points.size():
         raise ValueError("Points size is not the same as radii size")
-    out = _empty_like_field(_shape(input), input)
-    if int(np.prod(_shape(input))):
-        mem = _mem(input)
-        _sync_if_dev(mem)
-        check(lib().gpp_fill(igrid._h, _ptr(input), points._h, _ptr(radii), float(value), int(bool(outside)), _ptr(out), mem))
-    return out
+    if int(np.prod(_shape(input))) == 0:
+        return _empty_like_field(_shape(input), input)
+    return _m.run(lib().gpp_fill, igrid._h, _ptr(input), points._h, _ptr(radii), float(value), int(bool(outside)),
+                  out_shape=_shape(input), like=input, mem=_m.flags(False, input))
 
 
 def fill_missing(values):
     """src/api/fill.cpp:43-134"""
     f64 = _wants_f64(values)
-    values = _vec(values, 2, "values", np.float64 if f64 else np.float32)
-    out = _empty_like_field(_shape(values), values)
+    values = _m.field(values, 2, "values", f64)
     ny, nx = _shape(values)
-    if ny * nx:
-        mem = _mem(values)
-        _sync_if_dev(mem)
-        check(lib().gpp_fill_missing(_ptr(values), ny, nx, _ptr(out), mem | (_capi.HOST_F64 if f64 else 0)))
-    return out
+    if ny * nx == 0:
+        return _empty_like_field((ny, nx), values)
+    return _m.run(lib().gpp_fill_missing, _ptr(values), ny, nx, out_shape=(ny, nx), like=values, mem=_m.flags(f64, values))
 
 
 def _doping(igrid, background, points, observations, halfwidth, radii, max_elev_diff):
     background = _grid_field(igrid, background, "observations")
-    observations = _vec(observations, 1, "observations")
+    observations = _m.field(observations, 1, "observations")
     if _shape(observations)[0] != points.size():
         raise ValueError("Points size is not the same as observations size")
     per = halfwidth if halfwidth is not None else radii
     if per.size != points.size():
         raise ValueError("Points size is not the same as %s size" % ("halfwidth" if halfwidth is not None else "radii"))
-    out = _empty_like_field(_shape(background), background)
-    if int(np.prod(_shape(background))):
-        mem = _mem(background, observations)
-        _sync_if_dev(mem)
-        check(lib().gpp_doping(igrid._h, _ptr(background), points._h, _ptr(observations), _ptr(halfwidth), _ptr(radii), float(max_elev_diff),
-                               _ptr(out), mem))
-    return out
+    if int(np.prod(_shape(background))) == 0:
+        return _empty_like_field(_shape(background), background)
+    return _m.run(lib().gpp_doping, igrid._h, _ptr(background), points._h, _ptr(observations), _ptr(halfwidth), _ptr(radii),
+                  float(max_elev_diff), out_shape=_shape(background), like=background, mem=_m.flags(False, background, observations))
 
 
 def doping_square(igrid, background, points, observations, halfwidth, max_elev_diff=MV):
@@ -1035,8 +890,7 @@ def doping_circle(igrid, background, points, observations, radii, max_elev_diff=
 def neighbourhood_search(array, search_array, halfwidth, search_target_min, search_target_max, search_delta, apply_array=None):
     """src/api/neighbourhood_search.cpp:7-113"""
     f64 = _wants_f64(array, search_array)
-    dt = np.float64 if f64 else np.float32
-    array, search_array = _vec(array, 2, "array", dt), _vec(search_array, 2, "search_array", dt)
+    array, search_array = _m.field(array, 2, "array", f64), _m.field(search_array, 2, "search_array", f64)
     if _shape(array) != _shape(search_array):
         raise ValueError("search_array must either be the same size as array")
     if search_target_min > search_target_max:
@@ -1045,30 +899,22 @@ def neighbourhood_search(array, search_array, halfwidth, search_target_min, sear
         raise ValueError("halfwidth must be positive")
     ap = None
     if apply_array is not None and (apply_array.numel() if _is_dev(apply_array) else np.size(apply_array)) > 0:
-        if _is_dev(apply_array):
-            import torch
-            ap = apply_array.contiguous().to(torch.int32)
-        else:
-            ap = np.ascontiguousarray(np.asarray(apply_array).astype(np.int32))
+        ap = _m.field(apply_array, dtype=np.int32)
         # (the reference indexes apply_array[y][x] for every cell whatever its size; anything but a full-size mask reads out of bounds there)
         if tuple(ap.shape) != _shape(array):
             raise ValueError("apply_array must either be empty or same size as array")
-    out = _empty_like_field(_shape(array), array)
     ny, nx = _shape(array)
-    if ny * nx:
-        mem = _mem(array, search_array, ap)
-        _sync_if_dev(mem)
-        check(lib().gpp_neighbourhood_search(_ptr(array), _ptr(search_array), ny, nx, int(halfwidth), float(search_target_min),
-                                             float(search_target_max), float(search_delta), _ptr(ap), _ptr(out),
-                                             mem | (_capi.HOST_F64 if f64 and mem == _capi.MEM_HOST else 0)))
-    return out
+    if ny * nx == 0:
+        return _empty_like_field((ny, nx), array)
+    return _m.run(lib().gpp_neighbourhood_search, _ptr(array), _ptr(search_array), ny, nx, int(halfwidth), float(search_target_min),
+                  float(search_target_max), float(search_delta), _ptr(ap), out_shape=(ny, nx), like=array,
+                  mem=_m.flags(f64, array, search_array, ap))
 
 
 def calc_gradient(base, values, gradient_type, halfwidth, num_min=2, min_range=MV, default_gradient=0):
     """src/api/calc_gradient.cpp:7-126"""
     f64 = _wants_f64(base, values)
-    dt = np.float64 if f64 else np.float32
-    base, values = _vec(base, 2, "base", dt), _vec(values, 2, "values", dt)
+    base, values = _m.field(base, 2, "base", f64), _m.field(values, 2, "values", f64)
     if halfwidth <= 0:
         raise ValueError("Halwidth cannot be <= 0; must be positive integer")
     if is_valid(min_range) and min_range < 0:
@@ -1079,13 +925,9 @@ def calc_gradient(base, values, gradient_type, halfwidth, num_min=2, min_range=M
         raise ValueError("base input has no size")
     if _shape(base) != _shape(values):
         raise ValueError("base is not the same size as values")
-    out = _empty_like_field(_shape(base), base)
     ny, nx = _shape(base)
-    mem = _mem(base, values)
-    _sync_if_dev(mem)
-    check(lib().gpp_calc_gradient(_ptr(base), _ptr(values), ny, nx, int(gradient_type), int(halfwidth), int(num_min), float(min_range),
-                                  float(default_gradient), _ptr(out), mem | (_capi.HOST_F64 if f64 and mem == _capi.MEM_HOST else 0)))
-    return out
+    return _m.run(lib().gpp_calc_gradient, _ptr(base), _ptr(values), ny, nx, int(gradient_type), int(halfwidth), int(num_min),
+                  float(min_range), float(default_gradient), out_shape=(ny, nx), like=base, mem=_m.flags(f64, base, values))
 
 
 # ---- bilinear (include/gridpp.h:902-930, src/api/bilinear.cpp:26-135) ---------------------------------
@@ -1093,32 +935,7 @@ def bilinear(igrid, opoints, values):
     """values (Y, X) -> output shaped like opoints; values (T, Y, X) -> (T,) + that shape."""
     if not isinstance(igrid, Grid):
         raise TypeError("bilinear: the input must be a Grid")
-    if _is_dev(values):
-        import torch
-        values = values.contiguous().to(torch.float32)
-    else:
-        values = np.ascontiguousarray(np.asarray(values), dtype=np.float64 if _wants_f64(values) else np.float32)
-    shp = _shape(values)
-    if len(shp) not in (2, 3):
-        raise RuntimeError("bilinear: values must be 2-D or 3-D")
-    # src/api/util.cpp:427-432: no rows (2-D) / no time levels or no rows (3-D) passes the size check
-    empty = shp[0] == 0 or (len(shp) == 3 and shp[1] == 0)
-    if not empty and tuple(shp[-2:]) != tuple(igrid.size()):
-        raise ValueError("Grid size is not the same as values")
-    oshape = tuple(opoints.size()) if isinstance(opoints, Grid) else (opoints.size(),)
-    nt = shp[0] if len(shp) == 3 else 1
-    lead = (nt,) if len(shp) == 3 else ()
-    out = _empty_like_field(lead + oshape, values)
-    if int(np.prod(lead + oshape)) == 0:
-        return out
-    if igrid._n and empty:
-        raise ValueError("Grid size is not the same as values")   # nothing to read from (the reference would index past the end)
-    mem = _mem(values)
-    _sync_if_dev(mem)
-    if not _is_dev(values) and values.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    check(lib().gpp_bilinear(igrid._h, opoints._h, _ptr(values), nt, _ptr(out), mem))
-    return out
+    return _interpolate_levels(lib().gpp_bilinear, igrid, opoints, values, "bilinear: values must be 2-D or 3-D", False)
 
 
 # ---- downscaling, simple_gradient, full_gradient (include/gridpp.h:132-135,844-871,1017-1098) ---------------------------
@@ -1126,29 +943,21 @@ Nearest, Bilinear = 0, 1   # include/gridpp.h:132-135
 
 
 def _downscale_setup(name, igrid, output, ivalues, fields=()):
-    """Checks shared by the downscalers -> (values, other fields, ndim, output shape, empty, f64).  Fields are float32 (float64 in a
-    GPP_HOST_F64 call) arrays or float32 device tensors; None stays None."""
+    """Checks shared by the downscalers -> (values, other fields, ndim, output shape, empty, f64).  Fields are float32 arrays (float64
+    where f64) or float32 device tensors; None stays None."""
     if not isinstance(igrid, Grid):
         raise TypeError("%s: the input must be a Grid" % name)
     if not isinstance(output, (Grid, Points)):
         raise TypeError("%s: the output must be a Grid or Points" % name)
     f64 = _wants_f64(ivalues, *fields)
-
-    def conv(a):
-        if a is None:
-            return None
-        if _is_dev(a):
-            import torch
-            return a.contiguous().to(torch.float32)
-        return np.ascontiguousarray(np.asarray(a), dtype=np.float64 if f64 else np.float32)
-    values = conv(ivalues)
+    values = _m.field(ivalues, f64=f64)
     shp = _shape(values)
     if len(shp) not in (2, 3):
         raise RuntimeError("%s: values must be 2-D or 3-D" % name)
     # src/api/util.cpp:427-432: no rows (2-D) / no time levels or no rows (3-D) passes the size check
     empty = shp[0] == 0 or (len(shp) == 3 and shp[1] == 0)
     lead = (shp[0],) if len(shp) == 3 else ()
-    return values, [conv(a) for a in fields], len(shp), lead + _out_shape(output), empty, f64
+    return values, [_m.field(a, f64=f64) for a in fields], len(shp), lead + _out_shape(output), empty, f64
 
 
 def _downscaler(downscaler):
@@ -1170,17 +979,14 @@ def downscaling(igrid, output, ivalues, downscaler):
 def _gradient_call(entry, igrid, output, values, fields, oshape, empty, f64, downscaler, *args):
     """runs gpp_simple_gradient / gpp_full_gradient once the overload's checks have passed; fields = the present gradients"""
     downscaler = _downscaler(downscaler)
-    mem = _mem(values, *fields)
+    _mem(values, *fields)   # (mixed memory is refused whatever the shapes)
     if int(np.prod(oshape)) == 0:
         return _empty_like_field(oshape, values)
     if igrid._n and empty:
         raise ValueError("Grid size is not the same as values")   # nothing to read from (the reference would index past the end)
-    out = _empty_like_field(oshape, values)
-    _sync_if_dev(mem)
     nt = oshape[0] if len(_shape(values)) == 3 else 1
-    check(entry(igrid._h, output._h, _ptr(values), nt, *args, downscaler, _ptr(out),
-                mem | (_capi.HOST_F64 if f64 and mem == _capi.MEM_HOST else 0)))
-    return out
+    return _m.run(entry, igrid._h, output._h, _ptr(values), nt, *args, downscaler, out_shape=oshape, like=values,
+                  mem=_m.flags(f64, values, *fields))
 
 
 def simple_gradient(igrid, output, ivalues, elev_gradient, downscaler=Nearest):
@@ -1236,13 +1042,8 @@ def _ens_setup(name, igrid, ogrid, cubes, threshold, comparison_operator):
     if not isinstance(igrid, Grid) or not isinstance(ogrid, Grid):
         raise TypeError("%s: igrid and ogrid must be Grids" % name)
     f64 = _wants_f64(*cubes)
-
-    def conv(a, ndim, what):
-        if _is_dev(a):
-            return _vec(a, ndim, what)
-        return _vec(a, ndim, what, np.float64 if f64 else np.float32)
-    cubes = [conv(a, 3, "values") for a in cubes]
-    threshold = conv(threshold, 2, "threshold")
+    cubes = [_m.field(a, 3, "values", f64) for a in cubes]
+    threshold = _m.field(threshold, 2, "threshold", f64)
     _mem(threshold, *cubes)
     shp = _shape(cubes[0])
     if any(_shape(c) != shp for c in cubes[1:]):
@@ -1259,15 +1060,10 @@ def _ens_setup(name, igrid, ogrid, cubes, threshold, comparison_operator):
 
 
 def _ens_call(entry, igrid, ogrid, cubes, ne, threshold, f64, *args):
-    out = _empty_like_field(tuple(ogrid.size()), threshold)
     if ogrid._n == 0:
-        return out
-    mem = _mem(threshold, *cubes)
-    _sync_if_dev(mem)
-    if f64 and mem == _capi.MEM_HOST:
-        mem |= _capi.HOST_F64
-    check(entry(igrid._h, ogrid._h, *[_ptr(c) for c in cubes], int(ne), _ptr(threshold), *args, _ptr(out), mem))
-    return out
+        return _empty_like_field(_out_shape(ogrid), threshold)
+    return _m.run(entry, igrid._h, ogrid._h, *[_ptr(c) for c in cubes], int(ne), _ptr(threshold), *args, out_shape=_out_shape(ogrid),
+                  like=threshold, mem=_m.flags(f64, threshold, *cubes))
 
 
 def downscale_probability(igrid, ogrid, ivalues, threshold, comparison_operator):
@@ -1310,23 +1106,16 @@ def smart(igrid, ogrid, ivalues, num, structure):
     if not isinstance(igrid, Grid) or not isinstance(ogrid, Grid):
         raise TypeError("smart: igrid and ogrid must be Grids")
     st = _structure(structure)
-    if _is_dev(ivalues):
-        values = _vec(ivalues, 2, "values")
-    else:
-        values = _vec(ivalues, 2, "values", np.float64 if _wants_f64(ivalues) else np.float32)
+    f64 = _wants_f64(ivalues)
+    values = _m.field(ivalues, 2, "values", f64)
     if igrid._n and _shape(values) != tuple(igrid.size()):
         raise ValueError("Grid size is not the same as values")
     if igrid.get_coordinate_type() != ogrid.get_coordinate_type():
         raise ValueError("Coordinate types must be the same")
-    out = _empty_like_field(tuple(ogrid.size()), values)
     if ogrid._n == 0:
-        return out
-    mem = _mem(values)
-    _sync_if_dev(mem)
-    if not _is_dev(values) and values.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    check(lib().gpp_smart(igrid._h, ogrid._h, _ptr(values), int(num), st, _ptr(out), mem))
-    return out
+        return _empty_like_field(_out_shape(ogrid), values)
+    return _m.run(lib().gpp_smart, igrid._h, ogrid._h, _ptr(values), int(num), st, out_shape=_out_shape(ogrid), like=values,
+                  mem=_m.flags(f64, values))
 
 
 # ---- local_distribution_correction (include/gridpp.h:467-512) ---------------------------------------------------------------
@@ -1346,13 +1135,12 @@ def local_distribution_correction(bgrid, background, points, pobs, pbackground, 
     fields = (background, pobs, pbackground)
     dev = all(_is_dev(a) for a in fields)
     f64 = not dev and all(isinstance(a, np.ndarray) and a.dtype == np.float64 for a in fields)
-    dt = np.float64 if f64 else np.float32
     nd = _ndim(pobs)
     if nd not in (1, 2) or _ndim(pbackground) != nd:
         raise ValueError("pobs and pbackground must both be 1-D (points) or both 2-D (times, points)")
-    background = _vec(background, 2, "background", dt)
-    pobs, pbackground = _vec(pobs, nd, "pobs", dt), _vec(pbackground, nd, "pbackground", dt)
-    mem = _mem(background, pobs, pbackground)
+    background = _m.field(background, 2, "background", f64)
+    pobs, pbackground = _m.field(pobs, nd, "pobs", f64), _m.field(pbackground, nd, "pbackground", f64)
+    _mem(background, pobs, pbackground)   # (mixed memory is refused before the shapes are compared)
     if nd == 1:
         pobs, pbackground = pobs.reshape(1, -1), pbackground.reshape(1, -1)   # :27-31
     so, sb = _shape(pobs), _shape(pbackground)
@@ -1369,24 +1157,16 @@ def local_distribution_correction(bgrid, background, points, pobs, pbackground, 
     min_quantile, max_quantile = float(min_quantile), float(max_quantile)
     if not (np.isfinite(min_quantile) and np.isfinite(max_quantile) and 0 <= min_quantile <= max_quantile <= 1):
         raise ValueError("min_quantile and max_quantile must be finite with 0 <= min_quantile <= max_quantile <= 1")
-    out = _empty_like_field(tuple(bgrid.size()), background)
     if bgrid._n == 0:
-        return out
-    _sync_if_dev(mem)
-    if f64 and mem == _capi.MEM_HOST:
-        mem |= _capi.HOST_F64
-    check(lib().gpp_local_distribution_correction(bgrid._h, _ptr(background), points._h, _ptr(pobs), _ptr(pbackground), so[0], st,
-                                                  min_quantile, max_quantile, int(min_points), _ptr(out), mem))
-    return out
+        return _empty_like_field(_out_shape(bgrid), background)
+    return _m.run(lib().gpp_local_distribution_correction, bgrid._h, _ptr(background), points._h, _ptr(pobs), _ptr(pbackground), so[0], st,
+                  min_quantile, max_quantile, int(min_points), out_shape=_out_shape(bgrid), like=background,
+                  mem=_m.flags(f64, background, pobs, pbackground))
 
 
 # ---- calibration by a curve (include/gridpp.h:79-85,731-789,1549-1557) -----------------------------------------------------
 OneToOne, MeanSlope, NearestSlope, Zero, Unchanged = 0, 10, 20, 30, 40   # include/gridpp.h:79-85
 _POLICIES = (OneToOne, MeanSlope, NearestSlope, Zero, Unchanged)
-
-
-def _ndim(a):
-    return a.dim() if _is_dev(a) else np.ndim(a)
 
 
 def _host_curve(a):
@@ -1413,21 +1193,13 @@ def _values_call(entry, values, *args):
     nd = _ndim(values)
     if nd not in (1, 2):
         raise RuntimeError("input must be a scalar or have 1 or 2 dimensions, got %d" % nd)
-    if _is_dev(values):
-        v = _vec(values, nd, "input")
-    else:
-        v = np.ascontiguousarray(np.asarray(values), dtype=np.float64 if _wants_f64(values) else np.float32)
+    f64 = _wants_f64(values)
+    v = _m.field(values, f64=f64)
     shp = _shape(v)
     n = int(np.prod(shp))
     if n == 0:
         return np.zeros(shp, np.float32)
-    mem = _mem(v)
-    _sync_if_dev(mem)
-    if not _is_dev(v) and v.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    out = _empty_like_field(shp, v)
-    check(entry(_ptr(v), n, *args, _ptr(out), mem))
-    return out
+    return _m.run(entry, _ptr(v), n, *args, out_shape=shp, like=v, mem=_m.flags(f64, v))
 
 
 def apply_curve(fcst, curve_ref, curve_fcst, policy_below, policy_above):
@@ -1455,13 +1227,8 @@ def _apply_curve_field(fcst, curve_ref, curve_fcst, policy_below, policy_above):
     if _ndim(fcst) != 2:
         raise ValueError("Fcst and curve_ref dimension sizes mismatch")
     f64 = _wants_f64(fcst, curve_ref, curve_fcst)
-
-    def conv(a, ndim, what):
-        if _is_dev(a):
-            return _vec(a, ndim, what)
-        return _vec(a, ndim, what, np.float64 if f64 else np.float32)
-    v, cr, cf = conv(fcst, 2, "fcst"), conv(curve_ref, 3, "curve_ref"), conv(curve_fcst, 3, "curve_fcst")
-    mem = _mem(v, cr, cf)
+    v, cr, cf = _m.field(fcst, 2, "fcst", f64), _m.field(curve_ref, 3, "curve_ref", f64), _m.field(curve_fcst, 3, "curve_fcst", f64)
+    _mem(v, cr, cf)   # (mixed memory is refused before the shapes are compared)
     if _shape(cr) != _shape(cf):   # curve.cpp:111-116
         raise ValueError("curve_ref and curve_fcst dimension sizes mismatch")
     if _shape(v) != _shape(cr)[:2]:
@@ -1473,12 +1240,8 @@ def _apply_curve_field(fcst, curve_ref, curve_fcst, policy_below, policy_above):
         raise ValueError("Unknown extrapolation policy")
     if ny * nx == 0:
         return np.zeros((ny, nx), np.float32)
-    _sync_if_dev(mem)
-    if f64 and mem == _capi.MEM_HOST:
-        mem |= _capi.HOST_F64
-    out = _empty_like_field((ny, nx), v)
-    check(lib().gpp_apply_curve_field(_ptr(v), _ptr(cr), _ptr(cf), ny, nx, nc, nc, int(policy_below), int(policy_above), _ptr(out), mem))
-    return out
+    return _m.run(lib().gpp_apply_curve_field, _ptr(v), _ptr(cr), _ptr(cf), ny, nx, nc, nc, int(policy_below), int(policy_above),
+                  out_shape=(ny, nx), like=v, mem=_m.flags(f64, v, cr, cf))
 
 
 def interpolate(x, iX, iY):
@@ -1535,93 +1298,71 @@ def point_in_rectangle(A, B, C_, D, m):   # src/api/util.cpp:571-582
 
 # ---- neighbourhood filters (include/gridpp.h:588-716, src/api/neighbourhood.cpp) ---------------------
 def _field23(a, name="input", keep_f64=False):
-    """2-D or 3-D field -> (array, ny, nx, ne, is3d); [[]] -> empty.  keep_f64: a large float64 array stays float64 (the caller
-    passes GPP_HOST_F64)."""
-    if _is_dev(a):
-        nd = a.dim()
-        arr = _vec(a, nd, name)
-    else:
-        arr = np.ascontiguousarray(np.asarray(a), dtype=np.float64 if keep_f64 and _wants_f64(a) else np.float32)
-        nd = arr.ndim
+    """2-D or 3-D field -> (array, ny, nx, ne, is3d, f64); [[]] -> empty.  keep_f64: a large float64 array stays float64 (f64 is
+    then true, for the caller's flags)."""
+    f64 = keep_f64 and _wants_f64(a)
+    arr = _m.field(a, f64=f64)
+    nd = len(_shape(arr))
     if nd not in (2, 3):
         if getattr(arr, "size", 1) == 0:
-            return arr, 0, 0, 0, 0
+            return arr, 0, 0, 0, 0, f64
         raise RuntimeError("%s must have 2 or 3 dimensions" % name)
     shp = tuple(arr.shape)
     ny, nx = shp[0], shp[1]
     ne = shp[2] if nd == 3 else 1
-    return arr, ny, nx, ne, int(nd == 3)
-
-
-def _sync_if_dev(mem):
-    if mem == _capi.MEM_DEVICE:
-        import torch
-        torch.cuda.current_stream().synchronize()
+    return arr, ny, nx, ne, int(nd == 3), f64
 
 
 def neighbourhood(input, halfwidth, statistic):
     """gridpp::neighbourhood for 2-D and 3-D (Y, X, E) input (src/api/neighbourhood.cpp:12-242)."""
-    arr, ny, nx, ne, is3d = _field23(input, keep_f64=True)
+    arr, ny, nx, ne, is3d, f64 = _field23(input, keep_f64=True)
     if halfwidth < 0:
         raise ValueError("Half width must be > 0")
     if statistic == Quantile:
         raise ValueError("Use neighbourhood_quantile for computing neighbourhood quantiles")
     if ny * nx * ne == 0:
         return np.zeros((0, 0), np.float32)
-    mem = _mem(arr)
-    _sync_if_dev(mem)
-    if not _is_dev(arr) and arr.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    out = _empty_like_field((ny, nx), arr)
-    check(lib().gpp_neighbourhood(_ptr(arr), ny, nx, ne, is3d, int(halfwidth), int(statistic), _ptr(out), mem))
-    return out
+    return _m.run(lib().gpp_neighbourhood, _ptr(arr), ny, nx, ne, is3d, int(halfwidth), int(statistic), out_shape=(ny, nx), like=arr,
+                  mem=_m.flags(f64, arr))
 
 
-def neighbourhood_brute_force(input, halfwidth, statistic):
-    arr, ny, nx, ne, is3d = _field23(input)
+def _brute_force(input, halfwidth, statistic, quantile):
+    """the body neighbourhood_brute_force and neighbourhood_quantile share"""
+    arr, ny, nx, ne, is3d, _ = _field23(input)
     if halfwidth < 0:
         raise ValueError("Half width must be > 0")
     if ny * nx * ne == 0:
         return np.zeros((0, 0), np.float32)
-    mem = _mem(arr)
-    _sync_if_dev(mem)
-    out = _empty_like_field((ny, nx), arr)
-    check(lib().gpp_neighbourhood_brute_force(_ptr(arr), ny, nx, ne, int(halfwidth), int(statistic), 0.0, _ptr(out), mem))
-    return out
+    return _m.run(lib().gpp_neighbourhood_brute_force, _ptr(arr), ny, nx, ne, int(halfwidth), int(statistic), float(quantile), out_shape=(ny, nx),
+                  like=arr, mem=_m.flags(False, arr))
+
+
+def neighbourhood_brute_force(input, halfwidth, statistic):
+    return _brute_force(input, halfwidth, statistic, 0.0)
 
 
 def neighbourhood_quantile(input, quantile, halfwidth):
     """Exact neighbourhood quantile (src/api/neighbourhood.cpp:534-539)."""
-    arr, ny, nx, ne, is3d = _field23(input)
-    if halfwidth < 0:
-        raise ValueError("Half width must be > 0")
-    if ny * nx * ne == 0:
-        return np.zeros((0, 0), np.float32)
-    mem = _mem(arr)
-    _sync_if_dev(mem)
-    out = _empty_like_field((ny, nx), arr)
-    check(lib().gpp_neighbourhood_brute_force(_ptr(arr), ny, nx, ne, int(halfwidth), Quantile, float(quantile), _ptr(out), mem))
-    return out
+    return _brute_force(input, halfwidth, Quantile, quantile)
 
 
 def neighbourhood_quantile_fast(input, quantile, halfwidth, thresholds):
     """All four overloads of gridpp::neighbourhood_quantile_fast (src/api/neighbourhood.cpp:296-527)."""
-    arr, ny, nx, ne, is3d = _field23(input, keep_f64=True)
+    arr, ny, nx, ne, is3d, f64 = _field23(input, keep_f64=True)
     if halfwidth < 0:
         raise ValueError("Half width must be > 0")
     if ny * nx * ne == 0:
         return np.zeros((0, 0), np.float32)
-    mem = _mem(arr)
     if np.ndim(quantile) == 0 and not _is_dev(quantile):
         q = np.array([quantile], np.float32)
     else:
-        q = _vec(quantile, 2, "quantile")
+        q = _m.field(quantile, 2, "quantile")
         if _shape(q) not in ((1, 1), (ny, nx)):
             raise ValueError("Quantile must be the same size as input, or size (1, 1)")
-    thr = _vec(thresholds, 1, "thresholds")
+    thr = _m.field(thresholds, 1, "thresholds")
     nq = int(np.prod(_shape(q)))
     q_host = False
-    if mem == _capi.MEM_DEVICE:
+    if _is_dev(arr):
         import torch
         if not _is_dev(q) and nq == 1:
             q_host = True        # (a scalar beside a device-resident field stays on the host: GPP_Q_HOST)
@@ -1629,15 +1370,8 @@ def neighbourhood_quantile_fast(input, quantile, halfwidth, thresholds):
         else:
             q = q if _is_dev(q) else torch.from_numpy(np.asarray(q)).to(arr.device)
         thr = thr if _is_dev(thr) else torch.from_numpy(np.asarray(thr)).to(arr.device)
-    _sync_if_dev(mem)
-    out = _empty_like_field((ny, nx), arr)
-    if not _is_dev(arr) and arr.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    if q_host:
-        mem |= _capi.Q_HOST
-    check(lib().gpp_neighbourhood_quantile_fast(_ptr(arr), ny, nx, ne, is3d, _ptr(q), nq, int(halfwidth), _ptr(thr),
-                                                int(_shape(thr)[0]), _ptr(out), mem))
-    return out
+    return _m.run(lib().gpp_neighbourhood_quantile_fast, _ptr(arr), ny, nx, ne, is3d, _ptr(q), nq, int(halfwidth), _ptr(thr),
+                  int(_shape(thr)[0]), out_shape=(ny, nx), like=arr, mem=_m.flags(f64, arr) | (_capi.Q_HOST if q_host else 0))
 
 
 def neighbourhood_ens(input, halfwidth, statistic):   # deprecated aliases (neighbourhood.cpp:541-552), with the reference's message
@@ -1668,8 +1402,8 @@ def window(array, length, statistic, before=False, keep_missing=False, missing_e
     inside its loop; here before any device work)."""
     if length <= 0:
         raise ValueError("Length variable must be > 0")
-    dev = _is_dev(array)
-    arr = _vec(array, 2, "array") if dev else _vec(array, 2, "array", np.float64 if _wants_f64(array) else np.float32)
+    f64 = _wants_f64(array)
+    arr = _m.field(array, 2, "array", f64)
     ny, nx = _shape(arr)
     if ny == 0 or nx == 0:
         return _empty_like_field((0, 0) if ny == 0 else (ny, 0), arr)
@@ -1677,14 +1411,8 @@ def window(array, length, statistic, before=False, keep_missing=False, missing_e
         raise ValueError("Length variable must be an odd number")
     if statistic not in _WINDOW_STATISTICS:
         raise RuntimeError("Internal error. Cannot compute statistic")
-    mem = _mem(arr)
-    _sync_if_dev(mem)
-    if not dev and arr.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    out = _empty_like_field((ny, nx), arr)
-    check(lib().gpp_window(_ptr(arr), ny, nx, int(length), int(statistic), int(bool(before)), int(bool(keep_missing)), int(bool(missing_edges)),
-                           _ptr(out), mem))
-    return out
+    return _m.run(lib().gpp_window, _ptr(arr), ny, nx, int(length), int(statistic), int(bool(before)), int(bool(keep_missing)),
+                  int(bool(missing_edges)), out_shape=(ny, nx), like=arr, mem=_m.flags(f64, arr))
 
 
 # ---- weather diagnostics (include/gridpp.h:49-67,1249-1367; src/api/humidity.cpp, pressure.cpp, qnh.cpp, wind.cpp) ------------------
@@ -1699,6 +1427,20 @@ gas_constant_mol = float(np.float32(8.31447))
 gas_constant_si = float(np.float32(287.05))
 
 
+def _vectors_call(entry, args, names, size_checks):
+    """An element-wise entry point on 1-D arrays of one length (host, or all torch CUDA tensors) -> an array of that length where they
+    live.  size_checks: (i, j, message) in the reference's order."""
+    f64 = _mem(*args) == _capi.MEM_HOST and _wants_f64(*args)   # (mixed memory is refused before the ranks are looked at)
+    arrs = [_m.field(a, 1, n, f64) for a, n in zip(args, names)]
+    for i, j, message in size_checks:
+        if _shape(arrs[i]) != _shape(arrs[j]):
+            raise ValueError(message)
+    n = _shape(arrs[0])[0]
+    if n == 0:
+        return _empty_like_field((0,), arrs[0]) if _is_dev(arrs[0]) else np.zeros(0, np.float32)
+    return _m.run(entry, *[_ptr(a) for a in arrs], n, out_shape=(n,), like=arrs[0], mem=_m.flags(f64, *arrs))
+
+
 def _pointwise(entry, which, args, names, size_checks):
     """One diagnostic: every argument a scalar -> the host-only scalar form (a Python float back); otherwise 1-D arrays of one length
     (host, or all torch CUDA tensors) through the kernel.  size_checks: (i, j, message) in the reference's order."""
@@ -1707,19 +1449,7 @@ def _pointwise(entry, which, args, names, size_checks):
         out = C.c_float(np.nan)
         check(lib().gpp_diagnostic_scalar(which, vals, len(args), C.byref(out)))
         return out.value
-    mem = _mem(*args)
-    f64 = mem == _capi.MEM_HOST and _wants_f64(*args)
-    arrs = [_vec(a, 1, n) if _is_dev(a) else _vec(a, 1, n, np.float64 if f64 else np.float32) for a, n in zip(args, names)]
-    for i, j, message in size_checks:
-        if _shape(arrs[i]) != _shape(arrs[j]):
-            raise ValueError(message)
-    n = _shape(arrs[0])[0]
-    if n == 0:
-        return _empty_like_field((0,), arrs[0]) if mem == _capi.MEM_DEVICE else np.zeros(0, np.float32)
-    _sync_if_dev(mem)
-    out = _empty_like_field((n,), arrs[0])
-    check(entry(*[_ptr(a) for a in arrs], n, _ptr(out), mem | (_capi.HOST_F64 if f64 else 0)))
-    return out
+    return _vectors_call(entry, args, names, size_checks)
 
 
 def dewpoint(temperature, relative_humidity):
@@ -1816,22 +1546,17 @@ class Transform:
             return out.value
         if nd > 3:
             raise RuntimeError("input must be a scalar or have 1, 2 or 3 dimensions, got %d" % nd)
-        dev = _is_dev(value)
-        v = _vec(value, nd, "input") if dev else _vec(value, nd, "input", np.float64 if _wants_f64(value) else np.float32)
+        dev, f64 = _is_dev(value), _wants_f64(value)
+        v = _m.field(value, nd, "input", f64)
         shp = _shape(v)
         n = int(np.prod(shp))
         if n == 0:
             return _empty_like_field(_typemap_shape(shp), v) if dev else np.zeros(_typemap_shape(shp), np.float32)
-        out = _empty_like_field(shp, v)
         if self._kind is None:   # the vector forms call the virtual scalar one: -1 everywhere
+            out = _empty_like_field(shp, v)
             out[...] = -1
             return out
-        mem = _mem(v)
-        _sync_if_dev(mem)
-        if not dev and v.dtype == np.float64:
-            mem |= _capi.HOST_F64
-        check(self._vector_entry(_ptr(v), n, backward, _ptr(out), mem))
-        return out
+        return _m.run(self._vector_entry, _ptr(v), n, backward, out_shape=shp, like=v, mem=_m.flags(f64, v))
 
     # the two C-ABI calls of _apply (a transform with other parameters than (p0, p1) overrides them)
     def _scalar_entry(self, value, backward, out):
@@ -1915,18 +1640,8 @@ def gamma_inv(levels, shape, scale):
         out = C.c_float(np.nan)
         check(lib().gpp_gamma_inv_scalar(float(levels), float(shape), float(scale), C.byref(out)))
         return out.value
-    mem = _mem(*args)
-    f64 = mem == _capi.MEM_HOST and _wants_f64(*args)
-    arrs = [_vec(a, 1, n) if _is_dev(a) else _vec(a, 1, n, np.float64 if f64 else np.float32) for a, n in zip(args, ("levels", "shape", "scale"))]
-    if not (_shape(arrs[0]) == _shape(arrs[1]) == _shape(arrs[2])):
-        raise ValueError("gamma_inv: levels, shape and scale must be of the same size")
-    n = _shape(arrs[0])[0]
-    if n == 0:
-        return _empty_like_field((0,), arrs[0]) if mem == _capi.MEM_DEVICE else np.zeros(0, np.float32)
-    _sync_if_dev(mem)
-    out = _empty_like_field((n,), arrs[0])
-    check(lib().gpp_gamma_inv(*[_ptr(a) for a in arrs], n, _ptr(out), mem | (_capi.HOST_F64 if f64 else 0)))
-    return out
+    message = "gamma_inv: levels, shape and scale must be of the same size"
+    return _vectors_call(lib().gpp_gamma_inv, args, ("levels", "shape", "scale"), [(0, 1, message), (1, 2, message)])
 
 
 # ---- verification scores (include/gridpp.h:103-110; src/api/metric_optimizer.cpp:185-244, neighbourhood_score.cpp) ----
@@ -1940,13 +1655,10 @@ def _metric(metric):
     return int(metric)
 
 
-def _score_vector(a, name):
-    if _is_dev(a):
-        import torch
-        if a.dim() != 1:
-            raise RuntimeError("%s must have 1 dimension" % name)
-        return a.contiguous().to(torch.float32)
-    return _vec(a, 1, name)
+def _ref_fcst(ref, fcst, f64=False):
+    """ref and fcst as 1-D fields (a device tensor of another rank raises the score functions' own text)"""
+    return (_m.field(ref, 1, "ref", f64, dev_message="ref must have 1 dimension"),
+            _m.field(fcst, 1, "fcst", f64, dev_message="fcst must have 1 dimension"))
 
 
 def calc_score(*args):
@@ -1971,13 +1683,11 @@ def calc_score(*args):
     else:
         ref, fcst, threshold, fthreshold, metric = args
     metric = _metric(metric)
-    ref, fcst = _score_vector(ref, "ref"), _score_vector(fcst, "fcst")
+    ref, fcst = _ref_fcst(ref, fcst)
     n = _shape(fcst)[0]
     if _shape(ref)[0] < n:
         raise ValueError("ref and fcst not the same size")
-    mem = _mem(ref, fcst) if n else _capi.MEM_HOST
-    if n:
-        _sync_if_dev(mem)
+    mem = _m.flags(False, ref, fcst) if n else _capi.MEM_HOST
     check(lib().gpp_calc_score(_ptr(ref), _ptr(fcst), n, float(threshold), float(fthreshold), metric, C.byref(out), mem))
     return out.value
 
@@ -1988,8 +1698,8 @@ def neighbourhood_score(grid, points, fcst, ref, half_width, metric, threshold):
     both finite, and the fractions of a / b / c / d cells of the window go through calc_score.  fcst: a numpy array or a torch CUDA tensor
     (the result is then one too); ref: a host vector.  Checks in the reference's order: "Grid size is not the same as forecast values",
     "half_width must be greater than 0", "Unknown metric", "Points size is not the same as values".  An empty grid gives an empty array."""
-    dev = _is_dev(fcst)
-    f = _vec(fcst, 2, "fcst") if dev else _vec(fcst, 2, "fcst", np.float64 if _wants_f64(fcst) else np.float32)
+    f64 = _wants_f64(fcst)
+    f = _m.field(fcst, 2, "fcst", f64)
     shp = _shape(f)
     ny, nx = grid.size()
     if shp[0] != 0 and tuple(shp) != (ny, nx):                 # src/api/util.cpp:427-429
@@ -1997,30 +1707,22 @@ def neighbourhood_score(grid, points, fcst, ref, half_width, metric, threshold):
     if half_width <= 0:
         raise ValueError("half_width must be greater than 0")
     metric = _metric(metric)
-    r = _vec(ref, 1, "ref")
+    r = _m.field(ref, 1, "ref")
     if r.shape[0] != points.size():
         raise ValueError("Points size is not the same as values")
     if ny * nx == 0:
         return _empty_like_field((ny, nx), f)
     if shp[0] == 0:   # (the reference reads fcst[0] of an empty vector here)
         raise ValueError("Grid size is not the same as forecast values")
-    mem = _mem(f)
-    _sync_if_dev(mem)
-    if not dev and f.dtype == np.float64:
-        mem |= _capi.HOST_F64
-    out = _empty_like_field((ny, nx), f)
-    check(lib().gpp_neighbourhood_score(grid._h, points._h, _ptr(f), _ptr(r), int(half_width), metric, float(threshold), _ptr(out), mem))
-    return out
+    return _m.run(lib().gpp_neighbourhood_score, grid._h, points._h, _ptr(f), _ptr(r), int(half_width), metric, float(threshold),
+                  out_shape=(ny, nx), like=f, mem=_m.flags(f64, f))
 
 
 # ---- the optimal forecast threshold (src/api/metric_optimizer.cpp:105-184) ----
 def _optimizer_vectors(ref, fcst):
-    """-> ref, fcst, mem: numpy arrays (float64 ones of 2**20 values and more are cast on the device) or torch CUDA tensors"""
-    mem = _mem(ref, fcst)
-    dtype = np.float64 if mem == _capi.MEM_HOST and _wants_f64(ref, fcst) else np.float32
-    ref = _score_vector(ref, "ref") if _is_dev(ref) else _vec(ref, 1, "ref", dtype)
-    fcst = _score_vector(fcst, "fcst") if _is_dev(fcst) else _vec(fcst, 1, "fcst", dtype)
-    return ref, fcst, mem | (_capi.HOST_F64 if dtype == np.float64 else 0)
+    """-> ref, fcst, f64: numpy arrays (float64 ones of 2**20 values and more are cast on the device) or torch CUDA tensors"""
+    f64 = _mem(ref, fcst) == _capi.MEM_HOST and _wants_f64(ref, fcst)   # (mixed memory is refused before the ranks are looked at)
+    return _ref_fcst(ref, fcst, f64) + (f64,)
 
 
 def get_optimal_threshold(ref, fcst, threshold, metric):
@@ -2034,14 +1736,13 @@ def get_optimal_threshold(ref, fcst, threshold, metric):
     name is not part of the `gridpp` alias.  ref, fcst: numpy arrays or torch CUDA tensors; a float comes back.  ValueError("Unknown
     metric"); a ref shorter than fcst is ValueError("ref and fcst not the same size"), as for calc_score."""
     metric = _metric(metric)
-    ref, fcst, mem = _optimizer_vectors(ref, fcst)
+    ref, fcst, f64 = _optimizer_vectors(ref, fcst)
     n = _shape(fcst)[0]
     if _shape(ref)[0] < n:
         raise ValueError("ref and fcst not the same size")
     out = C.c_float(np.nan)
-    if n:
-        _sync_if_dev(mem)
-    check(lib().gpp_get_optimal_threshold(_ptr(ref), _ptr(fcst), n, float(threshold), metric, C.byref(out), mem if n else _capi.MEM_HOST))
+    mem = _m.flags(f64, ref, fcst) if n else _capi.MEM_HOST
+    check(lib().gpp_get_optimal_threshold(_ptr(ref), _ptr(fcst), n, float(threshold), metric, C.byref(out), mem))
     return out.value
 
 
@@ -2051,7 +1752,7 @@ def metric_optimizer_curve(ref, fcst, thresholds, metric):
     naming).  One sort serves all thresholds.  ValueError("ref and fcst not the same size") unless both have the same length; empty
     thresholds give two empty arrays and need no GPU.  Not part of the `gridpp` alias."""
     metric = _metric(metric)
-    ref, fcst, mem = _optimizer_vectors(ref, fcst)
+    ref, fcst, f64 = _optimizer_vectors(ref, fcst)
     n = _shape(fcst)[0]
     if _shape(ref)[0] != n:
         raise ValueError("ref and fcst not the same size")
@@ -2059,28 +1760,23 @@ def metric_optimizer_curve(ref, fcst, thresholds, metric):
     T = thresholds.shape[0]
     curve_ref, curve_fcst, count = np.empty(T, np.float32), np.empty(T, np.float32), C.c_int(0)
     if T and n:
-        _sync_if_dev(mem)
         check(lib().gpp_metric_optimizer_curve(_ptr(ref), _ptr(fcst), n, _ptr(thresholds), T, metric, _ptr(curve_ref), _ptr(curve_fcst),
-                                               C.byref(count), mem))
+                                               C.byref(count), _m.flags(f64, ref, fcst)))
     return curve_ref[:count.value].copy(), curve_fcst[:count.value].copy()
 
 
 # ---- util (include/gridpp.h:1454-1482, src/api/util.cpp) ---------------------------------------------
 def _rows_array(array, maxdim):
     """calc_statistic / calc_quantile input: a host array or a torch CUDA tensor -> C-contiguous float32 of 1 .. maxdim dimensions"""
-    nd = _ndim(array) if _is_dev(array) else np.ndim(array)
-    if _is_dev(array):
-        if not 1 <= nd <= maxdim:
-            raise RuntimeError("array must have %s dimensions" % ("1 or 2" if maxdim == 2 else "1, 2 or 3"))
-        return _vec(array, nd)
-    a = np.ascontiguousarray(np.asarray(array), dtype=np.float32)
-    if not 1 <= a.ndim <= maxdim:
+    a = _m.field(array)
+    if not 1 <= len(_shape(a)) <= maxdim:
         raise RuntimeError("array must have %s dimensions" % ("1 or 2" if maxdim == 2 else "1, 2 or 3"))
     return a
 
 
-def _rows_result(out, a):
-    """1-D input -> a Python float; otherwise the per-row result where the input lives"""
+def _rows_call(entry, a, rows, *args, mem):
+    """One value per row of `a` where it lives (none for no rows); a 1-D input -> a Python float."""
+    out = _m.run(entry, _ptr(a), rows, *args, out_shape=(rows,), like=a, mem=mem) if rows else _empty_like_field((0,), a)
     if len(_shape(a)) != 1:
         return out
     return float(out[0].item()) if _is_dev(out) else float(out[0])
@@ -2091,13 +1787,7 @@ def calc_statistic(array, statistic):
     a = _rows_array(array, 2)
     shp = _shape(a)
     rows = 1 if len(shp) == 1 else shp[0]
-    length = shp[-1]
-    mem = _mem(a)
-    _sync_if_dev(mem)
-    out = _empty_like_field((rows,), a) if _is_dev(a) else np.empty(rows, np.float32)
-    if rows:
-        check(lib().gpp_calc_statistic(_ptr(a), rows, length, int(statistic), _ptr(out), mem))
-    return _rows_result(out, a)
+    return _rows_call(lib().gpp_calc_statistic, a, rows, shp[-1], int(statistic), mem=_m.flags(False, a))
 
 
 def calc_quantile(array, quantile):
@@ -2108,48 +1798,37 @@ def calc_quantile(array, quantile):
     dev = _is_dev(a)
     if dev:
         import torch
-        if _is_dev(quantile):
-            q = quantile.contiguous().to(torch.float32)
-        else:
-            q = torch.from_numpy(np.ascontiguousarray(np.asarray(quantile), dtype=np.float32)).to(a.device)
+        q = _m.field(quantile)
+        if not _is_dev(q):
+            q = torch.from_numpy(q).to(a.device)
     else:
         _mem(a, quantile)   # (a device-resident quantile beside a host array: _mem's error)
-        q = np.ascontiguousarray(np.asarray(quantile), dtype=np.float32)
-    mem = _mem(a, q)
+        q = _m.field(quantile)
     if len(shp) == 3:
         if _shape(q) != shp[:2]:
             raise ValueError("Dimension mismatch between array and quantile")
         if shp[0] * shp[1] == 0:
             return np.zeros((0, 0), np.float32)
-        rows, length = shp[0] * shp[1], shp[2]
-        _sync_if_dev(mem)
-        out = _empty_like_field((rows,), a) if dev else np.empty(rows, np.float32)
-        check(lib().gpp_calc_quantile(_ptr(a), rows, length, _ptr(q), rows, _ptr(out), mem))
-        return out.reshape(shp[:2])
-    rows = 1 if len(shp) == 1 else shp[0]
-    out = _empty_like_field((rows,), a) if dev else np.empty(rows, np.float32)
+        rows = shp[0] * shp[1]
+        return _m.run(lib().gpp_calc_quantile, _ptr(a), rows, shp[2], _ptr(q), rows, out_shape=(rows,), like=a,
+                      mem=_m.flags(False, a, q)).reshape(shp[:2])
     qq = q.reshape(1)
-    if rows:
-        _sync_if_dev(mem)
-        check(lib().gpp_calc_quantile(_ptr(a), rows, shp[-1], _ptr(qq), 1, _ptr(out), mem))
-    return _rows_result(out, a)
+    return _rows_call(lib().gpp_calc_quantile, a, 1 if len(shp) == 1 else shp[0], shp[-1], _ptr(qq), 1, mem=_m.flags(False, a, qq))
 
 
 def _even_quantiles(values, num, only_valid):
     dev = _is_dev(values)
-    v = values.contiguous().float().reshape(-1) if dev else np.ascontiguousarray(np.asarray(values), dtype=np.float32).ravel()
+    v = _m.field(values).reshape(-1)
     n = int(v.numel()) if dev else v.size
     out = np.empty(max(int(num), 1) if n else 1, np.float32)
     if num > 0 and n > 0 and num >= n:
         out = np.empty(n, np.float32)
     cnt = C.c_int(0)
     if dev:
-        import torch
-        torch.cuda.current_stream().synchronize()
-        dout = torch.empty(out.size, dtype=torch.float32, device=v.device)
-        check(lib().gpp_calc_even_quantiles(_ptr(v), n, int(num), int(only_valid), _ptr(dout), C.byref(cnt), _capi.MEM_DEVICE))
+        dout = _empty_like_field(out.size, v)
+        check(lib().gpp_calc_even_quantiles(_ptr(v), n, int(num), int(only_valid), _ptr(dout), C.byref(cnt), _m.flags(False, v)))
         return dout[:cnt.value].cpu().numpy()
-    check(lib().gpp_calc_even_quantiles(_ptr(v), n, int(num), int(only_valid), _ptr(out), C.byref(cnt), _capi.MEM_HOST))
+    check(lib().gpp_calc_even_quantiles(_ptr(v), n, int(num), int(only_valid), _ptr(out), C.byref(cnt), _m.flags(False, v)))
     return out[:cnt.value].copy()
 
 
@@ -2175,20 +1854,19 @@ def optimal_interpolation_ensi(bgrid, background, points, pobs, psigmas, pbackgr
     nd = 3 if isinstance(bgrid, Grid) else 2
     S = points.size()
     f64 = S > 0 and _wants_f64(background)
-    dt = np.float64 if f64 else np.float32
-    background = _vec(background, nd, "background", dt)
+    background = _m.field(background, nd, "background", f64)
     if S == 0:   # src/api/oi_ensi.cpp:48-50,135-137: returns the background before any other check
         return background.clone() if _is_dev(background) else background.copy()
     if bgrid.get_coordinate_type() != points.get_coordinate_type():
         raise ValueError("Both background and observations points must be of same coordinate type (lat/lon or x/y)")
-    shape = tuple(bgrid.size()) if nd == 3 else (bgrid.size(),)
+    shape = _out_shape(bgrid)
     if nd == 3 and shape[0] * shape[1] == 0:
         raise ValueError("Grid size cannot be zero")
     if _shape(background)[:nd - 1] != shape:
         raise ValueError("Input field is not the same size as the grid")
     E = _shape(background)[-1]
-    pobs, psigmas = _vec(pobs, 1, "obs", dt), _vec(psigmas, 1, "sigmas", dt)
-    pbackground = _vec(pbackground, 2, "background_at_points", dt)
+    pobs, psigmas = _m.field(pobs, 1, "obs", f64), _m.field(psigmas, 1, "sigmas", f64)
+    pbackground = _m.field(pbackground, 2, "background_at_points", f64)
     if _shape(pobs)[0] != S:
         raise ValueError("Observations and points size mismatch")
     if _shape(psigmas)[0] != S:
@@ -2197,10 +1875,7 @@ def optimal_interpolation_ensi(bgrid, background, points, pobs, psigmas, pbackgr
         raise ValueError("Background and points size mismatch")
     if _shape(pbackground)[1] != E:
         raise ValueError("Ensemble members in gridded background is not the same as in the point background")
-    mem = _mem(background, pobs, psigmas, pbackground)
-    _sync_if_dev(mem)
-    if f64 and mem == _capi.MEM_HOST:
-        mem |= _capi.HOST_F64
+    mem = _m.flags(f64, background, pobs, psigmas, pbackground)
     out = _empty_like_field(_shape(background), background)
     check(lib().gpp_optimal_interpolation_ensi(bgrid._h, _ptr(background), int(E), points._h, _ptr(pobs), _ptr(psigmas),
                                                _ptr(pbackground), _structure(structure), int(max_points),
@@ -2235,12 +1910,12 @@ def _ensi_multi(variant, name, bgrid, bratios, background, background_corr, poin
         raise TypeError("bgrid must be a Grid or Points, points a Points")
     nd = 3 if isinstance(bgrid, Grid) else 2
     S = points.size()
-    background = _vec(background, nd, "background", np.float32)
+    background = _m.field(background, nd, "background")
     if S == 0:
         return background.clone() if _is_dev(background) else background.copy()
     if bgrid.get_coordinate_type() != points.get_coordinate_type():
         raise ValueError("Both background and observations points must be of same coorindate type (lat/lon or x/y)")
-    shape = tuple(bgrid.size()) if nd == 3 else (bgrid.size(),)
+    shape = _out_shape(bgrid)
     if nd == 3 and shape[0] * shape[1] == 0:
         raise ValueError("Grid size cannot be zero")
     if _shape(background)[:nd - 1] != shape:
@@ -2248,18 +1923,18 @@ def _ensi_multi(variant, name, bgrid, bratios, background, background_corr, poin
     E = _shape(background)[-1]
     corr = variant != 2
     if corr:
-        background_corr = _vec(background_corr, nd, "background_corr", np.float32)
+        background_corr = _m.field(background_corr, nd, "background_corr")
         if _shape(background_corr) != _shape(background):
             raise ValueError("Input background_corr field is not the same size as the grid")
-        pbackground_corr = _vec(pbackground_corr, 2, "pbackground_corr", np.float32)
+        pbackground_corr = _m.field(pbackground_corr, 2, "pbackground_corr")
         if _shape(pbackground_corr)[0] != S:
             raise ValueError("Background_corr and points size mismatch")
-    bratios = _vec(bratios, nd - 1, "bratios", np.float32)
+    bratios = _m.field(bratios, nd - 1, "bratios")
     if _shape(bratios) != shape:
         raise ValueError("Bratios and grid size mismatch")
-    pobs = _vec(pobs, 1 if variant == 3 else 2, "pobs", np.float32)
-    pratios = _vec(pratios, 1, "pratios", np.float32)
-    pbackground = _vec(pbackground, 2, "pbackground", np.float32)
+    pobs = _m.field(pobs, 1 if variant == 3 else 2, "pobs")
+    pratios = _m.field(pratios, 1, "pratios")
+    pbackground = _m.field(pbackground, 2, "pbackground")
     if _shape(pobs)[0] != S:
         raise ValueError("Observations and points exception mismatch")
     if _shape(pratios)[0] != S:
@@ -2269,8 +1944,7 @@ def _ensi_multi(variant, name, bgrid, bratios, background, background_corr, poin
     if _shape(pbackground)[1] != E or (variant != 3 and _shape(pobs)[1] != E) or (corr and _shape(pbackground_corr)[1] != E):
         raise ValueError("Ensemble members in gridded background is not the same as in the point fields")
     args = [bratios, background, pobs, pratios, pbackground] + ([background_corr, pbackground_corr] if corr else [])
-    mem = _mem(*args)
-    _sync_if_dev(mem)
+    mem = _m.flags(False, *args)
     out = _empty_like_field(_shape(background), background)
     check(lib().gpp_optimal_interpolation_ensi_multi(int(variant), bgrid._h, _ptr(bratios), _ptr(background),
                                                      _ptr(background_corr) if corr else None, int(E), points._h, _ptr(pobs), _ptr(pratios),
