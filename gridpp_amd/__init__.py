@@ -55,6 +55,72 @@ def is_valid(value):
     return bool(not np.isnan(v) and not np.isinf(v))
 
 
+def is_valid_lat(lat, type):
+    """src/api/util.cpp:617-621: a Cartesian y is any valid value; a latitude lies within +-90.001 (the float against the double bound)"""
+    if type == Cartesian:
+        return is_valid(lat)
+    return bool(is_valid(lat) and float(np.float32(lat)) >= -90.001 and float(np.float32(lat)) <= 90.001)
+
+
+def is_valid_lon(lon, type):
+    """src/api/util.cpp:622-624: any valid value, for both coordinate types"""
+    return is_valid(lon)
+
+
+def num_missing_values(array):
+    """src/api/util.cpp:217-225: how many values of a 2-D array are NaN or infinite"""
+    a = _vec(array, 2, "array")
+    return int(a.size - np.count_nonzero(np.isfinite(a)))
+
+
+# src/api/util.cpp:475-504
+def init_vec2(Y, X, value=MV):
+    return np.full((int(Y), int(X)), value, np.float32)
+
+
+def init_ivec2(Y, X, value):
+    return np.full((int(Y), int(X)), value, np.int32)
+
+
+def init_vec3(Y, X, T, value=MV):
+    return np.full((int(Y), int(X), int(T)), value, np.float32)
+
+
+def init_ivec3(Y, X, T, value):
+    return np.full((int(Y), int(X), int(T)), value, np.int32)
+
+
+def compatible_size(a, b):
+    """The seven overloads of src/api/util.cpp:427-474: (Grid, vec2), (Grid, vec3), (Points, vec), (Points, vec2), (vec2, vec2),
+    (vec2, vec3) and (vec3, vec3).  A Grid or Points first argument decides the overload, then the rank of the arrays; an array
+    without elements counts as one of the rank the overload asks for (numpy cannot tell [] from [[]])."""
+    sb = np.shape(b)
+    empty_b = 0 in sb
+    if isinstance(a, Grid):
+        if len(sb) not in (2, 3) and not empty_b:
+            raise TypeError("compatible_size(Grid, v): v must have 2 or 3 dimensions")
+        if sb[0] == 0:
+            return True
+        if len(sb) == 2:
+            return a.size()[0] == sb[0] and a.size()[1] == sb[1]
+        return sb[1] == 0 or (a.size()[0] == sb[1] and a.size()[1] == sb[2])   # v is [T][Y][X]; a v[0] without rows passes (:431)
+    if isinstance(a, Points):
+        if len(sb) == 1:
+            return a.size() == sb[0]
+        if len(sb) != 2:
+            raise TypeError("compatible_size(Points, v): v must have 1 or 2 dimensions")
+        return sb[0] == 0 or a.size() == sb[1]
+    sa = np.shape(a)
+    if (len(sa), len(sb)) == (2, 3):   # the first two sizes only (:448-461)
+        return sa[0] == sb[0] and (sa[0] == 0 or sa[1] == sb[1])
+    if len(sa) == len(sb) and len(sa) in (2, 3):
+        return sa == sb
+    if 0 in sa and empty_b:   # e.g. ([], [[]]): as far as both have sizes
+        n = min(len(sa), len(sb))
+        return sa[:n] == sb[:n]
+    raise TypeError("compatible_size: no overload for arrays of %d and %d dimensions" % (len(sa), len(sb)))
+
+
 _omp_threads = 1
 
 
@@ -438,18 +504,37 @@ class StructureFunction:
         check(lib().gpp_structure_localization_distance(C.byref(self._s), float(lat), float(lon), C.byref(d)))
         return d.value
 
-    def _corr(self, p1, p2, background):
+    def _corr(self, p1, p2, background, device=None):
+        """corr / corr_background of p1 against one Point (a float), a list or tuple of Points (np.float32 array) or every point of a
+        Points / KDTree / Grid (an array shaped like it; a torch tensor on `device` if one is given): the scales of a spatially varying
+        structure are looked up at p1 once and all pairs run in one launch (structure.cpp:231-267)"""
+        if isinstance(p2, _PointSet):
+            shape = _out_shape(p2)
+            if device is None:
+                out = _host_empty(shape)
+                mem = _capi.MEM_HOST
+            else:
+                import torch
+                out = torch.empty(shape, dtype=torch.float32, device=device)
+                if not _is_dev(out):
+                    raise ValueError("device must be a GPU device")
+                mem = _capi.MEM_DEVICE
+            check(lib().gpp_structure_corr_points(C.byref(self._s), p1._seven(), p2._h, int(background), _ptr(out), mem))
+            return out
         if isinstance(p2, (list, tuple)):
-            return np.array([self._corr(p1, q, background) for q in p2], np.float32)
+            rec = np.array([(q.x, q.y, q.z, q.elev, q.laf, q.lat, q.lon) for q in p2], np.float32).reshape(len(p2), 7)
+            out = np.empty(len(p2), np.float32)
+            check(lib().gpp_structure_corr_many(C.byref(self._s), p1._seven(), _ptr(rec), len(p2), int(background), _ptr(out)))
+            return out
         r = C.c_float(0)
         check(lib().gpp_structure_corr(C.byref(self._s), p1._seven(), p2._seven(), int(background), C.byref(r)))
         return r.value
 
-    def corr(self, p1, p2):
-        return self._corr(p1, p2, 0)
+    def corr(self, p1, p2, device=None):
+        return self._corr(p1, p2, 0, device)
 
-    def corr_background(self, p1, p2):
-        return self._corr(p1, p2, 1)
+    def corr_background(self, p1, p2, device=None):
+        return self._corr(p1, p2, 1, device)
 
     def clone(self):
         c = StructureFunction.__new__(type(self))

@@ -93,6 +93,8 @@ SIGNATURES = {
     "gpp_structure_min_rho": [C.c_int, C.c_float, C.c_float, fp],
     "gpp_structure_localization_distance": [C.POINTER(gpp_structure), C.c_float, C.c_float, fp],
     "gpp_structure_corr": [C.POINTER(gpp_structure), fp, fp, C.c_int, fp],
+    "gpp_structure_corr_many": [C.POINTER(gpp_structure), fp, vp, C.c_longlong, C.c_int, vp],
+    "gpp_structure_corr_points": [C.POINTER(gpp_structure), fp, vp, C.c_int, vp, C.c_int],
     "gpp_field_create": [vp, vp, vp, vp, C.c_int, C.c_float, C.POINTER(vp)],
     "gpp_field_destroy": [vp],
     "gpp_optimal_interpolation_full": [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(gpp_structure), C.c_int, C.c_int, vp, vp, C.c_int],

@@ -1466,7 +1466,7 @@ extern "C" int gpp_field_destroy(gpp_field* f) {
     GPP_CATCH
 }
 // scalar structure at one location of a spatially varying one (nearest neighbour of (lat, lon) in the field's grid)
-static gpp_structure structure_at(const gpp_structure* s, float lat, float lon) {
+gpp_structure gpp_structure_at(const gpp_structure* s, float lat, float lon) {
     gpp_structure t = *s;
     if(s->field_v || s->field_w || (s->field && (s->kind_v || s->kind_w))) {   // MultipleStructure with spatially varying parts
         auto at = [&](const gpp_field* f) {
@@ -1511,7 +1511,7 @@ static float loc_dist(const gpp_structure* s) { return gpp_resolve_structure(s).
 extern "C" int gpp_structure_localization_distance(const gpp_structure* s, float lat, float lon, float* dist) {
     GPP_TRY
     if(!s) invalid("structure is NULL");
-    gpp_structure t = structure_at(s, lat, lon);
+    gpp_structure t = gpp_structure_at(s, lat, lon);
     *dist = loc_dist(&t);
     return GPP_OK;
     GPP_CATCH
@@ -1519,7 +1519,7 @@ extern "C" int gpp_structure_localization_distance(const gpp_structure* s, float
 extern "C" int gpp_structure_corr(const gpp_structure* s, const float p1[7], const float p2[7], int background, float* rho) {
     GPP_TRY
     if(!s) invalid("structure is NULL");
-    gpp_structure t = structure_at(s, p1[5], p1[6]);
+    gpp_structure t = gpp_structure_at(s, p1[5], p1[6]);
     DevStructure d = gpp_resolve_structure(&t);
     DevBuf<float> out;
     out.get(1);

@@ -38,6 +38,7 @@ struct gpp_field {   // spatially varying structure parameters resident in HBM (
 int gpp_tile_wshift(gpp_points* grid);   // oi.hip
 struct DevStructure;
 DevStructure gpp_resolve_structure(const gpp_structure* s);   // oi.hip: validation + localization distance
+gpp_structure gpp_structure_at(const gpp_structure* s, float lat, float lon);   // oi.hip: the scalar structure a spatially varying one is at (lat, lon)
 void gpp_bind_field(DevStructure& d, const gpp_structure* s, gpp_points* bgrid, gpp_points* points, gpp::DevBuf<int>& cbuf, gpp::DevBuf<int>& obuf);
 
 // Scratch of the general ("huge") kernels (k_oi_huge, k_ensi_huge, k_ensi_multi_huge): no capacity of their own, sized per call.  A

@@ -3,10 +3,19 @@
 //
 // Same namespace, type names, signatures, defaults and exception types as the reference, so code written
 // against gridpp.h for this path compiles unchanged:
-//   vec/vec2/vec3/ivec                         include/gridpp.h:25-41
+//   vec/vec2/vec3/ivec/ivec2/ivec3             include/gridpp.h:25-41
 //   Statistic, CoordinateType, MV              :49,88-100,120-123
-//   Points, Grid, KDTree (queries)             :1746-2060
-//   BarnesStructure (scalar form)              :2160-2185
+//   Point (both constructors)                  :1713-1743
+//   KDTree (queries, getters, the static distance helpers)  :1746-1873
+//     (one addition: calc_distance_fast(const Point&, const Point&), which the reference does not declare)
+//   Points, Grid (every public member)         :1876-2060
+//   StructureFunction (corr / corr_background for one point and for a vector, localization_distance, clone,
+//     default_min_rho), StructureFunctionPtr   :2067-2105
+//   Barnes / Soar / Toar / Powerlaw / Linear structures (scalar and spatially varying forms), CressmanStructure,
+//     MultipleStructure, CrossValidation       :2107-2343
+//   staticcorr_points                          :462
+//   convert_coordinates (both overloads), is_valid_lat, is_valid_lon, num_missing_values  :1492-1522
+//   init_vec2 / init_ivec2 / init_vec3 / init_ivec3, compatible_size (all seven overloads)  :1565-1660
 //   optimal_interpolation(_full)(_ensi)        :162-294
 //   neighbourhood*, get_neighbourhood_thresholds :588-716
 //   nearest (all eight overloads)              :860-900
@@ -28,6 +37,7 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <mutex>
 #include <sstream>
 #include <stdexcept>
 #include <initializer_list>
@@ -42,6 +52,7 @@ typedef std::vector<vec> vec2;
 typedef std::vector<vec2> vec3;
 typedef std::vector<int> ivec;
 typedef std::vector<ivec> ivec2;
+typedef std::vector<ivec2> ivec3;
 static const float MV = NAN;
 static const double radius_earth = 6.378137e6;
 // include/gridpp.h:51-67
@@ -91,9 +102,24 @@ inline vec3 unflatten(const vec& f, size_t Y, size_t X, size_t E) {
     for(size_t y = 0; y < Y; y++) { o[y].resize(X); for(size_t x = 0; x < X; x++) o[y][x].assign(f.begin() + (y * X + x) * E, f.begin() + (y * X + x + 1) * E); }
     return o;
 }
+// A point set in HBM, shared by every copy of the KDTree / Points / Grid that made it.  The set never changes, so the host copy of a
+// field (0 lat, 1 lon, 2 elev, 3 laf, 4 x, 5 y, 6 z) is fetched once, the first time a getter asks for it, and kept.
 struct Handle {
     gpp_points* p = nullptr;
     ~Handle() { if(p) gpp_points_destroy(p); }
+    const vec& field(int k, size_t n) {
+        std::lock_guard<std::mutex> lock(m);
+        if(!have[k]) {
+            host[k].resize(n);
+            check(gpp_points_get(p, k, host[k].data()));
+            have[k] = true;
+        }
+        return host[k];
+    }
+  private:
+    std::mutex m;
+    vec host[7];
+    bool have[7] = {false, false, false, false, false, false, false};
 };
 }   // namespace detail
 
@@ -121,10 +147,116 @@ inline void future_deprecation_warning(const std::string& function, const std::s
     else std::cout << "." << std::endl;
 }
 
-class Points {
+// ---- coordinates, Point (include/gridpp.h:1492-1516,1713-1743) ----------------------------------------------------
+inline bool is_valid_lat(float lat, CoordinateType type) {   // src/api/util.cpp:617-621: a Cartesian y is any valid value
+    if(type == Cartesian) return is_valid(lat);
+    return is_valid(lat) && (lat >= -90.001) && (lat <= 90.001);
+}
+inline bool is_valid_lon(float lon, CoordinateType) { return is_valid(lon); }   // util.cpp:622-624
+// util.cpp:583-615; GPP_EINVAL "Invalid coords" -> std::invalid_argument
+inline bool convert_coordinates(const vec& lats, const vec& lons, CoordinateType type, vec& x_coords, vec& y_coords, vec& z_coords) {
+    const size_t N = lats.size();
+    if(lons.size() != N) throw std::invalid_argument("lats and lons must have the same size");
+    x_coords.resize(N); y_coords.resize(N); z_coords.resize(N);
+    if(N) detail::check(gpp_convert_coordinates(lats.data(), lons.data(), (int)N, (int)type, x_coords.data(), y_coords.data(), z_coords.data()));
+    return true;
+}
+inline bool convert_coordinates(float lat, float lon, CoordinateType type, float& x_coord, float& y_coord, float& z_coord) {
+    detail::check(gpp_convert_coordinates(&lat, &lon, 1, (int)type, &x_coord, &y_coord, &z_coord));
+    return true;
+}
+class Point {   // src/api/point.cpp:5-26
   public:
-    Points() : Points(vec(), vec()) {}
-    Points(vec lats, vec lons, vec elevs = vec(), vec lafs = vec(), CoordinateType type = Geodetic) : mType(type) {
+    Point(float lat, float lon, float elev = MV, float laf = MV, CoordinateType type = Geodetic) : lat(lat), lon(lon), elev(elev), laf(laf), type(type) {
+        if(type == Geodetic) convert_coordinates(lat, lon, type, x, y, z);
+        else { x = lat; y = lon; z = 0; }
+    }
+    Point(float lat, float lon, float elev, float laf, CoordinateType type, float x, float y, float z)
+        : lat(lat), lon(lon), elev(elev), laf(laf), type(type), x(x), y(y), z(z) {}
+    float lat, lon, elev, laf;
+    CoordinateType type;
+    float x, y, z;
+};
+namespace detail {
+// the C-ABI's record of a point: x, y, z, elev, laf, lat, lon
+struct Seven { float f[7]; explicit Seven(const Point& p) : f{p.x, p.y, p.z, p.elev, p.laf, p.lat, p.lon} {} };
+}
+
+// ---- KDTree / Points / Grid (include/gridpp.h:1746-2060) ----------------------------------------------------------
+class Grid;
+class KDTree {
+  public:
+    KDTree(vec lats, vec lons, CoordinateType type = Geodetic) : KDTree(lats, lons, vec(), vec(), type) {}
+    KDTree(CoordinateType type = Geodetic) : KDTree(vec(), vec(), vec(), vec(), type) {}
+    int size() const { return mN; }
+    CoordinateType get_coordinate_type() const { return mType; }
+    vec get_lats() const { return field(0); }
+    vec get_lons() const { return field(1); }
+    const vec& get_x() const { return field(4); }
+    const vec& get_y() const { return field(5); }
+    const vec& get_z() const { return field(6); }
+    ivec get_neighbours(float lat, float lon, float radius, bool include_match = true) const {
+        ivec idx(mN > 0 ? mN : 1); int count = 0;
+        detail::check(gpp_points_get_neighbours(mH->p, lat, lon, radius, include_match, idx.data(), nullptr, (int)idx.size(), &count));
+        idx.resize(count);
+        return idx;
+    }
+    ivec get_neighbours_with_distance(float lat, float lon, float radius, vec& distances, bool include_match = true) const {
+        ivec idx(mN > 0 ? mN : 1); int count = 0;
+        distances.assign(idx.size(), 0);
+        detail::check(gpp_points_get_neighbours(mH->p, lat, lon, radius, include_match, idx.data(), distances.data(), (int)idx.size(), &count));
+        idx.resize(count); distances.resize(count);
+        return idx;
+    }
+    int get_num_neighbours(float lat, float lon, float radius, bool include_match = true) const { return (int)get_neighbours(lat, lon, radius, include_match).size(); }
+    ivec get_closest_neighbours(float lat, float lon, int num, bool include_match = true) const {
+        ivec idx(num > 0 ? num : 1); int count = 0;
+        detail::check(gpp_points_get_closest_neighbours(mH->p, lat, lon, num, include_match, idx.data(), &count));
+        idx.resize(count);
+        return idx;
+    }
+    int get_nearest_neighbour(float lat, float lon, bool include_match = true) const {
+        int i = -1;
+        detail::check(gpp_points_nearest_neighbour(mH->p, &lat, &lon, 1, include_match, &i));
+        return i;
+    }
+    // src/api/kdtree.cpp:107-200, host scalar arithmetic: angles are rounded to float32 by deg2rad, the trigonometry is double
+    static float deg2rad(float deg) { return (float)((double)deg * 3.14159265358979323846 / 180); }
+    static float rad2deg(float rad) { return (float)((double)rad * 180 / 3.14159265358979323846); }
+    static float calc_distance(float lat1, float lon1, float lat2, float lon2, CoordinateType type = Geodetic) {
+        if(type == Cartesian) return planar(lat1, lon1, lat2, lon2);
+        if(lat1 == lat2 && lon1 == lon2) return 0;
+        const double la1 = deg2rad(lat1), la2 = deg2rad(lat2), lo1 = deg2rad(lon1), lo2 = deg2rad(lon2);
+        const double ratio = std::cos(la1) * std::cos(lo1) * std::cos(la2) * std::cos(lo2) + std::cos(la1) * std::sin(lo1) * std::cos(la2) * std::sin(lo2)
+                             + std::sin(la1) * std::sin(la2);
+        return (float)(std::acos(ratio) * radius_earth);
+    }
+    static float calc_distance(const Point& p1, const Point& p2) {
+        if(p1.type != p2.type) throw std::runtime_error("Coordinate types must be the same");
+        return calc_distance(p1.lat, p1.lon, p2.lat, p2.lon, p1.type);
+    }
+    static float calc_distance_fast(float lat1, float lon1, float lat2, float lon2, CoordinateType type = Geodetic) {
+        if(type == Cartesian) return planar(lat1, lon1, lat2, lon2);
+        const double two_pi = 2 * 3.14159265358979323846;
+        const double la1 = deg2rad(lat1), la2 = deg2rad(lat2), lo1 = deg2rad(lon1), lo2 = deg2rad(lon2);
+        double dlon = std::fmod(std::fabs(lo1 - lo2), two_pi);
+        if(dlon > two_pi / 2) dlon = two_pi - dlon;   // the longitudes wrap
+        const double c = std::cos(std::fabs(la2) > std::fabs(la1) ? la2 : la1);
+        const float dx2 = (float)(c * c * dlon * dlon), dy2 = (float)((la1 - la2) * (la1 - la2));
+        return (float)(radius_earth * std::sqrt((double)(dx2 + dy2)));
+    }
+    // (an addition: the reference declares only the float form, gridpp.h:1836; the python mirror has this one too)
+    static float calc_distance_fast(const Point& p1, const Point& p2) {
+        if(p1.type != p2.type) throw std::runtime_error("Coordinate types must be the same");
+        return calc_distance_fast(p1.lat, p1.lon, p2.lat, p2.lon, p1.type);
+    }
+    static float calc_straight_distance(float x0, float y0, float z0, float x1, float y1, float z1) {
+        return std::sqrt((x0 - x1) * (x0 - x1) + (y0 - y1) * (y0 - y1) + (z0 - z1) * (z0 - z1));
+    }
+    static float calc_straight_distance(const Point& p1, const Point& p2) { return calc_straight_distance(p1.x, p1.y, p1.z, p2.x, p2.y, p2.z); }
+    gpp_points* handle() const { return mH->p; }
+  protected:
+    KDTree(const vec& lats, const vec& lons, const vec& elevs, const vec& lafs, CoordinateType type) : mType(type) {
         size_t N = lats.size();
         if(lons.size() != N) throw std::invalid_argument("Cannot create points with unequal lat and lon sizes");
         if(elevs.size() != 0 && elevs.size() != N) throw std::invalid_argument("'elevs' must either be size 0 or the same size at lats/lons");
@@ -134,32 +266,40 @@ class Points {
                                         lafs.size() == N && N ? lafs.data() : nullptr, (int)N, (int)type, &mH->p));
         mN = (int)N;
     }
-    int size() const { return mN; }
-    CoordinateType get_coordinate_type() const { return mType; }
-    vec get_lats() const { return field(0); }
-    vec get_lons() const { return field(1); }
-    vec get_elevs() const { return field(2); }
-    vec get_lafs() const { return field(3); }
-    ivec get_neighbours(float lat, float lon, float radius, bool include_match = true) const {
-        ivec idx(mN > 0 ? mN : 1); int count = 0;
-        detail::check(gpp_points_get_neighbours(mH->p, lat, lon, radius, include_match, idx.data(), nullptr, (int)idx.size(), &count));
-        idx.resize(count);
-        return idx;
-    }
-    int get_num_neighbours(float lat, float lon, float radius, bool include_match = true) const { return (int)get_neighbours(lat, lon, radius, include_match).size(); }
-    int get_nearest_neighbour(float lat, float lon, bool include_match = true) const {
-        int i = -1;
-        detail::check(gpp_points_nearest_neighbour(mH->p, &lat, &lon, 1, include_match, &i));
-        return i;
-    }
-    gpp_points* handle() const { return mH->p; }
-  protected:
-    vec field(int k) const { vec o(mN); detail::check(gpp_points_get(mH->p, k, o.data())); return o; }
+    static float planar(float lat1, float lon1, float lat2, float lon2) { const float dx = lon1 - lon2, dy = lat1 - lat2; return std::sqrt(dx * dx + dy * dy); }
+    const vec& field(int k) const { return mH->field(k, mN); }
     std::shared_ptr<detail::Handle> mH;
     int mN = 0;
     CoordinateType mType = Geodetic;
 };
-typedef Points KDTree;
+
+class Points : public KDTree {   // a KDTree with elevations and land-area fractions (the reference's Points holds one: src/api/points.cpp)
+  public:
+    Points() : Points(vec(), vec()) {}
+    Points(vec lats, vec lons, vec elevs = vec(), vec lafs = vec(), CoordinateType type = Geodetic) : KDTree(lats, lons, elevs, lafs, type) {}
+    Points(KDTree tree, vec elevs = vec(), vec lafs = vec()) : KDTree(tree.get_lats(), tree.get_lons(), elevs, lafs, tree.get_coordinate_type()) {}
+    vec get_elevs() const { return field(2); }
+    vec get_lafs() const { return field(3); }
+    Point get_point(int index) const {   // points.cpp:128-130
+        float f[7];
+        for(int k = 0; k < 7; k++) f[k] = field(k).at(index);   // (single elements of the kept host copies)
+        return Point(f[0], f[1], f[2], f[3], mType, f[4], f[5], f[6]);
+    }
+    ivec get_in_domain_indices(const Grid& grid) const;   // points.cpp:77-92: the points some box of the grid encloses (Grid::get_box)
+    Points get_in_domain(const Grid& grid) const { return subset(get_in_domain_indices(grid)); }   // :93-109 (default coordinate type, as there)
+    Points subset(const ivec& indices) const {            // :131-150
+        const vec &la = field(0), &lo = field(1), &el = field(2), &lf = field(3);
+        const size_t N = indices.size();
+        vec lats(N), lons(N), elevs(N), lafs(N);
+        for(size_t i = 0; i < N; i++) {
+            const int k = indices[i];
+            if(k >= mN) throw std::invalid_argument("Index exceeds number of points");
+            if(k < 0) throw std::invalid_argument("Index is negative");   // (the reference reads before its vectors here)
+            lats[i] = la[k]; lons[i] = lo[k]; elevs[i] = el[k]; lafs[i] = lf[k];
+        }
+        return Points(lats, lons, elevs, lafs);
+    }
+};
 
 class Grid {
   public:
@@ -178,11 +318,27 @@ class Grid {
     }
     ivec size() const { return ivec{mY, mX}; }
     CoordinateType get_coordinate_type() const { return mType; }
+    vec2 get_lats() const { return field2(0); }
+    vec2 get_lons() const { return field2(1); }
+    vec2 get_elevs() const { return field2(2); }
+    vec2 get_lafs() const { return field2(3); }
     ivec get_nearest_neighbour(float lat, float lon, bool include_match = true) const {   // grid.cpp:76-82,108-114
         if(mY * mX == 0) return ivec();
         int i = -1;
         detail::check(gpp_points_nearest_neighbour(mH->p, &lat, &lon, 1, include_match, &i));
         return ivec{i / mX, i % mX};
+    }
+    // the radius and k-nearest queries of the flat set, each index as (y, x) (grid.cpp:56-75)
+    ivec2 get_neighbours(float lat, float lon, float radius, bool include_match = true) const { return yx(flat_neighbours(lat, lon, radius, include_match, nullptr)); }
+    ivec2 get_neighbours_with_distance(float lat, float lon, float radius, vec& distances, bool include_match = true) const {
+        return yx(flat_neighbours(lat, lon, radius, include_match, &distances));
+    }
+    int get_num_neighbours(float lat, float lon, float radius, bool include_match = true) const { return (int)flat_neighbours(lat, lon, radius, include_match, nullptr).size(); }
+    ivec2 get_closest_neighbours(float lat, float lon, int num, bool include_match = true) const {
+        ivec idx(num > 0 ? num : 1); int count = 0;
+        detail::check(gpp_points_get_closest_neighbours(mH->p, lat, lon, num, include_match, idx.data(), &count));
+        idx.resize(count);
+        return yx(idx);
     }
     bool get_box(float lat, float lon, int& Y1_out, int& X1_out, int& Y2_out, int& X2_out) const {   // grid.cpp:149-229
         int inside = 0, box[4] = {-1, -1, -1, -1};
@@ -190,19 +346,68 @@ class Grid {
         Y1_out = box[0]; X1_out = box[1]; Y2_out = box[2]; X2_out = box[3];
         return inside != 0;
     }
+    Points to_points() const { return Points(field(0), field(1), field(2), field(3), mType); }   // grid.cpp:131-145
+    Point get_point(int y_index, int x_index) const {   // grid.cpp:230-233
+        const size_t i = (size_t)y_index * mX + x_index;
+        float f[7];
+        for(int k = 0; k < 7; k++) f[k] = field(k).at(i);
+        return Point(f[0], f[1], f[2], f[3], mType, f[4], f[5], f[6]);
+    }
     gpp_points* handle() const { return mH->p; }
   private:
+    const vec& field(int k) const { return mH->field(k, (size_t)mY * mX); }
+    vec2 field2(int k) const { return detail::unflatten(field(k), mY, mX); }
+    ivec flat_neighbours(float lat, float lon, float radius, bool include_match, vec* distances) const {
+        ivec idx(mY * mX > 0 ? mY * mX : 1); int count = 0;
+        if(distances) distances->assign(idx.size(), 0);
+        detail::check(gpp_points_get_neighbours(mH->p, lat, lon, radius, include_match, idx.data(), distances ? distances->data() : nullptr, (int)idx.size(), &count));
+        idx.resize(count);
+        if(distances) distances->resize(count);
+        return idx;
+    }
+    ivec2 yx(const ivec& flat) const { ivec2 o(flat.size()); for(size_t i = 0; i < flat.size(); i++) o[i] = ivec{flat[i] / mX, flat[i] % mX}; return o; }
     std::shared_ptr<detail::Handle> mH;
     int mY = 0, mX = 0;
     CoordinateType mType = Geodetic;
 };
+inline ivec Points::get_in_domain_indices(const Grid& grid) const {
+    ivec indices;
+    if(mN == 0 || grid.size()[0] * grid.size()[1] == 0) return indices;
+    const vec &lats = field(0), &lons = field(1);
+    ivec inside(mN), boxes(4 * (size_t)mN);
+    detail::check(gpp_grid_get_box(grid.handle(), lats.data(), lons.data(), mN, inside.data(), boxes.data()));
+    for(int i = 0; i < mN; i++) if(inside[i]) indices.push_back(i);
+    return indices;
+}
 
-// ---- structure functions (include/gridpp.h:2069-2343), scalar forms -------------------------------------------
-class StructureFunction {
+// ---- structure functions (include/gridpp.h:2069-2343) -----------------------------------------------------------
+namespace detail {
+// the h, v, w fields of a spatially varying structure in HBM, and the grid they borrow: shared by every copy and clone of the structure
+struct Field {
+    Field(const Grid& g) : grid(g) {}
+    ~Field() { if(f) gpp_field_destroy(f); }
+    Field(const Field&) = delete;
+    Field& operator=(const Field&) = delete;
+    gpp_field* f = nullptr;
+    Grid grid;
+};
+template <class T> struct MinRho { static const float default_min_rho; };   // (a static data member a header can define)
+template <class T> const float MinRho<T>::default_min_rho = 0.0013f;        // structure.cpp:5
+}
+class StructureFunction;
+typedef std::shared_ptr<StructureFunction> StructureFunctionPtr;
+class StructureFunction : public detail::MinRho<void> {
   public:
     virtual ~StructureFunction() {}
     const gpp_structure* c_struct() const { return &mS; }
     float localization_distance() const { float d; detail::check(gpp_structure_localization_distance(&mS, 0.0f, 0.0f, &d)); return d; }
+    float localization_distance(const Point& p) const { float d; detail::check(gpp_structure_localization_distance(&mS, p.lat, p.lon, &d)); return d; }
+    float corr(const Point& p1, const Point& p2) const { return one(p1, p2, 0); }
+    vec corr(const Point& p1, const std::vector<Point>& p2) const { return many(p1, p2, 0); }
+    float corr_background(const Point& p1, const Point& p2) const { return one(p1, p2, 1); }
+    vec corr_background(const Point& p1, const std::vector<Point>& p2) const { return many(p1, p2, 1); }
+    // the descriptor and the shared fields are all a structure function holds: the copy is complete for every derived class
+    StructureFunctionPtr clone() const { return StructureFunctionPtr(new StructureFunction(*this)); }
   protected:
     StructureFunction() { mS = gpp_structure(); }
     void init(int kind, float h, float v, float w, float hmax) {
@@ -212,14 +417,50 @@ class StructureFunction {
         mS.kind = kind; mS.h = h; mS.v = v; mS.w = w;
         detail::check(gpp_structure_min_rho(kind, h, hmax, &mS.min_rho));
     }
+    // (grid, h, v, w, min_rho), e.g. structure.cpp:168-184
+    void init(int kind, const Grid& grid, const vec2& h, const vec2& v, const vec2& w, float min_rho) {
+        size_t Yh, Xh, Yv, Xv, Yw, Xw;
+        const vec fh = detail::flatten(h, Yh, Xh), fv = detail::flatten(v, Yv, Xv), fw = detail::flatten(w, Yw, Xw);
+        mS = gpp_structure();
+        mS.kind = kind; mS.min_rho = min_rho;
+        if(Yh * Xh == 1 && Yv * Xv == 1 && Yw * Xw == 1) { mS.h = fh[0]; mS.v = fv[0]; mS.w = fw[0]; return; }   // not spatial (:174-176)
+        const size_t Y = grid.size()[0], X = grid.size()[1];
+        if(Yh != Y || Xh != X || Yv != Y || Xv != X || Yw != Y || Xw != X) throw std::invalid_argument("Grid size not the same as scale size");
+        auto field = std::make_shared<detail::Field>(grid);
+        detail::check(gpp_field_create(field->grid.handle(), fh.data(), fv.data(), fw.data(), kind, min_rho, &field->f));
+        mS.field = field->f;
+        mFields.push_back(field);
+    }
+    void share_fields(const StructureFunction& other) { mFields.insert(mFields.end(), other.mFields.begin(), other.mFields.end()); }
     gpp_structure mS;
+    std::vector<std::shared_ptr<detail::Field> > mFields;   // what mS.field / field_v / field_w point into
+  private:
+    float one(const Point& p1, const Point& p2, int background) const {
+        float rho;
+        detail::check(gpp_structure_corr(&mS, detail::Seven(p1).f, detail::Seven(p2).f, background, &rho));
+        return rho;
+    }
+    vec many(const Point& p1, const std::vector<Point>& p2, int background) const {   // one launch for the whole vector
+        vec rec; rec.reserve(7 * p2.size());
+        for(const Point& p : p2) { const detail::Seven s(p); rec.insert(rec.end(), s.f, s.f + 7); }
+        vec rho(p2.size());
+        detail::check(gpp_structure_corr_many(&mS, detail::Seven(p1).f, rec.data(), (long long)p2.size(), background, rho.data()));
+        return rho;
+    }
 };
-class BarnesStructure : public StructureFunction { public: BarnesStructure(float h, float v = 0, float w = 0, float hmax = MV) { init(GPP_SK_BARNES, h, v, w, hmax); } };
+#define GPP_SPATIAL_STRUCTURE(Name, KIND)                                                                                           \
+    class Name : public StructureFunction {                                                                                         \
+      public:                                                                                                                       \
+        Name(float h, float v = 0, float w = 0, float hmax = MV) { init(KIND, h, v, w, hmax); }                                      \
+        Name(Grid grid, vec2 h, vec2 v, vec2 w, float min_rho = StructureFunction::default_min_rho) { init(KIND, grid, h, v, w, min_rho); } \
+    }
+GPP_SPATIAL_STRUCTURE(BarnesStructure, GPP_SK_BARNES);       // structure.cpp:143-184
+GPP_SPATIAL_STRUCTURE(SoarStructure, GPP_SK_SOAR);           // :317-341
+GPP_SPATIAL_STRUCTURE(ToarStructure, GPP_SK_TOAR);           // :467-491
+GPP_SPATIAL_STRUCTURE(PowerlawStructure, GPP_SK_POWERLAW);   // :618-642
+GPP_SPATIAL_STRUCTURE(LinearStructure, GPP_SK_LINEAR);       // :765-789
+#undef GPP_SPATIAL_STRUCTURE
 class CressmanStructure : public StructureFunction { public: CressmanStructure(float h, float v = 0, float w = 0) { init(GPP_SK_CRESSMAN, h, v, w, MV); } };
-class SoarStructure : public StructureFunction { public: SoarStructure(float h, float v = 0, float w = 0, float hmax = MV) { init(GPP_SK_SOAR, h, v, w, hmax); } };
-class ToarStructure : public StructureFunction { public: ToarStructure(float h, float v = 0, float w = 0, float hmax = MV) { init(GPP_SK_TOAR, h, v, w, hmax); } };
-class PowerlawStructure : public StructureFunction { public: PowerlawStructure(float h, float v = 0, float w = 0, float hmax = MV) { init(GPP_SK_POWERLAW, h, v, w, hmax); } };
-class LinearStructure : public StructureFunction { public: LinearStructure(float h, float v = 0, float w = 0, float hmax = MV) { init(GPP_SK_LINEAR, h, v, w, hmax); } };
 class MultipleStructure : public StructureFunction {   // src/api/structure.cpp:90-138
   public:
     MultipleStructure(const StructureFunction& sh, const StructureFunction& sv, const StructureFunction& sw) {
@@ -228,11 +469,12 @@ class MultipleStructure : public StructureFunction {   // src/api/structure.cpp:
         mS.v = v->v; mS.w = w->w;
         mS.kind_v = (v->kind_v ? v->kind_v - 1 : v->kind) + 1;
         mS.kind_w = (w->kind_w ? w->kind_w - 1 : w->kind) + 1;
-        mS.loc = sh.localization_distance();
-        mS.flags = GPP_ST_HAS_LOC;
+        if(h->field) { mS.loc = 0; mS.flags = 0; }   // the localization distance is the field's, at the first point
+        else { mS.loc = sh.localization_distance(); mS.flags = GPP_ST_HAS_LOC; }
         mS.cv_dist = 0;
         // (a nested MultipleStructure contributes the field of its own vertical / laf component)
         mS.field = h->field; mS.field_v = v->kind_v ? v->field_v : v->field; mS.field_w = w->kind_w ? w->field_w : w->field;
+        share_fields(sh); share_fields(sv); share_fields(sw);
     }
 };
 class CrossValidation : public StructureFunction {     // src/api/structure.cpp:910-944
@@ -242,8 +484,54 @@ class CrossValidation : public StructureFunction {     // src/api/structure.cpp:
         mS = *structure.c_struct();
         mS.flags |= GPP_ST_CV;
         mS.cv_dist = dist;
+        share_fields(structure);
     }
 };
+
+// ---- container helpers (include/gridpp.h:1509-1660; src/api/util.cpp:217-225,427-504) -----------------------------
+inline int num_missing_values(const vec2& iArray) {
+    int count = 0;
+    for(const vec& row : iArray) for(float value : row) count += !is_valid(value);
+    return count;
+}
+inline vec2 init_vec2(int Y, int X, float value = MV) { return vec2(Y, vec(X, value)); }
+inline ivec2 init_ivec2(int Y, int X, int value) { return ivec2(Y, ivec(X, value)); }
+inline vec3 init_vec3(int Y, int X, int E, float value = MV) { return vec3(Y, vec2(X, vec(E, value))); }
+inline ivec3 init_ivec3(int Y, int X, int E, int value) { return ivec3(Y, ivec2(X, ivec(E, value))); }
+inline bool compatible_size(const Grid& grid, const vec2& v) { return v.size() == 0 || (grid.size()[0] == (int)v.size() && grid.size()[1] == (int)v[0].size()); }
+// (v is [T][Y][X]; a first level without rows passes, util.cpp:430-432)
+inline bool compatible_size(const Grid& grid, const vec3& v) {
+    return v.size() == 0 || v[0].size() == 0 || (grid.size()[0] == (int)v[0].size() && grid.size()[1] == (int)v[0][0].size());
+}
+inline bool compatible_size(const Points& points, const vec& v) { return points.size() == (int)v.size(); }
+inline bool compatible_size(const Points& points, const vec2& v) { return v.size() == 0 || points.size() == (int)v[0].size(); }
+inline bool compatible_size(const vec2& a, const vec2& b) {
+    if(a.size() != b.size()) return false;
+    for(size_t y = 0; y < a.size(); y++) if(a[y].size() != b[y].size()) return false;
+    return true;
+}
+inline bool compatible_size(const vec2& a, const vec3& b) {   // the first two sizes only (util.cpp:448-461)
+    if(a.size() != b.size()) return false;
+    return a.size() == 0 || a[0].size() == b[0].size();
+}
+inline bool compatible_size(const vec3& a, const vec3& b) {
+    if(a.size() != b.size()) return false;
+    for(size_t t = 0; t < a.size(); t++) {
+        if(a[t].size() != b[t].size()) return false;
+        for(size_t y = 0; y < a[t].size(); y++) if(a[t][y].size() != b[t][y].size()) return false;
+    }
+    return true;
+}
+// include/gridpp.h:462, src/api/corr_points.cpp:26-131: (L, K) static correlations between a set of points and a set of knots
+inline vec2 staticcorr_points(const Points& points, const Points& knots, const StructureFunction& structure, int max_points) {
+    if(max_points < 0) throw std::invalid_argument("max_points must be >= 0");
+    if(points.get_coordinate_type() != knots.get_coordinate_type())
+        throw std::invalid_argument("Both background grid and observations points must be of same coordinate type (lat/lon or x/y)");
+    const size_t L = points.size(), K = knots.size();
+    vec out(L * K);
+    if(!out.empty()) detail::check(gpp_staticcorr_points(points.handle(), knots.handle(), structure.c_struct(), max_points, out.data(), GPP_MEM_HOST));
+    return detail::unflatten(out, L, K);
+}
 
 // ---- optimal interpolation (include/gridpp.h:162-248) -------------------------------------------------
 inline vec optimal_interpolation_full(const Points& bpoints, const vec& background, const vec& bvariance, const Points& points,

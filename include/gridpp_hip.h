@@ -337,6 +337,14 @@ int gpp_structure_localization_distance(const gpp_structure* s, float lat, float
 /* corr (background = 0) / corr_background (background = 1) for one pair of points given as
  * (x, y, z, elev, laf, lat, lon) -- runs the same device code as the OI kernels */
 int gpp_structure_corr(const gpp_structure* s, const float p1[7], const float p2[7], int background, float* rho);
+/* corr / corr_background of p1 against n points, StructureFunction::corr(const Point&, const std::vector<Point>&)
+ * (include/gridpp.h:2078,2086; structure.cpp:13-25,113-135,231-267): the scales are taken at p1 ONCE (structure.cpp:234-243) and all
+ * pairs run in one kernel launch over the device code of gpp_structure_corr, so the values equal that entry's bit for bit.
+ * p2: n records of 7 floats (x, y, z, elev, laf, lat, lon), host memory; rho: n floats, host memory.  n == 0: nothing is done. */
+int gpp_structure_corr_many(const gpp_structure* s, const float p1[7], const float* p2, long long n, int background, float* rho);
+/* the same against every point of a Points / Grid handle (its x, y, z, elev, laf are already in HBM: nothing is uploaded);
+ * rho: size of the handle (row-major for a grid), GPP_MEM_HOST or GPP_MEM_DEVICE.  An empty handle: nothing is done. */
+int gpp_structure_corr_points(const gpp_structure* s, const float p1[7], gpp_points* to, int background, float* rho, int mem);
 
 /* gridpp::staticcorr_points (src/api/corr_points.cpp:26-131): out [size of points][size of knots] = corr_background(point,
  * knot) for the knots a point keeps (inside its localization radius, rho > 0, the max_points largest if there are more; 0
