@@ -35,7 +35,10 @@ else:
     # (DESIGN.md 4.12): they too are asked for by their own names, gridpp_amd.Gamma and gridpp_amd.gamma_inv.
     # get_optimal_threshold and metric_optimizer_curve return the exact optimum over the plateaus of the score where the reference returns
     # wherever Boost's brent_find_minima ends: gridpp_amd.get_optimal_threshold, gridpp_amd.metric_optimizer_curve.
-    for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve"):
+    # optimal_interpolation_gain and its OiGain have no counterpart in the reference at all (the selections and weights of
+    # optimal_interpolation computed once per geometry and applied to any number of fields): gridpp_amd.optimal_interpolation_gain.
+    for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve",
+                  "optimal_interpolation_gain", "OiGain"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

@@ -793,6 +793,143 @@ def optimal_interpolation_full(bgrid, background, bvariance, points, obs, obs_va
     return out, var
 
 
+# ---- the reusable OI gain (include/gridpp_hip.h: gpp_oi_gain_*; no counterpart in the reference) ------------------
+class OiGain:
+    """What optimal_interpolation_gain returns: for every background point the selected observations, their weights and w . g."""
+
+    def __init__(self, handle, bgrid, stations, max_points):
+        self._h, self._nd, self._shape, self._S, self.max_points = handle, (2 if isinstance(bgrid, Grid) else 1), _out_shape(bgrid), stations, max_points
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:   # noqa: BLE001  (interpreter shutdown)
+            pass
+
+    def release(self):
+        """gpp_oi_gain_destroy: returns the HBM the gain holds (`nbytes`); the gain cannot be used afterwards."""
+        h, self._h = self._h, None
+        if h:
+            check(lib().gpp_oi_gain_destroy(h))
+
+    def _handle(self):
+        if not self._h:
+            raise RuntimeError("the gain was released")
+        return self._h
+
+    def apply(self, background, pobs, pbackground, allow_extrapolation=True):
+        """The analysis of a field, (Y, X) / (N,), or of a stack of E fields in gridpp's cube layout, (Y, X, E) / (N, E) with
+        pbackground (S, E) and pobs (S,) or (S, E) -- the argument shapes of optimal_interpolation_ensi.  numpy in, numpy out; torch CUDA
+        tensors in, a torch CUDA tensor out.  ValueError naming the lowest (field, station) where a usable station has an invalid pobs or
+        pbackground."""
+        h = self._handle()
+        nd = _ndim(background)
+        if nd not in (self._nd, self._nd + 1):
+            raise RuntimeError("background must have %d or %d dimensions" % (self._nd, self._nd + 1))
+        stack = nd == self._nd + 1
+        f64 = _wants_f64(background)
+        background = _m.field(background, nd, "background", f64)
+        if _shape(background)[:self._nd] != self._shape:
+            raise ValueError("input field %s is not the same size as the grid %s" % (_shape(background), self._shape))
+        E = _shape(background)[-1] if stack else 1
+        if E < 1:
+            raise ValueError("background holds no fields")
+        pobs = _m.field(pobs, None, "pobs", f64)
+        pbackground = _m.field(pbackground, None, "pbackground", f64)
+        S = self._S
+        if _shape(pobs) not in ((S,), (S, E)):
+            raise ValueError("Observations %s and points (%d), fields (%d) size mismatch" % (_shape(pobs), S, E))
+        if _shape(pbackground) != (S, E) and not (E == 1 and _shape(pbackground) == (S,)):
+            raise ValueError("Background at points %s and points (%d), fields (%d) size mismatch" % (_shape(pbackground), S, E))
+        per_field = int(len(_shape(pobs)) == 2 and E > 1)
+        mem = _m.flags(f64, background, pobs, pbackground)
+        out = _empty_like_field(_shape(background), background)
+        check(lib().gpp_oi_gain_apply(h, _ptr(background), int(E), _ptr(pobs), per_field, _ptr(pbackground), int(bool(allow_extrapolation)),
+                                      _ptr(out), mem))
+        return out
+
+    def analysis_variance(self, bvariance):
+        """The analysis variance of optimal_interpolation_full for this background variance (with the gain's ratios)."""
+        h = self._handle()
+        bvariance = _m.field(bvariance, self._nd, "bvariance", False)
+        if _shape(bvariance) != self._shape:
+            raise ValueError("Input bvariance is not the same size as the grid")
+        return _m.run(lib().gpp_oi_gain_variance, h, _ptr(bvariance), out_shape=self._shape, like=bvariance, mem=_m.flags(False, bvariance))
+
+    def _info(self):
+        cells, nbytes = C.c_longlong(), C.c_longlong()
+        stations, mp, largest = C.c_int(), C.c_int(), C.c_int()
+        check(lib().gpp_oi_gain_info(self._handle(), C.byref(cells), C.byref(stations), C.byref(mp), C.byref(nbytes), C.byref(largest)))
+        return cells.value, stations.value, mp.value, nbytes.value, largest.value
+
+    @property
+    def nbytes(self):
+        """HBM the gain holds now: about cells * max_points * 12 bytes plus 9 per cell (and the innovation table of its last apply)."""
+        return self._info()[3]
+
+    @property
+    def largest_selection(self):
+        return self._info()[4]
+
+    def _selection(self, which):
+        n = int(np.prod(self._shape))
+        counts = np.empty(self._shape, np.int32) if which == 0 else None
+        indices = np.empty(self._shape + (self.max_points,), np.int32) if which == 1 else None
+        weights = np.empty(self._shape + (self.max_points,), np.float64) if which == 2 else None
+        if n:
+            check(lib().gpp_oi_gain_selection(self._handle(), _ptr(counts), _ptr(indices), _ptr(weights), _capi.MEM_HOST))
+        return (counts, indices, weights)[which]
+
+    def counts(self):
+        """selected observations per background point: int32, the shape of a field"""
+        return self._selection(0)
+
+    def indices(self):
+        """their indices into the observation arrays, ascending, -1 behind the selection: int32, field shape + (max_points,)"""
+        return self._selection(1)
+
+    def weights(self):
+        """their weights w = G (P + R)^-1 (float64), 0 behind the selection: field shape + (max_points,)"""
+        return self._selection(2)
+
+
+def optimal_interpolation_gain(bgrid, points, pratios, structure, max_points, usable=None):
+    """Everything of optimal_interpolation that does not depend on a value, computed once: which observations every background point
+    selects (src/api/oi.cpp:229-287) and their weights (:304-317).  The returned OiGain analyses any number of fields with it --
+
+        gain = optimal_interpolation_gain(grid, points, pratios, structure, 30)
+        out = gain.apply(background, pobs, pbackground)          # = optimal_interpolation(grid, background, points, pobs, pratios, pbackground, structure, 30)
+        out = gain.apply(background_yxe, pobs, pbackground_se)   # E fields in one call
+
+    instead of a loop of optimal_interpolation calls over members, hours or perturbed observations with the same grid, stations,
+    ratios, structure and max_points.  pratios is optimal_interpolation's; a caller of optimal_interpolation_full passes
+    obs_variance / bvariance_at_points, divided in float32 as oi.cpp:194 does.  usable (S booleans, None: every station): the
+    reference drops a station whose pobs or pbackground is missing in each call; a gain is told at construction which stations to
+    leave out, and apply raises when a usable station has a missing value.  1 <= max_points <= 62.  The gain holds about
+    cells * max_points * 12 bytes of HBM (5.9 GB for 4000 x 4000 points and max_points 30; `nbytes`) until release() / gpp_oi_gain_destroy
+    or until it is garbage-collected."""
+    if not isinstance(bgrid, (Grid, Points)) or not isinstance(points, Points):
+        raise TypeError("bgrid must be a Grid or Points, points a Points")
+    if bgrid.get_coordinate_type() != points.get_coordinate_type():
+        raise ValueError("Both background and observations points must be of same coordinate type (lat/lon or x/y)")
+    max_points = int(max_points)
+    if max_points < 1:
+        raise ValueError("max_points must be >= 1: a gain holds max_points columns per background point")
+    if max_points > _capi.OI_GAIN_MAX_POINTS:
+        raise ValueError("max_points must be <= %d (GPP_OI_GAIN_MAX_POINTS)" % _capi.OI_GAIN_MAX_POINTS)
+    S = points.size()
+    pratios = np.ascontiguousarray(np.asarray(pratios.cpu() if _is_dev(pratios) else pratios), dtype=np.float32)
+    if pratios.ndim != 1 or pratios.shape[0] != S:
+        raise ValueError("Ratios (%s) and points (%d) size mismatch" % (pratios.shape, S))
+    if usable is not None:
+        usable = np.ascontiguousarray(np.asarray(usable.cpu() if _is_dev(usable) else usable).astype(bool), dtype=np.uint8)
+        if usable.ndim != 1 or usable.shape[0] != S:
+            raise ValueError("usable (%s) and points (%d) size mismatch" % (usable.shape, S))
+    handle = C.c_void_p()
+    check(lib().gpp_oi_gain_create(bgrid._h, points._h, _ptr(pratios), _ptr(usable), _structure(structure), max_points, C.byref(handle)))
+    return OiGain(handle, bgrid, S, max_points)
+
+
 def oi_last_stats():
     s = _capi.gpp_oi_stats()
     check(lib().gpp_oi_last_stats(C.byref(s)))

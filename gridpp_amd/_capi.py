@@ -17,6 +17,7 @@ SCORE_TILE_COLS, SCORE_TILE_ROWS, SCORE_FUSED_MAXHW = 64, 32, 16   # GPP_SCORE_*
 POINTWISE_BLOCK, POINTWISE_MAX_BLOCKS = 256, 2048   # GPP_POINTWISE_* of include/gridpp_hip.h
 GAMMA_BLOCK, GAMMA_MAX_BLOCKS = 256, 2048   # GPP_GAMMA_* of include/gridpp_hip.h
 MO_TILE_ITEMS, MO_GROUP = 2048, 4   # GPP_MO_* of include/gridpp_hip.h
+OI_GAIN_MAX_POINTS = 62   # GPP_OI_GAIN_MAX_POINTS of include/gridpp_hip.h
 TRANSFORM_IDENTITY, TRANSFORM_LOG, TRANSFORM_BOXCOX, TRANSFORM_STARTED_BOXCOX = 0, 1, 2, 3   # GPP_TRANSFORM_* of include/gridpp_hip.h
 (DIAG_DEWPOINT, DIAG_RELATIVE_HUMIDITY, DIAG_WETBULB, DIAG_PRESSURE, DIAG_SEA_LEVEL_PRESSURE, DIAG_QNH, DIAG_WIND_SPEED,
  DIAG_WIND_DIRECTION) = range(8)   # GPP_DIAG_* of include/gridpp_hip.h
@@ -146,6 +147,12 @@ SIGNATURES = {
     "gpp_gamma_transform": [vp, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, vp, C.c_int],
     "gpp_gamma_inv_scalar": [C.c_float, C.c_float, C.c_float, fp],
     "gpp_gamma_transform_scalar": [C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, fp],
+    "gpp_oi_gain_create": [vp, vp, vp, vp, C.POINTER(gpp_structure), C.c_int, C.POINTER(vp)],
+    "gpp_oi_gain_apply": [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_oi_gain_variance": [vp, vp, vp, C.c_int],
+    "gpp_oi_gain_info": [vp, C.POINTER(C.c_longlong), ip, ip, C.POINTER(C.c_longlong), ip],
+    "gpp_oi_gain_selection": [vp, vp, vp, vp, C.c_int],
+    "gpp_oi_gain_destroy": [vp],
 }
 STRING_GETTERS = ("gpp_last_error", "gpp_version")
 

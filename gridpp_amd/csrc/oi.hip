@@ -1440,6 +1440,22 @@ void gpp_bind_field(DevStructure& d, const gpp_structure* s, gpp_points* bgrid, 
     }
     d.obs_idx = oi;
 }
+// What the candidate scan takes from the observation index and from max_points (everything of ScanArgs but the per-call observation block
+// `pgeo`, the structure and the statistics pointer); N: the list capacity of the calling kernel
+void gpp_scan_geometry(ScanArgs& s, const gpp_obs_index* ix, const int S, const int max_points, const int N) {
+    s.smeta = ix->d_smeta.p; s.bin_start = ix->d_bin_start.p;
+    s.axis_a = ix->axis_a; s.axis_b = ix->axis_b; s.nbx = ix->nbx; s.nby = ix->nby;
+    s.amin = ix->amin; s.bmin = ix->bmin; s.inv_s = ix->inv_s;
+    s.max_points = max_points;
+    const double occ = (double)S / ((double)ix->nbx * ix->nby);
+    const int kk = (max_points > 0 && max_points <= N) ? max_points : N;
+    s.q0 = std::max(1, std::min(8, (int)std::ceil(0.5 * (std::sqrt(1.6 * kk / std::max(occ, 1e-3)) - 1.0))));
+    // expected distance of the kk-th nearest observation: k_oi_union looks for its bulk disc below 1.5x that and then
+    // visits rings 0.15x wide
+    const double r_k = std::sqrt(kk / (3.14159265358979 * std::max(occ, 1e-3))) / ix->inv_s;
+    s.ring_r0 = (float)(1.5 * r_k); s.ring_dr = (float)(0.15 * r_k);
+    s.K = kk;
+}
 
 extern "C" int gpp_field_create(gpp_points* grid, const float* h, const float* v, const float* w, int kind, float min_rho, gpp_field** out) {
     GPP_TRY
@@ -1775,21 +1791,11 @@ struct OiCall {
             a.tiles_x = (a.nx + tw - 1) / tw; a.ntiles = a.tiles_x * ((a.ny + th - 1) / th);
         }
         else { a.tiles_x = 0; a.ntiles = (C + 63) / 64; }
-        a.s.smeta = ix->d_smeta.p; a.s.bin_start = ix->d_bin_start.p; a.ogeo = ix->d_ogeo.p;
-        a.S = S; a.s.axis_a = ix->axis_a; a.s.axis_b = ix->axis_b; a.s.nbx = ix->nbx; a.s.nby = ix->nby;
-        a.s.amin = ix->amin; a.s.bmin = ix->bmin; a.s.inv_s = ix->inv_s;
+        a.ogeo = ix->d_ogeo.p; a.S = S;
+        gpp_scan_geometry(a.s, ix, S, max_points, N);
         a.s.st = gpp_resolve_structure(st);
         gpp_bind_field(a.s.st, st, bgrid, points, ws.cell_idx, ws.obs_idx);
-        a.s.max_points = max_points;
-        { const double occ = (double)S / ((double)ix->nbx * ix->nby);
-          const int kk = (max_points > 0 && max_points <= N) ? max_points : N;
-          a.s.q0 = std::max(1, std::min(8, (int)std::ceil(0.5 * (std::sqrt(1.6 * kk / std::max(occ, 1e-3)) - 1.0))));
-          // expected distance of the kk-th nearest observation: k_oi_union looks for its bulk disc below 1.5x that and then
-          // visits rings 0.15x wide
-          const double r_k = std::sqrt(kk / (3.14159265358979 * std::max(occ, 1e-3))) / ix->inv_s;
-          a.s.ring_r0 = (float)(1.5 * r_k); a.s.ring_dr = (float)(0.15 * r_k); }
         a.allow_extrap = allow_extrapolation ? 1 : 0;
-        a.s.K = (max_points > 0 && max_points <= N) ? max_points : N;
         a.debug = timing_env("GPP_OI_DEBUG") ? atoi(timing_env("GPP_OI_DEBUG")) : 0;
         a.tile0 = 0; a.tile_n = a.ntiles;
     }

@@ -542,6 +542,7 @@ struct ScanArgs {
     float ring_r0, ring_dr;  // k_oi_union: upper bound of the bulk disc / ring width of the phase-1 visiting order (projected distance from the tile centre)
     unsigned long long* scan_stats;   // optional: [0] candidates iterated, [1] wave-level survivor-branch executions
 };
+void gpp_scan_geometry(ScanArgs& s, const gpp_obs_index* ix, int S, int max_points, int N);   // oi.hip: the index, max_points and the visiting order
 
 // Per-tile candidate scan (src/api/oi.cpp:229-273 for 64 cells at once).  On return every lane holds `cnt` 64-bit
 // keys (rho bits << 32 | ~observation index) in keys[0..cnt)[lane]: the observations the reference would keep for

@@ -661,6 +661,40 @@ int gpp_debug_obs_index(gpp_points* points, int* dims, float* geom, int* bin_sta
 int gpp_wait(void);
 int gpp_pending(int* count);
 
+/* ---- the reusable OI gain (no counterpart in the reference; gridpp_amd/csrc/oi_gain.hip) -----------------------------
+ * In a loop of optimal_interpolation calls over ensemble members, hours or perturbed observations the grid, the stations, the ratios, the
+ * structure function and max_points stay the same and only values change.  The candidate scan and the factorisation depend on none of the
+ * values (src/api/oi.cpp:229-317): a gain holds their result -- for every background point the observations the reference would select,
+ * their weights w = G (P + R)^-1 as doubles and a = w . g -- and analyses any number of fields with it:
+ *     out[cell, e] = background[cell, e] + clamp(sum_k w[cell, k] * d[idx[cell, k], e]),   d = (double) pobs - (double) pbackground
+ * (the sum in double, the clamp of oi.cpp:318-334 over the selected d of that cell and field when allow_extrapolation is 0, the cast to
+ * float32 last; an invalid background value and a cell without a selection pass through).  A gain holds about cells * max_points * 12
+ * bytes of HBM until gpp_oi_gain_destroy; it copies what it needs, so the Grid, Points and structure it was built from may be destroyed
+ * first, and it shares no workspace with the OI calls (which may run, GPP_ASYNC or not, between its operations).  GPP_ASYNC is ignored here. */
+#define GPP_OI_GAIN_MAX_POINTS 62   /* what the register-tile kernels of optimal_interpolation serve; a lane of a wave per column */
+typedef struct gpp_oi_gain gpp_oi_gain;
+/* pratios: S host floats -- the `pratios` of optimal_interpolation; a caller of optimal_interpolation_full passes obs_variance /
+ * bvariance_at_points divided in float32 (oi.cpp:194).  usable: S host bytes, NULL = every station; a station with missing values in ANY of
+ * the fields to come is marked unusable here (the reference drops it per call, oi.cpp:252).  GPP_EINVAL before any device work: differing
+ * coordinate types (the text of oi.cpp:155-157), max_points < 1 (a gain has max_points columns per cell: 0, "no limit", has no fixed
+ * width), max_points > GPP_OI_GAIN_MAX_POINTS.  No observations, or none usable: a valid gain without selections.  GPP_ERUNTIME for an
+ * exactly singular local system, as gpp_optimal_interpolation_full on the same inputs. */
+int gpp_oi_gain_create(gpp_points* bgrid, gpp_points* points, const float* pratios, const unsigned char* usable,
+                       const gpp_structure* structure, int max_points, gpp_oi_gain** gain);
+/* background, out: [cells][ne] (gridpp's cube layout, the field index innermost: (Y, X, E) or (N, E)); pbackground: [S][ne]; pobs: [S]
+ * (pobs_per_field 0) or [S][ne]; `mem` as everywhere, GPP_HOST_F64 for the three inputs.  GPP_EINVAL naming the lowest offending
+ * (field, station) when pobs or pbackground is invalid at a usable station.  From 16 fields on a wave runs along the fields of a cell. */
+int gpp_oi_gain_apply(gpp_oi_gain* gain, const float* background, int ne, const float* pobs, int pobs_per_field, const float* pbackground,
+                      int allow_extrapolation, float* out, int mem);
+/* the analysis variance of optimal_interpolation_full: bvariance * (1 - a) where the cell has a selection, bvariance elsewhere */
+int gpp_oi_gain_variance(gpp_oi_gain* gain, const float* bvariance, float* out, int mem);
+/* any pointer may be NULL; bytes: the HBM the gain holds now (the planes and the innovation table of its last apply) */
+int gpp_oi_gain_info(const gpp_oi_gain* gain, long long* cells, int* stations, int* max_points, long long* bytes, int* largest_selection);
+/* counts[cells] (int), indices[cells][max_points] (int, the caller's observation order, ascending, -1 behind the selection),
+ * weights[cells][max_points] (double, 0 behind the selection); any of them may be NULL; `mem`: where the three arrays live */
+int gpp_oi_gain_selection(gpp_oi_gain* gain, int* counts, int* indices, double* weights, int mem);
+int gpp_oi_gain_destroy(gpp_oi_gain* gain);
+
 #ifdef __cplusplus
 }
 #endif
