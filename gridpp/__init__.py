@@ -37,8 +37,10 @@ else:
     # wherever Boost's brent_find_minima ends: gridpp_amd.get_optimal_threshold, gridpp_amd.metric_optimizer_curve.
     # optimal_interpolation_gain and its OiGain have no counterpart in the reference at all (the selections and weights of
     # optimal_interpolation computed once per geometry and applied to any number of fields): gridpp_amd.optimal_interpolation_gain.
+    # calc_quantiles and quantile_mapping_curves have no counterpart in the reference either (many quantiles of every row from
+    # one sort, and one quantile-mapping curve per cell for apply_curve): gridpp_amd.calc_quantiles, gridpp_amd.quantile_mapping_curves.
     for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve",
-                  "optimal_interpolation_gain", "OiGain"):
+                  "optimal_interpolation_gain", "OiGain", "calc_quantiles", "quantile_mapping_curves"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

@@ -2038,6 +2038,51 @@ def calc_quantile(array, quantile):
     return _rows_call(lib().gpp_calc_quantile, a, 1 if len(shp) == 1 else shp[0], shp[-1], _ptr(qq), 1, mem=_m.flags(False, a, qq))
 
 
+def _levels(quantiles):
+    """the levels of calc_quantiles / quantile_mapping_curves: a 1-D sequence -> host float32 (a device tensor is copied to the host)"""
+    return _vec(quantiles.cpu().numpy() if _is_dev(quantiles) else quantiles, 1, "quantiles")
+
+
+def calc_quantiles(array, quantiles):
+    """Many quantiles of every row in one call: (N,) -> (Q,), (R, N) -> (R, Q), (Y, X, N) -> (Y, X, Q), where out[..., j] holds exactly the
+    bits of calc_quantile(row, quantiles[j]).  Host arrays or torch CUDA tensors; the result lives where the input does.  `quantiles` is a
+    1-D sequence on the host (a device tensor is copied there), in any order, repeats allowed; a NaN level gives NaN.  Rows of up to 8192
+    values are sorted once in LDS and every level picked out of the sorted row.  RuntimeError for an array that has not
+    1, 2 or 3 dimensions, ValueError for a level below 0 or above 1.  No counterpart in the reference: not part of the `gridpp` alias."""
+    a = _rows_array(array, 3)
+    q = _levels(quantiles)
+    if np.any((q < 0) | (q > 1)):
+        raise ValueError("calc_quantiles: Quantiles must be between 0 and 1 inclusive")
+    shp = _shape(a)
+    rows, nq = int(np.prod(shp[:-1], dtype=np.int64)), q.shape[0]
+    if rows == 0 or nq == 0:
+        return _empty_like_field(shp[:-1] + (nq,), a)
+    return _m.run(lib().gpp_calc_quantiles, _ptr(a), rows, shp[-1], _ptr(q), nq, out_shape=(rows, nq), like=a,
+                  mem=_m.flags(False, a)).reshape(shp[:-1] + (nq,))
+
+
+def quantile_mapping_curves(ref, fcst, quantiles):
+    """One quantile-mapping curve per cell -> (curve_ref, curve_fcst) for cubes ref (Y, X, Tr) and fcst (Y, X, Tf): (Y, X, Q) each, with
+    curve_*[y, x, j] = calc_quantile(that cell's values, quantiles[j]); the pair is what apply_curve(fcst (Y, X), curve_ref, curve_fcst, ...)
+    takes, and it lives where the cubes do (host arrays or torch CUDA tensors).  Tr and Tf may differ.
+
+    Unlike the 1-D quantile_mapping_curve these are TRUE quantiles of each cell's valid values (calc_quantile's interpolation between order
+    statistics).  The reference's 1-D function with quantiles indexes into the inputs as given (src/api/quantile_mapping.cpp:41-42), and the
+    1-D function here reproduces that.  ValueError: first two dimensions that differ, host and device inputs mixed, empty quantiles (the
+    sorted-rows form of the 1-D function is not built per cell), a level that is NaN or outside [0, 1] (a NaN knot is useless in a curve).
+    No counterpart in the reference: not part of the `gridpp` alias."""
+    r, f = _m.field(ref, 3, "ref"), _m.field(fcst, 3, "fcst")
+    if _shape(r)[:2] != _shape(f)[:2]:
+        raise ValueError("quantile_mapping_curves: ref and fcst must have the same first two dimensions")
+    _mem(r, f)
+    q = _levels(quantiles)
+    if q.shape[0] == 0:
+        raise ValueError("quantile_mapping_curves: empty quantiles: the sorted-rows form is not built")
+    if not np.all((q >= 0) & (q <= 1)):   # (NaN fails)
+        raise ValueError("Quantiles must be >= 0 and <= 1")
+    return calc_quantiles(r, q), calc_quantiles(f, q)
+
+
 def _even_quantiles(values, num, only_valid):
     dev = _is_dev(values)
     v = _m.field(values).reshape(-1)

@@ -25,19 +25,11 @@ using namespace gpp;
 
 #include "row_stats.h"
 
-#define RS_TILE_MAXLEN 160        // (MEMBER_EC of neighbourhood.hip: rows up to this length are selected out of LDS)
 #define RS_SPLIT_MINLEN (1 << 15) // default dispatch: rows at least this long ...
 #define RS_SPLIT_MAXROWS 2048     // ... and at most this many of them take several workgroups per row (measured: DESIGN.md 4.14)
-#define RS_INV 0xFFFFFFFFu        // key of an invalid value: no finite float maps to it
+// (RS_TILE_MAXLEN, RS_INV, rs_key, rs_indices and rs_canon: rows_select.h, shared with rows_quantiles.hip)
 
-__device__ __forceinline__ unsigned rs_key(float v) { return nv(v) ? f2ord(v) : RS_INV; }
 __device__ __forceinline__ float rs_level(const float* __restrict__ q, int qfield, long r) { return q ? (qfield ? q[r] : q[0]) : 0.5f; }
-__device__ __forceinline__ void rs_indices(float q, int N, int& lo, int& up) {   // util.cpp:152-157
-    const float pos = q * (float)(N - 1);
-    lo = (int)floorf(pos); up = (int)ceilf(pos);
-}
-// -0.0 and +0.0 compare equal in row_statistic's Min / Max: one key for both, so that the index decides between them
-__device__ __forceinline__ unsigned rs_canon(unsigned k) { return k == 0x7FFFFFFFu ? 0x80000000u : k; }
 
 // ---- lane ---------------------------------------------------------------------------------------------------------------
 __global__ void k_rows_lane(const float* __restrict__ in, long rows, int len, const float* __restrict__ q, int qfield, float* __restrict__ out) {

@@ -467,6 +467,14 @@ int gpp_calc_statistic(const float* array, long rows, int len, int statistic, fl
  * (csrc/rows_select.hip: selection by keys out of LDS for rows of up to 160 values, a radix select per row beyond, several workgroups per row
  * for few long rows); the result does not depend on the path. */
 int gpp_calc_quantile(const float* array, long rows, int len, const float* quantile, long nq, float* out, int mem);
+/* Many levels per row, no counterpart in the reference (gridpp_amd.calc_quantiles, quantile_mapping_curves): out is [rows][nq] with nq contiguous,
+ * out[r][j] = exactly the bits gpp_calc_quantile gives for row r at the level quantiles[j].  array / out follow `mem`; `quantiles` is a host
+ * float32 array whatever `mem` says (like the curves of gpp_apply_curve), in any order, repeats allowed.  GPP_EINVAL before any device work: a
+ * NULL pointer, a level below 0 or above 1 ("calc_quantiles: Quantiles must be between 0 and 1 inclusive"; NaN passes and gives NaN).  rows == 0
+ * or nq == 0 returns GPP_OK and writes nothing.  Rows of up to 8192 values are sorted once in LDS and every level picked out of the sorted row
+ * where that beats one selection per level (csrc/rows_quantiles.hip; the path override GPP_ROWS_QUANTILES = tile | block | loop forces a path
+ * where it applies); longer rows, and nq == 1, run gpp_calc_quantile's selection once per level.  The result does not depend on the path. */
+int gpp_calc_quantiles(const float* array, long rows, int len, const float* quantiles, int nq, float* out, int mem);
 /* gridpp::calc_even_quantiles (util.cpp:261-338) and, with only_valid = 1,
  * gridpp::get_neighbourhood_thresholds (neighbourhood.cpp:243-295) over the n
  * values of a flattened field.  out holds num floats; *count = number written. */
