@@ -39,8 +39,11 @@ else:
     # optimal_interpolation computed once per geometry and applied to any number of fields): gridpp_amd.optimal_interpolation_gain.
     # calc_quantiles and quantile_mapping_curves have no counterpart in the reference either (many quantiles of every row from
     # one sort, and one quantile-mapping curve per cell for apply_curve): gridpp_amd.calc_quantiles, gridpp_amd.quantile_mapping_curves.
+    # Nor have neighbourhood_quantiles_fast and neighbourhood_cdf (many levels of neighbourhood_quantile_fast from one pass over
+    # the cube, and the per-threshold neighbourhood probabilities it interpolates in): gridpp_amd.neighbourhood_quantiles_fast, gridpp_amd.neighbourhood_cdf.
     for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve",
-                  "optimal_interpolation_gain", "OiGain", "calc_quantiles", "quantile_mapping_curves"):
+                  "optimal_interpolation_gain", "OiGain", "calc_quantiles", "quantile_mapping_curves",
+                  "neighbourhood_quantiles_fast", "neighbourhood_cdf"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

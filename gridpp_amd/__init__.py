@@ -1596,6 +1596,62 @@ def neighbourhood_quantile_fast(input, quantile, halfwidth, thresholds):
                   int(_shape(thr)[0]), out_shape=(ny, nx), like=arr, mem=_m.flags(f64, arr) | (_capi.Q_HOST if q_host else 0))
 
 
+def _dev_thresholds(thr, arr):
+    """thresholds beside a device-resident field go to its device"""
+    if _is_dev(arr) and not _is_dev(thr):
+        import torch
+        return torch.from_numpy(np.asarray(thr)).to(arr.device)
+    return thr
+
+
+def neighbourhood_quantiles_fast(input, quantiles, halfwidth, thresholds):
+    """Many levels of neighbourhood_quantile_fast from one call (no counterpart in the reference): (Y, X, Q) float32,
+    plane [..., j] holding exactly the bits neighbourhood_quantile_fast(input, quantiles[j], halfwidth, thresholds) returns.  The
+    member pass over the cube and the window sums do not depend on the level: they run once for all Q.
+
+    input: (Y, X) or (Y, X, E), numpy or a torch CUDA tensor (then the result is one), as for neighbourhood_quantile_fast.
+    quantiles: a 1-D sequence of scalar levels in host memory, in any order, repeats allowed; a level outside [0, 1] raises
+    ValueError before any device work, a NaN level gives a NaN plane.  Per-cell level fields stay with the single-level function.
+    No thresholds: NaN everywhere.  See neighbourhood_cdf for the curve the levels are read from."""
+    arr, ny, nx, ne, is3d, f64 = _field23(input, keep_f64=True)
+    if halfwidth < 0:
+        raise ValueError("Half width must be > 0")
+    if ny * nx * ne == 0:
+        return np.zeros((0, 0, 0), np.float32)
+    q = _m.field(quantiles, 1, "quantiles") if not _is_dev(quantiles) else _m.field(quantiles.cpu().numpy(), 1, "quantiles")
+    with np.errstate(invalid="ignore"):
+        if np.any((q < 0) | (q > 1)):    # (NaN passes)
+            raise ValueError("All quantiles must be >= 0 and <= 1")
+    thr = _dev_thresholds(_m.field(thresholds, 1, "thresholds"), arr)
+    nq = int(q.size)
+    if nq == 0:
+        return _m._empty_like_field((ny, nx, 0), arr)
+    return _m.run(lib().gpp_neighbourhood_quantiles_fast, _ptr(arr), ny, nx, ne, is3d, _ptr(q), nq, int(halfwidth), _ptr(thr),
+                  int(_shape(thr)[0]), out_shape=(ny, nx, nq), like=arr, mem=_m.flags(f64, arr, thr))
+
+
+def neighbourhood_cdf(input, thresholds, halfwidth):
+    """The curve neighbourhood_quantile_fast interpolates in (the reference computes it and throws it away,
+    src/api/neighbourhood.cpp:490-509): (Y, X, T) float32, plane [..., t] = P(member <= thresholds[t]) over the window of
+    halfwidth and the members -- the per-cell fraction float(sum) / count, its neighbourhood Mean, the E-fold float32 sum / E, clamped
+    to [0, 1].  The planes follow the thresholds as given (unsorted, duplicated, non-finite ones included); a value is NaN where
+    the window holds no valid cell.  The exceedance probability P(member > threshold) is 1 - cdf.
+
+    interpolate(q, cdf[y, x, :], thresholds) in float32 (with the two special cases of neighbourhood.cpp:514-517) gives the bits
+    of neighbourhood_quantile_fast(input, q, halfwidth, thresholds) wherever the column holds no NaN."""
+    arr, ny, nx, ne, is3d, f64 = _field23(input, keep_f64=True)
+    if halfwidth < 0:
+        raise ValueError("Half width must be > 0")
+    if ny * nx * ne == 0:
+        return np.zeros((0, 0, 0), np.float32)
+    thr = _dev_thresholds(_m.field(thresholds, 1, "thresholds"), arr)
+    nt = int(_shape(thr)[0])
+    if nt == 0:
+        return _m._empty_like_field((ny, nx, 0), arr)
+    return _m.run(lib().gpp_neighbourhood_cdf, _ptr(arr), ny, nx, ne, is3d, int(halfwidth), _ptr(thr), nt, out_shape=(ny, nx, nt), like=arr,
+                  mem=_m.flags(f64, arr, thr))
+
+
 def neighbourhood_ens(input, halfwidth, statistic):   # deprecated aliases (neighbourhood.cpp:541-552), with the reference's message
     future_deprecation_warning("neighbourhood_ens", "neighbourhood")
     return neighbourhood(input, halfwidth, statistic)

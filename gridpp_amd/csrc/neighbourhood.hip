@@ -1099,37 +1099,49 @@ __global__ void k_qf_yarray(float* __restrict__ planes, long n, int reps) {
     if(yv > 1) yv = 1; else if(yv < 0) yv = 0;
     planes[i] = yv;
 }
+// interpolate() (util.cpp:377-414) with the two special cases of neighbourhood.cpp:508-513 on the column of cell c of ya [T][C], none of whose entries is missing
+__device__ __forceinline__ float qf_interp_column(const float* __restrict__ ya, const long C, const long c, const int T, const float* __restrict__ thr, const float x) {
+    const float y0a = ya[c], yLa = ya[(long)(T - 1) * C + c];
+    if(x == 1 && y0a == 1) return thr[0];
+    if(x == 0 && yLa == 0) return thr[T - 1];
+    if(!nv(x)) return NAN;                         // interpolate(): util.cpp:378-379
+    if(x > yLa) return thr[T - 1];                 // util.cpp:386-389
+    if(x < y0a) return thr[0];
+    int i0 = -1, i1 = -1;                          // get_lower_index / get_upper_index (util.cpp:339-376)
+    for(int i = 0; i < T; i++) { float cv = ya[(long)i * C + c]; if(cv < x) i0 = i; else if(cv == x) { i0 = i; break; } else break; }
+    for(int i = T - 1; i >= 0; i--) { float cv = ya[(long)i * C + c]; if(cv > x) i1 = i; else if(cv == x) { i1 = i; break; } else break; }
+    if(i0 < 0) i0 = 0;
+    if(i1 < 0) i1 = T - 1;
+    const float x0 = ya[(long)i0 * C + c], x1 = ya[(long)i1 * C + c], y0 = thr[i0], y1 = thr[i1];
+    if(x0 == x1) {
+        if(i0 == 0 && i1 == T - 1) return (y0 + y1) / 2;
+        if(i0 == 0) return y1;
+        if(i1 == T - 1) return y0;
+        return (y0 + y1) / 2;
+    }
+    return y0 + (y1 - y0) * (x - x0) / (x1 - x0);
+}
 __global__ void k_qf_interp(const float* __restrict__ ya, long C, int T, const float* __restrict__ thr, const float* __restrict__ q, int qfield, float* __restrict__ out) {
     long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if(c >= C) return;
-    const float x = qfield ? q[c] : q[0];
     bool missing = false;
     for(int t = 0; t < T; t++) if(!nv(ya[(long)t * C + c])) missing = true;
-    float o = NAN;
-    if(!missing) {
-        const float y0a = ya[c], yLa = ya[(long)(T - 1) * C + c];
-        if(x == 1 && y0a == 1) o = thr[0];
-        else if(x == 0 && yLa == 0) o = thr[T - 1];
-        else if(!nv(x)) o = NAN;                       // interpolate(): util.cpp:378-379
-        else if(x > yLa) o = thr[T - 1];               // util.cpp:386-389
-        else if(x < y0a) o = thr[0];
-        else {
-            int i0 = -1, i1 = -1;                      // get_lower_index / get_upper_index (util.cpp:339-376)
-            for(int i = 0; i < T; i++) { float cv = ya[(long)i * C + c]; if(cv < x) i0 = i; else if(cv == x) { i0 = i; break; } else break; }
-            for(int i = T - 1; i >= 0; i--) { float cv = ya[(long)i * C + c]; if(cv > x) i1 = i; else if(cv == x) { i1 = i; break; } else break; }
-            if(i0 < 0) i0 = 0;
-            if(i1 < 0) i1 = T - 1;
-            const float x0 = ya[(long)i0 * C + c], x1 = ya[(long)i1 * C + c], y0 = thr[i0], y1 = thr[i1];
-            if(x0 == x1) {
-                if(i0 == 0 && i1 == T - 1) o = (y0 + y1) / 2;
-                else if(i0 == 0) o = y1;
-                else if(i1 == T - 1) o = y0;
-                else o = (y0 + y1) / 2;
-            }
-            else o = y0 + (y1 - y0) * (x - x0) / (x1 - x0);
-        }
-    }
-    out[c] = o;
+    out[c] = missing ? NAN : qf_interp_column(ya, C, c, T, thr, qfield ? q[c] : q[0]);
+}
+// The unfused finish of the many-level forms.  k_qf_interp_multi: the same column for nq scalar levels, out [C][nq].
+// k_qf_cdf_copy: yarray [T][C] -> out [C][T].
+__global__ void k_qf_interp_multi(const float* __restrict__ ya, long C, int T, const float* __restrict__ thr, const float* __restrict__ levels, int nq, float* __restrict__ out) {
+    long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if(c >= C) return;
+    bool missing = false;
+    for(int t = 0; t < T; t++) if(!nv(ya[(long)t * C + c])) missing = true;
+    for(int j = 0; j < nq; j++) out[c * nq + j] = missing ? NAN : qf_interp_column(ya, C, c, T, thr, levels[j]);
+}
+__global__ void k_qf_cdf_copy(const float* __restrict__ ya, long C, int T, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= C * T) return;
+    const long c = i / T;
+    out[i] = ya[(i - c * T) * C + c];
 }
 
 // -------------------------------------------------------------------------------------------
@@ -1411,10 +1423,15 @@ struct NbhCall : Fields {
 struct QfCall : Fields {
     const float* const input; const int ny, nx, ne, is3d; const float* const quantile; const int nq, halfwidth; const float* const thresholds; const int nt;
     float* const out; const int mem;
+    // multi: 0 = one level per cell (gpp_neighbourhood_quantile_fast); QF_LEVELS = `quantile` holds nq scalar levels in HOST memory, out is [ny][nx][nq]
+    // (gpp_neighbourhood_quantiles_fast); QF_CDF = no level at all (nq == 0), out is [ny][nx][nt], the yarray itself (gpp_neighbourhood_cdf)
+    enum { QF_LEVELS = 1, QF_CDF = 2 };
+    const int multi = 0;
     NbWorkspace& ws = g_nb; const long C = (long)ny * nx;
+    const int width = multi == QF_LEVELS ? nq : (multi == QF_CDF ? nt : 1);   // floats per cell of `out`
     // GPP_Q_HOST: the quantile argument is host memory although the field is in HBM (the scalar quantile of a script beside a device-resident
     // cube: uploaded by the caller and read back here for its validation it cost two transfers and a host round trip per call)
-    const int qmem = (mem & GPP_Q_HOST) ? GPP_MEM_HOST : (mem & ~GPP_HOST_F64);   // GPP_HOST_F64 applies to `input` only: quantile / thresholds stay float32
+    const int qmem = (multi || (mem & GPP_Q_HOST)) ? GPP_MEM_HOST : (mem & ~GPP_HOST_F64);   // GPP_HOST_F64 applies to `input` only: quantile / thresholds stay float32
     const bool q_on_device = (qmem & GPP_MEM_DEVICE) != 0;
     InField qf, th; bool fused = false, ranked = false;
     std::vector<float> hq_buf; float* hq = nullptr;   // quantiles of a device-resident argument on their way to the host
@@ -1423,7 +1440,8 @@ struct QfCall : Fields {
     bool check_args() const {   // false: an empty field, nothing to do
         if(halfwidth < 0) invalid("Half width must be > 0");                                   // :303-304,419-420
         if(ny <= 0 || nx <= 0 || ne <= 0) return false;                                         // :306-307
-        if(nq != 1 && nq != C) invalid("Quantile must be the same size as input, or size (1, 1)");   // :312-313
+        if(!multi && nq != 1 && nq != C) invalid("Quantile must be the same size as input, or size (1, 1)");   // :312-313
+        if(nq < 0) invalid("negative number of quantiles");
         if(nt < 0) invalid("negative number of thresholds");
         return true;
     }
@@ -1437,7 +1455,7 @@ struct QfCall : Fields {
     }
     void check_fetched_q() const { if(q_on_device) check_q(hq); }
     void bind_fields() {
-        bind(input, (size_t)C * ne, out, C, mem);
+        bind(input, (size_t)C * ne, out, (size_t)C * width, mem);
         fused = nt > 0 && is3d && ne <= 254 && nt <= 16 && halfwidth <= QF_MAXHW && C < (1L << 31) && !path_env("GPP_QF_NO_FUSED");
         ranked = fused && (ne & 3) == 0 && (reinterpret_cast<size_t>(in.d) & 15) == 0 && !path_env("GPP_QF_NO_RANKS");
         if(nt > 0) th.bind(thresholds, nt, mem & ~GPP_HOST_F64);
@@ -1447,11 +1465,12 @@ struct QfCall : Fields {
         fetch_q();
         if(q_on_device) GPP_HIP(hipStreamSynchronize(stream()));
         check_fetched_q();
-        hipLaunchKernelGGL(k_fill_nan, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), o.d, C);
+        const long n = C * width;
+        if(n > 0) hipLaunchKernelGGL(k_fill_nan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), o.d, n);
         return done();
     }
     void bind_quantile() {
-        qf.bind(quantile, nq, qmem);
+        if(nq > 0) qf.bind(quantile, nq, qmem);
         if(!ws.h_pin) GPP_HIP(hipHostMalloc((void**)&ws.h_pin, 64, hipHostMallocDefault));
     }
     bool may_speculate() const { return fused && ranked && ws.spec_nt == nt && ws.spec_U >= 0 && !path_env("GPP_QF_NO_SPEC"); }
@@ -1493,7 +1512,9 @@ struct QfCall : Fields {
         g.rowflag = rowflag;
         if(ranked) qf_count_launch(in.d, C, ne, th.d, nt, lut, U, cnt8, g, spec ? U : -1);
         else member_pass(in.d, C, ne, 2, 0, th.d, nt, reinterpret_cast<float*>(cnt8), g);
-        qf_box_launch(cnt8, g, ne, halfwidth, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
+        // (one scalar level of the many-level entry is the single-level kernel: [ny][nx][1] is [ny][nx])
+        if(!multi || (multi == QF_LEVELS && nq == 1)) qf_box_launch(cnt8, g, ne, halfwidth, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
+        else qf_box_multi_launch(cnt8, g, ne, halfwidth, nt, th.d, qf.d, multi == QF_CDF ? 0 : nq, o.d);
     }
     // the one read-back of a speculative round: did the count pass run, and the quantile(s) for the validation a plain round does first
     bool speculation_held() {
@@ -1517,8 +1538,20 @@ struct QfCall : Fields {
         member_pass(in.d, C, ne, 1, 0, th.d, nt, planes);                 // fractions per threshold (:453-472)
         // stats[t] = neighbourhood(temp, hw, Mean) (:473) with the yarray epilogue (:494-506) fused into the column pass
         box_stat(planes, ny, nx, nt, halfwidth, GPP_MEAN, stats, is3d ? ne : 1);
-        hipLaunchKernelGGL(k_qf_interp, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
+        if(!multi) hipLaunchKernelGGL(k_qf_interp, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
+        else if(multi == QF_LEVELS) hipLaunchKernelGGL(k_qf_interp_multi, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, th.d, qf.d, nq, o.d);
+        else hipLaunchKernelGGL(k_qf_cdf_copy, dim3((unsigned)((C * nt + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, o.d);
         GPP_HIP(hipGetLastError());
+    }
+    int run() {   // the rounds of a call whose arguments are checked and whose device is there
+        bind_fields();
+        if(nt == 0) return all_missing();
+        bind_quantile();
+        // Two rounds at most.  The first may be speculative: the table's head and the quantile are read back once, behind the box pass.  A table that turns out
+        // different stops the passes on the device, and the second round does what every call did until round 5 -- wait for the table, then launch.
+        const bool held = may_speculate() && round(true);   // the speculative round
+        if(!held) round(false);                              // the plain round
+        return done();
     }
 };
 }   // namespace
@@ -1557,14 +1590,35 @@ extern "C" int gpp_neighbourhood_quantile_fast(const float* input, int ny, int n
     QfCall c{{}, input, ny, nx, ne, is3d, quantile, nq, halfwidth, thresholds, nt, out, mem};
     if(!c.check_args()) return GPP_OK;
     ensure_device();
-    c.bind_fields();
-    if(nt == 0) return c.all_missing();
-    c.bind_quantile();
-    // Two rounds at most.  The first may be speculative: the table's head and the quantile are read back once, behind the box pass.  A table that turns out
-    // different stops the passes on the device, and the second round does what every call did until round 5 -- wait for the table, then launch.
-    const bool held = c.may_speculate() && c.round(true);   // the speculative round
-    if(!held) c.round(false);                                // the plain round
-    return c.done();
+    return c.run();
+    GPP_CATCH
+}
+
+// gridpp_amd.neighbourhood_quantiles_fast: out[y][x][j] = the bits gpp_neighbourhood_quantile_fast gives for the scalar level quantiles[j]; the levels are a
+// host array whatever `mem` says.  One count pass and one march of the window sums for all of them.
+extern "C" int gpp_neighbourhood_quantiles_fast(const float* input, int ny, int nx, int ne, int is3d, const float* quantiles, int nq,
+                                                int halfwidth, const float* thresholds, int nt, float* out, int mem) {
+    GPP_TRY
+    QfCall c{{}, input, ny, nx, ne, is3d, quantiles, nq, halfwidth, thresholds, nt, out, mem, QfCall::QF_LEVELS};
+    if(!c.check_args()) return GPP_OK;
+    if((nq > 0 && !quantiles) || (nt > 0 && !thresholds) || !input) invalid("neighbourhood_quantiles_fast: input / quantiles / thresholds is NULL");
+    c.check_q(quantiles);
+    if(nq == 0) return GPP_OK;
+    if(!out) invalid("neighbourhood_quantiles_fast: out is NULL");
+    ensure_device();
+    return c.run();
+    GPP_CATCH
+}
+
+// gridpp_amd.neighbourhood_cdf: out[y][x][t] = P(member <= thresholds[t]) over the window and the members, the reference's yarray[t] (neighbourhood.cpp:490-509)
+extern "C" int gpp_neighbourhood_cdf(const float* input, int ny, int nx, int ne, int is3d, int halfwidth, const float* thresholds, int nt, float* out, int mem) {
+    GPP_TRY
+    QfCall c{{}, input, ny, nx, ne, is3d, nullptr, 0, halfwidth, thresholds, nt, out, mem, QfCall::QF_CDF};
+    if(!c.check_args()) return GPP_OK;
+    if(nt == 0) return GPP_OK;
+    if(!input || !thresholds || !out) invalid("neighbourhood_cdf: input / thresholds / out is NULL");
+    ensure_device();
+    return c.run();
     GPP_CATCH
 }
 

@@ -31,3 +31,6 @@ __device__ __forceinline__ long qf_cell_offset(const QfGeom& g, const long cell)
 
 // box pass: cnt8 = the T + 1 planes above -> out [Y][X]   (neighbourhood.cpp:473-522, util.cpp:339-414)
 void qf_box_launch(const unsigned char* cnt8, const QfGeom& g, int reps, int hw, int T, const float* d_thr, const float* d_q, int qfield, float* d_out, hipStream_t st = nullptr);
+// the same march with the whole column of a cell as its result: nq >= 1 scalar levels at d_levels -> out [Y][X][nq], plane j with the bits
+// qf_box_launch gives for d_levels[j]; nq == 0 -> out [Y][X][T], the clamped E-fold means themselves (the reference's yarray, neighbourhood.cpp:490-509)
+void qf_box_multi_launch(const unsigned char* cnt8, const QfGeom& g, int reps, int hw, int T, const float* d_thr, const float* d_levels, int nq, float* d_out, hipStream_t st = nullptr);

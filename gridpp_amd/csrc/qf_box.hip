@@ -191,13 +191,24 @@ __device__ float qb_interp_lazy(float* __restrict__ ya, const int stride, const 
 
 // GENERAL = false: every cell of the field has E valid members (g.rowflag[Y] == 0, else the kernel returns at once);
 // GENERAL = true: the other case (returns at once when no row is flagged).  Both are launched, one of them works.
-template <int HW, bool GENERAL>
-__global__ __launch_bounds__(512) void k_qf_box(const unsigned char* __restrict__ cnt8, const QfGeom g, const int reps, const int T,
-                                                const float* __restrict__ thr, const float* __restrict__ q, const int qfield, float* __restrict__ out, const int SH) {
+//
+// MODE 0: one level per cell (a scalar or a field), the lazy form above -- gpp_neighbourhood_quantile_fast.
+// MODE 1: the whole column of a cell -- gpp_neighbourhood_quantiles_fast (nq >= 1 scalar levels, out [Y][X][qstride], this launch
+//         writes levels [0, nq) of every cell) and gpp_neighbourhood_cdf (nq == 0, out [Y][X][T]).  The threads (p, s) leave F(o) itself, the eager
+//         form, as [column][T]: a cell's column is then read-only and contiguous, the cdf of a step is the buffer as it stands, and the levels
+//         are (cell, level) pairs spread over all threads of the workgroup, pair i writing float i of the step's run of 256 nq floats.
+//         Every pair runs the unchanged interpolate() on the F column, which is what qb_interp_lazy's comparisons are argued to equal.
+#define QB_MAXQ 32      // levels per launch of MODE 1 (the table in LDS); more levels: another launch, which forms the window sums again
+template <int HW, bool GENERAL, int MODE>
+__device__ __forceinline__ void qb_march(const unsigned char* __restrict__ cnt8, const QfGeom g, const int reps, const int T,   // (g by value, as k_qf_box takes it: by reference ten GENERAL kernels change their SGPR spills by one or two)
+                                         const float* __restrict__ thr, const float* __restrict__ q, const int qfield, float* __restrict__ out, const int SH,
+                                         const int nq, const int qstride) {
+    constexpr bool LAZY = MODE == 0 && QB_LAZY != 0;
     extern __shared__ double qb_lds[];
     double* const tab = qb_lds;                                             // [256] count -> (double)(float)(count / E); 255 -> 0
     float* const sthr = reinterpret_cast<float*>(tab + 256);                // [16]
-    float* const ya = sthr + 16;                                            // [2][T][QB_SW] clamped means of the current / previous step
+    float* const ya = sthr + 16;                                            // [2][T][QB_SW] clamped means of the current / previous step (MODE 1: [2][QB_SW][T])
+    float* const slev = ya + 2 * T * QB_SW;                                 // MODE 1: [QB_MAXQ] the levels of this launch
     if((unsigned)(size_t)(__attribute__((address_space(3))) double*)qb_lds != 0u) __builtin_trap();   // see qb_tab()
     if(g.rowflag[g.Y + 1] != 0) return;      // (the count pass did not run: launched for another table than this call's, see k_qf_count)
     if((g.rowflag[g.Y] != 0) != GENERAL) return;
@@ -210,6 +221,7 @@ __global__ __launch_bounds__(512) void k_qf_box(const unsigned char* __restrict_
     const bool active = p < T && x0 < X;
     for(int k = tid; k < 256; k += blockDim.x) tab[k] = (k <= reps) ? (double)((float)k / (float)reps) : 0.0;
     if(tid < 16) sthr[tid] = tid < T ? thr[tid] : 0.0f;
+    if constexpr (MODE == 1) { if(tid < nq) slev[tid] = q[tid]; }
     __syncthreads();
     // byte i of a loaded row = padded column x0 + i = field column x0 - 16 + i (QF_PADX == 16)
     const unsigned char* const plane = cnt8 + (long)(active ? p : 0) * g.Pp + (active ? x0 : 0);
@@ -327,12 +339,12 @@ __global__ __launch_bounds__(512) void k_qf_box(const unsigned char* __restrict_
                     acc[j] = 0.0f;
                 }
             }
-#if QB_LAZY
+            if constexpr (LAZY) {
 #pragma unroll
             for(int j = 0; j < QB_SEG; j++) yab[p * QB_SW + s * QB_SEG + j] = qb_nv(o[j]) ? o[j] : NAN;   // the means: F where interpolate() looks, qb_interp_lazy
             (void)acc;
-        }
-#else
+            }
+            else {
             // (a wave whose means are all 0 or 1 -- a threshold below or above everything in sight -- has nothing to add up:
             //  E * 0 and E * 1 are exact, and so is every partial sum)
             bool plain01 = true;
@@ -367,11 +379,27 @@ __global__ __launch_bounds__(512) void k_qf_box(const unsigned char* __restrict_
                 // rounding boundary, the double product is within 2^-52 of it)
                 float yv = reps > 1 ? (float)((double)acc[j] * rreps) : o[j];
                 yv = yv > 1 ? 1.0f : (yv < 0 ? 0.0f : yv);
-                yab[p * QB_SW + s * QB_SEG + j] = qb_nv(o[j]) ? yv : NAN;
+                yab[MODE == 1 ? (s * QB_SEG + j) * T + p : p * QB_SW + s * QB_SEG + j] = qb_nv(o[j]) ? yv : NAN;
+            }
             }
         }
-#endif
         qb_lds_barrier();
+        if constexpr (MODE == 1) {
+            // the step's run of the result: ncols cells x T (cdf) or x qstride (levels) floats, contiguous in `out`; lane i writes float i
+            const int ncols = min(QB_SW, X - xs);
+            if(nq == 0) {
+                float* const dst = out + ((long)y * X + xs) * T;
+                for(int i = tid; i < ncols * T; i += blockDim.x) dst[i] = yab[i];
+            }
+            else {
+                float* const dst = out + ((long)y * X + xs) * qstride;
+                for(int i = tid; i < ncols * nq; i += blockDim.x) {
+                    const int c = i / nq, j = i - c * nq;
+                    dst[(long)c * qstride + j] = qb_interp(yab + c * T, 1, T, sthr, slev[j]);
+                }
+            }
+            continue;
+        }
         for(int c = tid; c < QB_SW; c += blockDim.x) {
             const int x = xs + c;
             if(x < X) {
@@ -379,21 +407,33 @@ __global__ __launch_bounds__(512) void k_qf_box(const unsigned char* __restrict_
 #if defined(QB_ABL) && (QB_ABL & 2)      // timing experiment: no interpolation
                 out[cell] = yab[c] + yab[c + (T - 1) * QB_SW];
 #else
-#if QB_LAZY
-                out[cell] = qb_interp_lazy(yab + c, QB_SW, T, sthr, qfield ? q[cell] : q[0], reps, rreps);
-#else
-                out[cell] = qb_interp(yab + c, QB_SW, T, sthr, qfield ? q[cell] : q[0]);
-#endif
+                if constexpr (LAZY) out[cell] = qb_interp_lazy(yab + c, QB_SW, T, sthr, qfield ? q[cell] : q[0], reps, rreps);
+                else out[cell] = qb_interp(yab + c, QB_SW, T, sthr, qfield ? q[cell] : q[0]);
 #endif
             }
         }
     }
 }
 
+template <int HW, bool GENERAL>
+__global__ __launch_bounds__(512) void k_qf_box(const unsigned char* __restrict__ cnt8, const QfGeom g, const int reps, const int T,
+                                                const float* __restrict__ thr, const float* __restrict__ q, const int qfield, float* __restrict__ out, const int SH) {
+    qb_march<HW, GENERAL, 0>(cnt8, g, reps, T, thr, q, qfield, out, SH, 0, 0);
+}
+// levels: device pointer to the nq <= QB_MAXQ levels of this launch (nq == 0: the cdf); out: the first float this launch writes of cell (0, 0)
+template <int HW, bool GENERAL>
+__global__ __launch_bounds__(512) void k_qf_box_multi(const unsigned char* __restrict__ cnt8, const QfGeom g, const int reps, const int T,
+                                                      const float* __restrict__ thr, const float* __restrict__ levels, const int nq, const int qstride,
+                                                      float* __restrict__ out, const int SH) {
+    qb_march<HW, GENERAL, 1>(cnt8, g, reps, T, thr, levels, 0, out, SH, nq, qstride);
+}
+
+// multi: the MODE 1 kernels (nq levels at d_q, all launches of QB_MAXQ levels at most; nq == 0: the cdf); else the one level (field) of MODE 0
 template <int HW>
-void launch_hw(const unsigned char* cnt8, const QfGeom& g, int reps, int T, const float* d_thr, const float* d_q, int qfield, float* d_out, hipStream_t st) {
+void launch_hw(const unsigned char* cnt8, const QfGeom& g, int reps, int T, const float* d_thr, const float* d_q, int qfield, float* d_out, hipStream_t st,
+               const bool multi, const int nq) {
     const int threads = 64 * ((T * (QB_SW / QB_SEG) + 63) / 64);
-    const size_t lds = 256 * sizeof(double) + 16 * sizeof(float) + (size_t)2 * T * QB_SW * sizeof(float);
+    const size_t lds = 256 * sizeof(double) + 16 * sizeof(float) + (size_t)2 * T * QB_SW * sizeof(float) + (multi ? QB_MAXQ * sizeof(float) : 0);
     // rows per workgroup: about QB_SH, chosen so that the workgroups fill the 256 CUs a whole number of times
     const int strips = (g.X + QB_SW - 1) / QB_SW;
     int segs = std::max(1, (g.Y + QB_SH - 1) / QB_SH);
@@ -407,19 +447,35 @@ void launch_hw(const unsigned char* cnt8, const QfGeom& g, int reps, int T, cons
     if(strips * segs > 256) { const int per = 256 / std::__gcd(256, strips); segs = (segs + per - 1) / per * per; }
     const int SH = std::max(1, (g.Y + segs - 1) / segs);
     const dim3 grid(strips, (g.Y + SH - 1) / SH);
-    hipLaunchKernelGGL((k_qf_box<HW, false>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
-    hipLaunchKernelGGL((k_qf_box<HW, true>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
+    if(!multi) {
+        hipLaunchKernelGGL((k_qf_box<HW, false>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
+        hipLaunchKernelGGL((k_qf_box<HW, true>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
+    }
+    else {
+        for(int q0 = 0; q0 < std::max(nq, 1); q0 += QB_MAXQ) {
+            const int n = std::min(QB_MAXQ, nq - q0);   // (0: the cdf)
+            hipLaunchKernelGGL((k_qf_box_multi<HW, false>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q + q0, n, nq, d_out + q0, SH);
+            hipLaunchKernelGGL((k_qf_box_multi<HW, true>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q + q0, n, nq, d_out + q0, SH);
+        }
+    }
     GPP_HIP(hipGetLastError());
 }
-}   // namespace
-
-void qf_box_launch(const unsigned char* cnt8, const QfGeom& g, int reps, int hw, int T, const float* d_thr, const float* d_q, int qfield, float* d_out, hipStream_t st) {
+void launch_any(const unsigned char* cnt8, const QfGeom& g, int reps, int hw, int T, const float* d_thr, const float* d_q, int qfield, float* d_out, hipStream_t st,
+                const bool multi, const int nq) {
     if(!st) st = stream();
     switch(hw) {
-#define QB_CASE(n) case n: launch_hw<n>(cnt8, g, reps, T, d_thr, d_q, qfield, d_out, st); break;
+#define QB_CASE(n) case n: launch_hw<n>(cnt8, g, reps, T, d_thr, d_q, qfield, d_out, st, multi, nq); break;
         QB_CASE(0) QB_CASE(1) QB_CASE(2) QB_CASE(3) QB_CASE(4) QB_CASE(5) QB_CASE(6) QB_CASE(7) QB_CASE(8)
         QB_CASE(9) QB_CASE(10) QB_CASE(11) QB_CASE(12) QB_CASE(13) QB_CASE(14) QB_CASE(15) QB_CASE(16)
 #undef QB_CASE
         default: runtime("Internal error. quantile_fast: halfwidth of the fused box pass");
     }
+}
+}   // namespace
+
+void qf_box_launch(const unsigned char* cnt8, const QfGeom& g, int reps, int hw, int T, const float* d_thr, const float* d_q, int qfield, float* d_out, hipStream_t st) {
+    launch_any(cnt8, g, reps, hw, T, d_thr, d_q, qfield, d_out, st, false, 0);
+}
+void qf_box_multi_launch(const unsigned char* cnt8, const QfGeom& g, int reps, int hw, int T, const float* d_thr, const float* d_levels, int nq, float* d_out, hipStream_t st) {
+    launch_any(cnt8, g, reps, hw, T, d_thr, d_levels, 0, d_out, st, true, nq);
 }

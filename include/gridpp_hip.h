@@ -456,6 +456,23 @@ int gpp_neighbourhood_brute_force(const float* input, int ny, int nx, int ne, in
 int gpp_neighbourhood_quantile_fast(const float* input, int ny, int nx, int ne, int is3d,
                                     const float* quantile, int nq, int halfwidth,
                                     const float* thresholds, int nt, float* out, int mem);
+/* Many levels per cell, no counterpart in the reference (gridpp_amd.neighbourhood_quantiles_fast): out is [ny][nx][nq] with nq contiguous,
+ * out[y][x][j] = exactly the bits gpp_neighbourhood_quantile_fast gives at (y, x) for the scalar level quantiles[j], on every path.  input,
+ * thresholds and out follow `mem` (GPP_HOST_F64 applies to `input` only); `quantiles` is a host float32 array whatever `mem` says, in any
+ * order, repeats allowed.  Checked in this order, before any device work: halfwidth < 0 is GPP_EINVAL ("Half width must be > 0"); an empty
+ * field returns GPP_OK and writes nothing; a NULL pointer is GPP_EINVAL; a level below 0 or above 1 is GPP_EINVAL ("All quantiles must be >= 0
+ * and <= 1"; NaN passes and gives a NaN plane); nq == 0 returns GPP_OK and writes nothing.  nt == 0 gives NaN everywhere.  The member pass and
+ * the window sums run once for all levels (csrc/qf_box.hip, k_qf_box_multi); GPP_QF_NO_FUSED, GPP_QF_NO_RANKS and
+ * GPP_QF_NO_SPEC act as they do on gpp_neighbourhood_quantile_fast, and the two entry points may follow each other in any order. */
+int gpp_neighbourhood_quantiles_fast(const float* input, int ny, int nx, int ne, int is3d,
+                                     const float* quantiles, int nq, int halfwidth,
+                                     const float* thresholds, int nt, float* out, int mem);
+/* The curve gpp_neighbourhood_quantile_fast interpolates in (gridpp_amd.neighbourhood_cdf): out is [ny][nx][nt] with nt contiguous, out[y][x][t] =
+ * P(member <= thresholds[t]) over the window and the members -- the reference's yarray[t] (neighbourhood.cpp:490-509; 2-D input: :374-394) for the
+ * thresholds as given, in [0, 1], NaN where the window holds no valid cell.  halfwidth < 0 is GPP_EINVAL ("Half width must be > 0"); an empty
+ * field or nt == 0 returns GPP_OK and writes nothing; a NULL pointer is GPP_EINVAL.  Same passes, paths and overrides as above. */
+int gpp_neighbourhood_cdf(const float* input, int ny, int nx, int ne, int is3d, int halfwidth,
+                          const float* thresholds, int nt, float* out, int mem);
 
 /* ---- per-row statistics (src/api/util.cpp) -------------------------------------
  * array is [rows][len]; one result per row. */
