@@ -41,9 +41,11 @@ else:
     # one sort, and one quantile-mapping curve per cell for apply_curve): gridpp_amd.calc_quantiles, gridpp_amd.quantile_mapping_curves.
     # Nor have neighbourhood_quantiles_fast and neighbourhood_cdf (many levels of neighbourhood_quantile_fast from one pass over
     # the cube, and the per-threshold neighbourhood probabilities it interpolates in): gridpp_amd.neighbourhood_quantiles_fast, gridpp_amd.neighbourhood_cdf.
+    # calc_ranks, sort_rows, reorder_by_ranks and calc_crps have none either (the rank of every member within its cell, the sorted
+    # rows, ensemble copula coupling and the CRPS): gridpp_amd.calc_ranks, gridpp_amd.sort_rows, gridpp_amd.reorder_by_ranks, gridpp_amd.calc_crps.
     for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve",
                   "optimal_interpolation_gain", "OiGain", "calc_quantiles", "quantile_mapping_curves",
-                  "neighbourhood_quantiles_fast", "neighbourhood_cdf"):
+                  "neighbourhood_quantiles_fast", "neighbourhood_cdf", "calc_ranks", "sort_rows", "reorder_by_ranks", "calc_crps"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

@@ -2139,6 +2139,76 @@ def quantile_mapping_curves(ref, fcst, quantiles):
     return calc_quantiles(r, q), calc_quantiles(f, q)
 
 
+def _rank_rows(a):
+    """(rows, len) of an array whose last axis is the row"""
+    shp = _shape(a)
+    return int(np.prod(shp[:-1], dtype=np.int64)), shp[-1]
+
+
+def calc_ranks(array):
+    """The rank of every value within its row (the last axis): (N,), (R, N) or (Y, X, N) -> int32 of the same shape.  For a valid (finite)
+    element rank[i] = #{valid j : a[j] < a[i]} + #{valid j < i : a[j] == a[i]}: values compare numerically (-0.0 == +0.0) and equal values are
+    ordered by position, lower index first -- numpy.argsort(kind="stable") on the valid values of the row.  An invalid element has rank -1.
+    Host arrays or torch CUDA tensors; the result lives where the input does.  RuntimeError for an array that has not 1, 2 or
+    3 dimensions.  No counterpart in the reference: not part of the `gridpp` alias."""
+    a = _rows_array(array, 3)
+    rows, n = _rank_rows(a)
+    if rows * n == 0:
+        return _empty_like_field(_shape(a), a, np.int32)
+    L = lib()
+    return _m.run(lambda p, r, l, out, mem: L.gpp_calc_ranks(p, r, l, out, None, mem), _ptr(a), rows, n, out_shape=_shape(a), like=a,
+                  mem=_m.flags(False, a), dtype=np.int32)
+
+
+def sort_rows(array):
+    """Every row (the last axis) in the order of calc_ranks: out[..., calc_ranks(a)[..., i]] = a[..., i] with the bits of a[..., i] kept (a
+    -0.0 stays -0.0, equal values keep their order), and NaN in the slots from N, the number of valid values, on.  float32 of the input's
+    shape, where the input lives.  No counterpart in the reference: not part of the `gridpp` alias."""
+    a = _rows_array(array, 3)
+    rows, n = _rank_rows(a)
+    if rows * n == 0:
+        return _empty_like_field(_shape(a), a)
+    L = lib()
+    return _m.run(lambda p, r, l, out, mem: L.gpp_calc_ranks(p, r, l, None, out, mem), _ptr(a), rows, n, out_shape=_shape(a), like=a,
+                  mem=_m.flags(False, a))
+
+
+def reorder_by_ranks(values, template):
+    """Ensemble copula coupling (ECC-Q; the Schaake shuffle when `template` is a historical sample): member i receives the value of `values`
+    whose rank equals the rank of template member i.  Two arrays of the same shape, (N,), (R, N) or (Y, X, N); out[..., i] =
+    sort_rows(values)[..., calc_ranks(template)[..., i]], bit for bit, and NaN where the template's value is invalid or its rank is not below the
+    number of valid entries of the `values` row.  Ties in the template are broken by position (lower index first), not at random.  The result
+    lives where the inputs do.  RuntimeError for an array that has not 1, 2 or 3 dimensions, ValueError for shapes that differ.
+    No counterpart in the reference: not part of the `gridpp` alias."""
+    v, t = _rows_array(values, 3), _rows_array(template, 3)
+    if _shape(v) != _shape(t):
+        raise ValueError("reorder_by_ranks: values and template must have the same shape")
+    _mem(v, t)
+    rows, n = _rank_rows(v)
+    if rows * n == 0:
+        return _empty_like_field(_shape(v), v)
+    return _m.run(lib().gpp_reorder_by_ranks, _ptr(v), _ptr(t), rows, n, out_shape=_shape(v), like=v, mem=_m.flags(False, v, t))
+
+
+def calc_crps(ensemble, ref):
+    """The continuous ranked probability score of every row (the last axis) of `ensemble` against `ref`, whose shape is the ensemble's without
+    its last axis: CRPS = (1/N) sum_k |x_(k) - y| - (1/N^2) sum_k (2k - N + 1) x_(k) over the N sorted valid members, the rank form of
+    (1/N) sum |x_i - y| - (1/(2 N^2)) sum sum |x_i - x_j|.  Both sums are taken in double and cast to float32 last; NaN when a row has no valid
+    member or y is not finite.  float32 of ref's shape, where the inputs live.  RuntimeError for an ensemble that has not 1, 2
+    or 3 dimensions, ValueError for a `ref` of another shape.  No counterpart in the reference: not part of the `gridpp` alias."""
+    e = _rows_array(ensemble, 3)
+    yshape = _shape(ref) if _is_dev(ref) else np.shape(ref)   # (before the conversion: a scalar beside a vector comes back as one value)
+    y = _m.field(ref)
+    if tuple(yshape) != _shape(e)[:-1]:
+        raise ValueError("calc_crps: ref must have the shape of ensemble without its last axis")
+    _mem(e, y)
+    rows, n = _rank_rows(e)
+    if rows == 0:
+        return _empty_like_field(yshape, e)
+    out = _m.run(lib().gpp_calc_crps, _ptr(e), _ptr(y), rows, n, out_shape=(rows,), like=e, mem=_m.flags(False, e, y))
+    return out.reshape(yshape)
+
+
 def _even_quantiles(values, num, only_valid):
     dev = _is_dev(values)
     v = _m.field(values).reshape(-1)

@@ -123,6 +123,9 @@ SIGNATURES = {
     "gpp_calc_statistic": [vp, C.c_long, C.c_int, C.c_int, vp, C.c_int],
     "gpp_calc_quantile": [vp, C.c_long, C.c_int, vp, C.c_long, vp, C.c_int],
     "gpp_calc_quantiles": [vp, C.c_long, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_calc_ranks": [vp, C.c_long, C.c_int, vp, vp, C.c_int],
+    "gpp_reorder_by_ranks": [vp, vp, C.c_long, C.c_int, vp, C.c_int],
+    "gpp_calc_crps": [vp, vp, C.c_long, C.c_int, vp, C.c_int],
     "gpp_calc_even_quantiles": [vp, C.c_long, C.c_int, C.c_int, vp, ip, C.c_int],
     "gpp_neighbourhood": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
     "gpp_neighbourhood_brute_force": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int],

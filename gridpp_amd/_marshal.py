@@ -115,10 +115,12 @@ def _host_empty(shape):
     return np.frombuffer(buf, dtype=np.float32).reshape(shape)     # the array keeps `buf` alive
 
 
-def _empty_like_field(shape, like):
+def _empty_like_field(shape, like, dtype=np.float32):
     if _is_dev(like):
         import torch
-        return torch.empty(shape, dtype=torch.float32, device=like.device)
+        return torch.empty(shape, dtype=torch.int32 if dtype == np.int32 else torch.float32, device=like.device)
+    if dtype == np.int32:
+        return np.empty(shape, dtype=np.int32)
     return _host_empty(shape)
 
 
@@ -145,9 +147,10 @@ def flags(f64, *fields):
     return mem
 
 
-def run(entry, *args, out_shape, like, mem):
-    """Calls an entry point that ends in (..., out, mem) and returns its result, allocated where `like` lives."""
-    out = _empty_like_field(out_shape, like)
+def run(entry, *args, out_shape, like, mem, dtype=np.float32):
+    """Calls an entry point that ends in (..., out, mem) and returns its result, allocated where `like` lives (dtype: np.int32 for an
+    entry point that writes int32)."""
+    out = _empty_like_field(out_shape, like, dtype)
     check(entry(*args, _ptr(out), mem))
     return out
 

@@ -185,6 +185,22 @@ struct OutField {
         if(host && n) GPP_HIP(hipMemcpyAsync(host, d, n * sizeof(float), hipMemcpyDeviceToHost, stream()));
     }
 };
+// the int32 form of OutField (the ranks of gpp_calc_ranks)
+struct OutInts {
+    Staged<int> staged;
+    int* d = nullptr;
+    int* host = nullptr;
+    size_t n = 0;
+    void bind(int* dst, size_t n_, int mem) {
+        n = n_;
+        if(!dst) { d = nullptr; host = nullptr; return; }
+        if(mem & GPP_MEM_DEVICE) { d = dst; host = nullptr; }
+        else { d = staged.get(n); host = dst; }
+    }
+    void finish() {
+        if(host && n) GPP_HIP(hipMemcpyAsync(host, d, n * sizeof(int), hipMemcpyDeviceToHost, stream()));
+    }
+};
 
 inline bool is_valid(float v) { return !std::isnan(v) && !std::isinf(v); }   // src/api/util.cpp:16-18
 

@@ -492,6 +492,22 @@ int gpp_calc_quantile(const float* array, long rows, int len, const float* quant
  * where that beats one selection per level (csrc/rows_quantiles.hip; the path override GPP_ROWS_QUANTILES = tile | block | loop forces a path
  * where it applies); longer rows, and nq == 1, run gpp_calc_quantile's selection once per level.  The result does not depend on the path. */
 int gpp_calc_quantiles(const float* array, long rows, int len, const float* quantiles, int nq, float* out, int mem);
+/* Ranks within rows, no counterpart in the reference (gridpp_amd.calc_ranks, sort_rows, reorder_by_ranks, calc_crps).  Valid means
+ * finite; valid values compare numerically (-0.0 == +0.0) and equal values are ordered by position, lower index first: the order of
+ * numpy.argsort(kind="stable") on the valid values of a row.  All arrays are [rows][len] with len contiguous and follow `mem`.  GPP_EINVAL
+ * before any device work: a negative size, a NULL pointer.  rows == 0 returns GPP_OK and writes nothing.  Rows of up to 160 values are ranked by
+ * counting out of LDS, 64 rows per wave; rows of up to 8192 are sorted in LDS, one workgroup per row; longer rows go through a segmented radix
+ * sort (csrc/rows_rank.hip; the path override GPP_ROWS_RANKS = tile | block | long forces a path where it applies).  The result does not depend
+ * on the path. */
+/* ranks[r][i] (int32) = #{valid j : a[j] < a[i]} + #{valid j < i : a[j] == a[i]}, -1 for an invalid a[i]; sorted[r][ranks[r][i]] = a[i] with
+ * its bits kept, NaN from the number of valid values on.  Either output may be NULL (both NULL is GPP_EINVAL); both come from one launch. */
+int gpp_calc_ranks(const float* array, long rows, int len, int* ranks, float* sorted, int mem);
+/* out[r][i] = sorted(values row r)[rank of templ[r][i] within its row]; NaN where templ[r][i] is invalid or its rank is not below the number of
+ * valid entries of the values row.  Bit for bit the composition of the two outputs of gpp_calc_ranks. */
+int gpp_reorder_by_ranks(const float* values, const float* templ, long rows, int len, float* out, int mem);
+/* out[r] = (1 / N) sum_k |x_(k) - y| - (1 / N^2) sum_k (2 k - N + 1) x_(k) over the N sorted valid members x_(k) of ensemble row r, y = ref[r];
+ * both sums in double, cast to float32 last; NaN when N == 0 or y is not finite.  ref and out hold rows values. */
+int gpp_calc_crps(const float* ensemble, const float* ref, long rows, int len, float* out, int mem);
 /* gridpp::calc_even_quantiles (util.cpp:261-338) and, with only_valid = 1,
  * gridpp::get_neighbourhood_thresholds (neighbourhood.cpp:243-295) over the n
  * values of a flattened field.  out holds num floats; *count = number written. */
