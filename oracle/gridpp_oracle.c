@@ -784,12 +784,16 @@ static int orc_upper_index(float x, const float* v, int n) {
     }
     return index;
 }
+/* util.cpp:377-414.  Where a scan finds no valid entry on its side the reference's index is (int) NaN and what it reads with it
+ * (util.cpp:391-396) is undefined.  The project's rule for that case is NaN, decided before any array is indexed: the device
+ * code states it (gridpp_amd/csrc/curve.h, interpolate / between) and tests/curve_ref.py restates it. */
 float orc_interpolate(float x, const float* iX, const float* iY, int n) {
     if(!orc_valid(x)) return NAN;
     if(n == 0) return NAN;
     if(x > iX[n - 1]) return iY[n - 1];
     if(x < iX[0]) return iY[0];
     int i0 = orc_lower_index(x, iX, n), i1 = orc_upper_index(x, iX, n);
+    if(i0 < 0 || i1 < 0) return NAN;
     float x0 = iX[i0], x1 = iX[i1], y0 = iY[i0], y1 = iY[i1];
     if(x0 == x1) {
         if(i0 == 0 && i1 == n - 1) return (y0 + y1) / 2;

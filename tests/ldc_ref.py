@@ -14,7 +14,9 @@ restatement alone (and the restatement by the hand-derived answers of tests/test
     trimming        d0 = (int)((float)count * min_quantile), d1 likewise; entries [d0, d1)
     the curves      (0, 0) prepended, sequential float32 cumulative rho, normalised as :151-154 (the leading 0 stays 0)
     branches        :156-198 in their order; 0.01 and 0.1 are double literals there, so those two comparisons are made in double
-    interpolate     the oracle's (src/api/util.cpp:377-414); exp rounded to float32
+    interpolate     the oracle's (src/api/util.cpp:377-414); exp rounded to float32.  Where a rho total of 0 has made a curve's quantiles
+                    NaN a scan can end without an index; the reference indexes with (int) NaN there, the project's rule is NaN
+                    (gridpp_amd/csrc/curve.h, tests/curve_ref.py) and the oracle follows it
 
 Per cell it also returns the branch taken and the count."""
 import math
@@ -48,12 +50,14 @@ def _curve(values, rho, d0, d1, stable, min_quantile, max_quantile):
     total = q[-1]
     with np.errstate(invalid="ignore", divide="ignore"):
         q[1:] = min_quantile + q[1:] / total * F(max_quantile - min_quantile)   # :151-154
-    return x, q
+    return x, q, total
 
 
-def ldc(O, cands, background, pobs, pbackground, min_quantile, max_quantile, min_points, stable=False, order=None):
+def ldc(O, cands, background, pobs, pbackground, min_quantile, max_quantile, min_points, stable=False, order=None, sums=None):
     """-> (out float32 of background's shape, tag per cell, count per cell).  pobs / pbackground are (S) or (T, S).
-    order: a function permuting each cell's enumeration (the sensitivity test shuffles it)."""
+    order: a function permuting each cell's enumeration (the sensitivity test shuffles it).
+    sums: a dict that receives, per cell that built its curves (NaN elsewhere), "sum_r" and "sum_f" -- the rho totals of the
+    trimmed ref and fcst curves, the divisors of :151-154 -- "sum_rho" and, on branch 4, the weight "w0"."""
     bg = np.asarray(background, F)
     b_flat = bg.ravel()
     po, pb = np.atleast_2d(np.asarray(pobs, F)), np.atleast_2d(np.asarray(pbackground, F))
@@ -61,6 +65,8 @@ def ldc(O, cands, background, pobs, pbackground, min_quantile, max_quantile, min
     nT = po.shape[0]
     out = b_flat.copy()
     tags, counts = [], np.zeros(b_flat.size, int)
+    if sums is not None:
+        sums.update({name: np.full(b_flat.size, np.nan, F) for name in ("sum_r", "sum_f", "sum_rho", "w0")})
     for k, (idx, rho) in enumerate(cands):
         b = b_flat[k]
         if not np.isfinite(b):   # :72
@@ -84,8 +90,10 @@ def ldc(O, cands, background, pobs, pbackground, min_quantile, max_quantile, min
             continue
         ref, fcst, w = np.array(ref, F), np.array(fcst, F), np.array(w, F) + F(0)
         d0, d1 = int(F(count) * min_quantile), int(F(count) * max_quantile)   # :121-122
-        x_ref, q_ref = _curve(ref, w, d0, d1, stable, min_quantile, max_quantile)
-        x_fcst, q_fcst = _curve(fcst, w, d0, d1, stable, min_quantile, max_quantile)
+        x_ref, q_ref, sum_r = _curve(ref, w, d0, d1, stable, min_quantile, max_quantile)
+        x_fcst, q_fcst, sum_f = _curve(fcst, w, d0, d1, stable, min_quantile, max_quantile)
+        if sums is not None:
+            sums["sum_r"][k], sums["sum_f"][k], sums["sum_rho"][k] = sum_r, sum_f, sum_rho
         if float(b) < 0.01:   # :156
             out[k] = 0
             tags.append(B1)
@@ -106,6 +114,8 @@ def ldc(O, cands, background, pobs, pbackground, min_quantile, max_quantile, min
             new_ref = F(O.interpolate(q, q_ref, x_ref))
             w0 = F(F(1) - F(math.exp(float(F(F(-0.01) * sum_rho)))))
             w1 = F(F(1) - w0)
+            if sums is not None:
+                sums["w0"][k] = w0
             out[k] = F(F(w0 * new_ref) + F(w1 * b))
             tags.append(B4)
     return out.reshape(bg.shape), np.array(tags), counts

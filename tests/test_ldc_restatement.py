@@ -73,6 +73,68 @@ def test_hand_derived_edges(O):
     np.testing.assert_array_equal(out, np.array([[0, 0.5, 3, 0]], F))
 
 
+def test_hand_derived_zero_rho(O):
+    """One cell at the origin, ten stations, T = 1, CrossValidation(Barnes 2 500, 1 000), quantiles 0.2 / 0.8, background 5.5: ten pairs,
+    d0 = (int)(10 x 0.2f) = 2, d1 = (int)(10 x 0.8f) = 8.  Stations 2 ... 7 lie within the cross-validation distance (rho = 0), the other
+    four 2 000 m away (rho = exp(-0.32) = 0.726149).
+
+    The trimmed ref curve all rho = 0, the fcst curve not: pobs = 1 ... 10 by station, so the six middle values 3 ... 8 are the inner
+    stations'; pbackground gives the outer stations 4 ... 7.  ref: values (0, 3, ..., 8), cumulative rho all 0, total 0, quantiles
+    (0, NaN x 6) -- the leading 0 is never normalised (:151).  fcst: values (0, 3, 4, 5, 6, 7, 8), cumulative rho (0, 0, r, 2r, 3r, 4r, 4r),
+    quantiles (0, 0.2, 0.35, 0.5, 0.65, 0.8, 0.8).  ref_last = 8 > 0 and 5.5 < fcst_last = 8: branch 4.  q = 0.5 + 0.15 / 2 = 0.575.  In the
+    second interpolate 0.575 is neither > NaN nor < 0; the scan from the front stops at index 0; the scan from the back skips the NaN,
+    meets 0 < 0.575 and leaves with no index: the reference indexes with (int) NaN there (util.cpp:391-396), the project's rule is NaN
+    (gridpp_amd/csrc/curve.h).  w0 = 1 - exp(-0.01 x 4r) is finite and not 0, so the result is NaN.
+
+    The mirror (pobs and pbackground exchanged): the fcst quantiles are (0, NaN x 6), 5.5 lies between its entries 5 and 6, q is NaN
+    and interpolate of an invalid x is NaN.
+
+    All ten stations within the distance: both totals and sum_rho are 0, w0 = 1 - exp(0) = 0, and 0 x NaN + 1 x 5.5 is NaN."""
+    g = O.Pts([[0.0]], [[0.0]], ctype=1)
+    x = np.array([2000.0, 0.0, 100, 200, 300, 400, 500, 600, -2000.0, 0.0])
+    y = np.array([0.0, 2000.0, 0, 0, 0, 0, 0, 0, 0.0, -2000.0])
+    st = O.Struct("Barnes", 2500).cross_validation(1000)
+    cands = R.candidates(O, g, O.Pts(y, x, ctype=1), st)
+    rho = F(np.exp(-0.5 * (2000.0 / 2500.0) ** 2))
+    np.testing.assert_array_equal(cands[0][0], np.arange(10))
+    np.testing.assert_allclose(cands[0][1], [rho, rho, 0, 0, 0, 0, 0, 0, rho, rho], rtol=2e-7)
+    middle = np.arange(1.0, 11.0)
+    spread = [4, 5, 9, 10, 1, 2, 3, 8, 6, 7]
+    for pobs, pbg, zero in ((middle, spread, "sum_r"), (spread, middle, "sum_f")):
+        sums = {}
+        out, tags, count = R.ldc(O, cands, [[5.5]], pobs, pbg, 0.2, 0.8, 0, sums=sums)
+        other = "sum_f" if zero == "sum_r" else "sum_r"
+        assert list(tags) == [R.B4] and list(count) == [10]
+        assert sums[zero][0] == 0 and abs(sums[other][0] - 4 * rho) < 1e-6 and abs(sums["sum_rho"][0] - 4 * rho) < 1e-6
+        assert abs(sums["w0"][0] - (1 - np.exp(-0.04 * rho))) < 1e-7
+        assert np.isnan(out[0, 0]), (zero, out)
+    # the fcst quantiles of the first case, as derived: the background maps to q = 0.575
+    xs, qs, total = R._curve(np.array(spread, F), cands[0][1], 2, 8, False, F(0.2), F(0.8))
+    np.testing.assert_array_equal(xs, [0, 3, 4, 5, 6, 7, 8])
+    np.testing.assert_allclose(qs, [0, 0.2, 0.35, 0.5, 0.65, 0.8, 0.8], atol=1e-6)
+    assert abs(O.interpolate(5.5, xs, qs) - 0.575) < 1e-6
+    # every station inside
+    inside = O.Pts(np.zeros(10), 100.0 * np.arange(10), ctype=1)
+    cands = R.candidates(O, g, inside, st)
+    assert (cands[0][1] == 0).all() and cands[0][0].size == 10
+    sums = {}
+    out, tags, _ = R.ldc(O, cands, [[5.5]], middle, spread, 0.2, 0.8, 0, sums=sums)
+    assert list(tags) == [R.B4] and sums["sum_r"][0] == 0 and sums["sum_f"][0] == 0 and sums["sum_rho"][0] == 0 and sums["w0"][0] == 0
+    assert np.isnan(out[0, 0])
+
+
+def test_interpolate_with_an_undefined_index_is_nan(O):
+    """the oracle's interpolate where one scan finds no valid entry on its side, and that nothing else moved: the defined cases of
+    util.cpp:377-414 as before"""
+    nan = np.nan
+    assert np.isnan(O.interpolate(0.5, [0, nan, nan], [0, 3, 4]))        # no valid entry >= x from the back
+    assert np.isnan(O.interpolate(0.5, [nan, nan, 1], [2, 3, 4]))        # no valid entry <= x from the front
+    assert O.interpolate(0.5, [0, nan, 1], [2, 3, 4]) == 3.0             # both found: NaN entries are skipped
+    assert O.interpolate(0.0, [0, nan, nan], [7, 3, 4]) == 7.0           # x on the one valid entry: both scans stop there
+    assert O.interpolate(2.0, [0, 1], [5, 6]) == 6.0 and O.interpolate(-1.0, [0, 1], [5, 6]) == 5.0
+    assert O.interpolate(0.25, [0, 1], [4, 8]) == 5.0
+
+
 @pytest.fixture(scope="module")
 def sensitivity(O):
     res = {}
