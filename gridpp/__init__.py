@@ -43,9 +43,12 @@ else:
     # the cube, and the per-threshold neighbourhood probabilities it interpolates in): gridpp_amd.neighbourhood_quantiles_fast, gridpp_amd.neighbourhood_cdf.
     # calc_ranks, sort_rows, reorder_by_ranks and calc_crps have none either (the rank of every member within its cell, the sorted
     # rows, ensemble copula coupling and the CRPS): gridpp_amd.calc_ranks, gridpp_amd.sort_rows, gridpp_amd.reorder_by_ranks, gridpp_amd.calc_crps.
+    # downscaling_plan and its DownscalingPlan have none either (the nearest grid point, box and weights of every output
+    # location computed once per pair of geometries and applied to any number of fields): gridpp_amd.downscaling_plan.
     for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve",
                   "optimal_interpolation_gain", "OiGain", "calc_quantiles", "quantile_mapping_curves",
-                  "neighbourhood_quantiles_fast", "neighbourhood_cdf", "calc_ranks", "sort_rows", "reorder_by_ranks", "calc_crps"):
+                  "neighbourhood_quantiles_fast", "neighbourhood_cdf", "calc_ranks", "sort_rows", "reorder_by_ranks", "calc_crps",
+                  "downscaling_plan", "DownscalingPlan"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

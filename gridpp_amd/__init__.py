@@ -1164,13 +1164,22 @@ def bilinear(igrid, opoints, values):
 Nearest, Bilinear = 0, 1   # include/gridpp.h:132-135
 
 
-def _downscale_setup(name, igrid, output, ivalues, fields=()):
-    """Checks shared by the downscalers -> (values, other fields, ndim, output shape, empty, f64).  Fields are float32 arrays (float64
-    where f64) or float32 device tensors; None stays None."""
+def _downscale_sets(name, igrid, output):
     if not isinstance(igrid, Grid):
         raise TypeError("%s: the input must be a Grid" % name)
     if not isinstance(output, (Grid, Points)):
         raise TypeError("%s: the output must be a Grid or Points" % name)
+
+
+def _downscale_setup(name, igrid, output, ivalues, fields=()):
+    """Checks shared by the downscalers -> (values, other fields, ndim, output shape, empty, f64).  Fields are float32 arrays (float64
+    where f64) or float32 device tensors; None stays None."""
+    _downscale_sets(name, igrid, output)
+    return _downscale_fields(name, _out_shape(output), ivalues, fields)
+
+
+def _downscale_fields(name, out_shape, ivalues, fields=()):
+    """_downscale_setup once the two sets are known to be a Grid and a Grid or Points; out_shape: the shape of a field on the output"""
     f64 = _wants_f64(ivalues, *fields)
     values = _m.field(ivalues, f64=f64)
     shp = _shape(values)
@@ -1179,7 +1188,7 @@ def _downscale_setup(name, igrid, output, ivalues, fields=()):
     # src/api/util.cpp:427-432: no rows (2-D) / no time levels or no rows (3-D) passes the size check
     empty = shp[0] == 0 or (len(shp) == 3 and shp[1] == 0)
     lead = (shp[0],) if len(shp) == 3 else ()
-    return values, [_m.field(a, f64=f64) for a in fields], len(shp), lead + _out_shape(output), empty, f64
+    return values, [_m.field(a, f64=f64) for a in fields], len(shp), lead + out_shape, empty, f64
 
 
 def _downscaler(downscaler):
@@ -1201,14 +1210,18 @@ def downscaling(igrid, output, ivalues, downscaler):
 def _gradient_call(entry, igrid, output, values, fields, oshape, empty, f64, downscaler, *args):
     """runs gpp_simple_gradient / gpp_full_gradient once the overload's checks have passed; fields = the present gradients"""
     downscaler = _downscaler(downscaler)
+    return _gradient_run(entry, (igrid._h, output._h), igrid._n, values, fields, oshape, empty, f64, *args, downscaler)
+
+
+def _gradient_run(entry, handles, n_in, values, fields, oshape, empty, f64, *args):
+    """entry(*handles, values, nt, *args, out, mem); n_in: the number of points of the input grid"""
     _mem(values, *fields)   # (mixed memory is refused whatever the shapes)
     if int(np.prod(oshape)) == 0:
         return _empty_like_field(oshape, values)
-    if igrid._n and empty:
+    if n_in and empty:
         raise ValueError("Grid size is not the same as values")   # nothing to read from (the reference would index past the end)
     nt = oshape[0] if len(_shape(values)) == 3 else 1
-    return _m.run(entry, igrid._h, output._h, _ptr(values), nt, *args, downscaler, out_shape=oshape, like=values,
-                  mem=_m.flags(f64, values, *fields))
+    return _m.run(entry, *handles, _ptr(values), nt, *args, out_shape=oshape, like=values, mem=_m.flags(f64, values, *fields))
 
 
 def simple_gradient(igrid, output, ivalues, elev_gradient, downscaler=Nearest):
@@ -1227,17 +1240,26 @@ def full_gradient(igrid, output, ivalues, elev_gradient, laf_gradient=_NO_LAF, d
     """src/api/gradient.cpp:5-274: d(values) + (laf_corr + elev_corr), elev_corr = d(elev_gradient) * (output elevation - d(grid
     elevation)) where both elevations are valid (else 0), laf_corr likewise.  A gradient with no elements leaves its term out.
     Gradients have the shape of the values; only the Grid -> Grid 2-D overload may leave out laf_gradient (include/gridpp.h:1065)."""
-    values, (egrad, lgrad), nd, oshape, empty, f64 = _downscale_setup(
-        "full_gradient", igrid, output, ivalues, (elev_gradient, None if laf_gradient is _NO_LAF else laf_gradient))
-    grid_vec2 = isinstance(output, Grid) and nd == 2
+    _downscale_sets("full_gradient", igrid, output)
+    values, egrad, lgrad, oshape, empty, f64 = _full_gradient_fields(tuple(igrid.size()), _out_shape(output), isinstance(output, Grid),
+                                                                     ivalues, elev_gradient, laf_gradient)
+    return _gradient_call(lib().gpp_full_gradient, igrid, output, values, [g for g in (egrad, lgrad) if g is not None], oshape, empty,
+                          f64, downscaler, _ptr(egrad), _ptr(lgrad))
+
+
+def _full_gradient_fields(ishape, out_shape, out_is_grid, ivalues, elev_gradient, laf_gradient):
+    """The overload rules and size checks of full_gradient -> (values, egrad, lgrad, output shape, empty, f64); an absent gradient is None"""
+    values, (egrad, lgrad), nd, oshape, empty, f64 = _downscale_fields(
+        "full_gradient", out_shape, ivalues, (elev_gradient, None if laf_gradient is _NO_LAF else laf_gradient))
+    grid_vec2 = out_is_grid and nd == 2
     if laf_gradient is _NO_LAF:
         if not grid_vec2:
             raise TypeError("full_gradient: laf_gradient is required unless both grids are 2-D fields (include/gridpp.h:1065-1098)")
         lgrad = np.zeros((0, 0), np.float32)
     if grid_vec2:   # gradient.cpp:10-11
-        if _shape(values) != tuple(igrid.size()):
+        if _shape(values) != ishape:
             raise ValueError("Values is the wrong size")
-    elif not empty and _shape(values)[-2:] != tuple(igrid.size()):
+    elif not empty and _shape(values)[-2:] != ishape:
         raise ValueError("Grid size is not the same as values")   # downscaling.cpp:8-9
     present = []
     # gradient.cpp:13-20 (checked in this order); the other overloads only assert it and would read past the end
@@ -1250,8 +1272,113 @@ def full_gradient(igrid, output, ivalues, elev_gradient, laf_gradient=_NO_LAF, d
         else:
             present.append(g)
     lgrad, egrad = present
-    return _gradient_call(lib().gpp_full_gradient, igrid, output, values, [g for g in (egrad, lgrad) if g is not None], oshape, empty,
-                          f64, downscaler, _ptr(egrad), _ptr(lgrad))
+    return values, egrad, lgrad, oshape, empty, f64
+
+
+# ---- the reusable downscaling plan (include/gridpp_hip.h: gpp_downscale_plan_*; no counterpart in the reference) -------------------
+class DownscalingPlan:
+    """What downscaling_plan returns: for every output location the nearest grid point and, for Bilinear, its box and weights."""
+
+    def __init__(self, handle, igrid, output, downscaler):
+        self._h, self.downscaler = handle, downscaler
+        self._ishape, self._n_in = tuple(igrid.size()), igrid._n
+        self._oshape, self._out_grid = _out_shape(output), isinstance(output, Grid)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:   # noqa: BLE001  (interpreter shutdown)
+            pass
+
+    def release(self):
+        """gpp_downscale_plan_destroy: returns the HBM the plan holds (`nbytes`); the plan cannot be used afterwards."""
+        h, self._h = self._h, None
+        if h:
+            check(lib().gpp_downscale_plan_destroy(h))
+
+    def _handle(self):
+        if not self._h:
+            raise RuntimeError("the plan was released")
+        return self._h
+
+    def apply(self, values):
+        """downscaling(igrid, output, values, downscaler), bit for bit: values (Y, X) or (T, Y, X)."""
+        h = self._handle()
+        values, _, _, oshape, empty, f64 = _downscale_fields("downscaling", self._oshape, values)
+        if not empty and _shape(values)[-2:] != self._ishape:
+            raise ValueError("Grid size is not the same as values")
+        return _gradient_run(lib().gpp_downscale_plan_apply, (h,), self._n_in, values, (), oshape, empty, f64)
+
+    def apply_cube(self, values):
+        """An ensemble in gridpp's cube layout, (Y, X, E) -> (oY, oX, E) or (N, E): plane [..., e] is downscaling(igrid, output,
+        values[..., e], downscaler), bit for bit.  For Bilinear the four-corner validity test is per member and location."""
+        h = self._handle()
+        f64 = _wants_f64(values)
+        values = _m.field(values, f64=f64)
+        shp = _shape(values)
+        if len(shp) != 3:
+            raise RuntimeError("apply_cube: values must be 3-D (Y, X, E)")
+        if shp[:2] != self._ishape:
+            raise ValueError("Grid size is not the same as values")
+        oshape = self._oshape + (shp[2],)
+        if int(np.prod(oshape)) == 0:
+            return _empty_like_field(oshape, values)
+        return _m.run(lib().gpp_downscale_plan_apply_cube, h, _ptr(values), shp[2], out_shape=oshape, like=values, mem=_m.flags(f64, values))
+
+    def simple_gradient(self, values, elev_gradient):
+        """simple_gradient(igrid, output, values, elev_gradient, downscaler), bit for bit."""
+        h = self._handle()
+        values, _, _, oshape, empty, f64 = _downscale_fields("simple_gradient", self._oshape, values)
+        if not empty and _shape(values)[-2:] != self._ishape:
+            raise ValueError("Grid size is not the same as values")
+        return _gradient_run(lib().gpp_downscale_plan_simple_gradient, (h,), self._n_in, values, (), oshape, empty, f64, float(elev_gradient))
+
+    def full_gradient(self, values, elev_gradient, laf_gradient=_NO_LAF):
+        """full_gradient(igrid, output, values, elev_gradient, laf_gradient, downscaler), bit for bit, with its overload rules."""
+        h = self._handle()
+        values, egrad, lgrad, oshape, empty, f64 = _full_gradient_fields(self._ishape, self._oshape, self._out_grid, values, elev_gradient,
+                                                                         laf_gradient)
+        return _gradient_run(lib().gpp_downscale_plan_full_gradient, (h,), self._n_in, values, [g for g in (egrad, lgrad) if g is not None],
+                             oshape, empty, f64, _ptr(egrad), _ptr(lgrad))
+
+    def _info(self):
+        locations, cells, nbytes, distorted = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+        downscaler = C.c_int()
+        check(lib().gpp_downscale_plan_info(self._handle(), C.byref(locations), C.byref(cells), C.byref(downscaler), C.byref(nbytes),
+                                            C.byref(distorted)))
+        return locations.value, cells.value, downscaler.value, nbytes.value, distorted.value
+
+    @property
+    def nbytes(self):
+        """HBM the plan holds: 4 (Nearest) or 16 (Bilinear) bytes per output location, plus the elevations and lafs of both sets."""
+        return self._info()[3]
+
+    @property
+    def distorted(self):
+        """output locations whose bilinear weights leave [0, 1]: an apply raises there once a field has four valid corners"""
+        return self._info()[4]
+
+
+def downscaling_plan(igrid, output, downscaler=Nearest):
+    """Everything of downscaling, simple_gradient and full_gradient that does not depend on a value, computed once: the nearest grid
+    point of every output location and, for Bilinear, its box and weights (src/api/grid.cpp:149-229, bilinear.cpp:137-320).
+
+        plan = downscaling_plan(igrid, ogrid, Bilinear)
+        out = plan.apply(values)                    # = downscaling(igrid, ogrid, values, Bilinear)
+        out = plan.apply_cube(values_yxe)           # an ensemble in gridpp's cube layout, E innermost
+        out = plan.full_gradient(values, egrad, lgrad)
+
+    instead of a loop of direct calls over lead times, members or variables on the same pair of grids.  The plan holds 4 (Nearest) or
+    16 (Bilinear) bytes of HBM per output location plus copies of both sets' elevations and lafs (`nbytes`) until release() or until
+    it is garbage-collected; igrid and output may be dropped first.  A box whose weights leave [0, 1] does not fail the construction
+    (`distorted` counts them): the methods raise where the direct calls do."""
+    _downscale_sets("downscaling_plan", igrid, output)
+    downscaler = _downscaler(downscaler)
+    if downscaler == Nearest and igrid.get_coordinate_type() != output.get_coordinate_type():
+        raise ValueError("Coordinate types must be the same")
+    handle = C.c_void_p()
+    check(lib().gpp_downscale_plan_create(igrid._h, output._h, downscaler, C.byref(handle)))
+    return DownscalingPlan(handle, igrid, output, downscaler)
 
 
 # ---- ensemble downscalers and smart (include/gridpp.h:138-143,945-990,1112) ----------------------------------------------

@@ -159,6 +159,13 @@ SIGNATURES = {
     "gpp_oi_gain_info": [vp, C.POINTER(C.c_longlong), ip, ip, C.POINTER(C.c_longlong), ip],
     "gpp_oi_gain_selection": [vp, vp, vp, vp, C.c_int],
     "gpp_oi_gain_destroy": [vp],
+    "gpp_downscale_plan_create": [vp, vp, C.c_int, C.POINTER(vp)],
+    "gpp_downscale_plan_apply": [vp, vp, C.c_int, vp, C.c_int],
+    "gpp_downscale_plan_apply_cube": [vp, vp, C.c_int, vp, C.c_int],
+    "gpp_downscale_plan_simple_gradient": [vp, vp, C.c_int, C.c_float, vp, C.c_int],
+    "gpp_downscale_plan_full_gradient": [vp, vp, C.c_int, vp, vp, vp, C.c_int],
+    "gpp_downscale_plan_info": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+    "gpp_downscale_plan_destroy": [vp],
 }
 STRING_GETTERS = ("gpp_last_error", "gpp_version")
 

@@ -1,0 +1,421 @@
+// The reusable downscaling plan (include/gridpp_hip.h: gpp_downscale_plan_*).  Everything of nearest / bilinear /
+// simple_gradient / full_gradient that depends on no value -- the nearest grid point of every output location, its box (Grid::get_box)
+// and the weights (s, t) -- is computed ONCE per pair of geometries; an apply is then a gather and, for Bilinear, four products per
+// location and field: no search, no box test, no double-precision solve.
+//
+// Record of an output location:
+//   Nearest    int32          the nearest grid point (-1: none)
+//   Bilinear   int4, 16 B     .x the nearest grid point; .y the flat index c of corner (Y1, X1) of its box, -1 when it is in no box,
+//                             -2 - c when the weights of the box leave [0, 1] (the reference throws there); .z / .w the bits of s / t.
+// get_box always returns Y2 = Y1 + 1 and X2 = X1 + 1, so the other corners are c + nX, c + 1 and c + nX + 1, and the nearest grid point
+// is one of the four: inside a box the nearest-neighbour fallback of a field with a missing corner takes that corner's value from the
+// registers instead of a fifth load.
+//
+// The error of a distorted box keeps the condition of the direct calls: a location with bad weights raises in the apply in which one
+// of the downscaled fields has four valid corners there (bilinear.cpp:309-313), never at construction.
+#include "common.h"
+#include "bilinear_geom.h"
+#include <climits>
+#include <memory>
+
+using namespace gpp;
+
+namespace {
+
+__global__ __launch_bounds__(256) void k_plan_build(const float* __restrict__ glat, const float* __restrict__ glon, int nY, int nX,
+                                                    const int* __restrict__ nn, const float* __restrict__ qlat,
+                                                    const float* __restrict__ qlon, int nq, int4* __restrict__ rec,
+                                                    unsigned long long* __restrict__ distorted) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if(q >= nq) return;
+    const int n0 = nn[q];
+    const float lat = qlat[q], lon = qlon[q];
+    int I1, J1, I2, J2;
+    int code = -1;
+    float s = 0, t = 0;
+    if(get_box(glat, glon, nY, nX, n0, lat, lon, I1, J1, I2, J2)) {
+        const int i0 = I1 * nX + J1, i1 = I2 * nX + J1, i2 = I1 * nX + J2, i3 = I2 * nX + J2;
+        const bool bad = weights(lon, lat, glon[i0], glon[i1], glon[i2], glon[i3], glat[i0], glat[i1], glat[i2], glat[i3], s, t);
+        code = bad ? -2 - i0 : i0;
+        if(bad) atomicAdd(distorted, 1ull);
+    }
+    rec[q] = make_int4(n0, code, __float_as_int(s), __float_as_int(t));
+}
+
+// A record in registers.  c >= 0: corner (Y1, X1) of the box; `bad`: its weights leave [0, 1].
+struct Loc {
+    int n0, c;
+    bool inside, bad;
+    float s, t;
+};
+template <bool BIL>
+__device__ __forceinline__ Loc load_loc(const int4* __restrict__ rec, const int* __restrict__ nn, const int q) {
+    Loc l;
+    l.c = -1; l.inside = false; l.bad = false; l.s = 0; l.t = 0;
+    if(BIL) {
+        const int4 r = rec[q];
+        l.n0 = r.x;
+        l.inside = r.y != -1;
+        l.bad = r.y < -1;
+        l.c = l.bad ? -2 - r.y : r.y;
+        l.s = __int_as_float(r.z); l.t = __int_as_float(r.w);
+    }
+    else l.n0 = nn[q];
+    return l;
+}
+__device__ __forceinline__ void flag_distorted(int* __restrict__ err, const float s, const float t) {
+    if(atomicCAS(&err[0], 0, 1) == 0) { err[1] = __float_as_int(s); err[2] = __float_as_int(t); }
+}
+// the value of a field with corners v0 = (Y1, X1), v1 = (Y2, X1), v2 = (Y1, X2), v3 = (Y2, X2) at a location inside that box
+__device__ __forceinline__ float in_box(const Loc& l, const float v0, const float v1, const float v2, const float v3, const int nX,
+                                        bool& flagged, int* __restrict__ err) {
+    if(dev_valid(v0) && dev_valid(v1) && dev_valid(v2) && dev_valid(v3)) {
+        if(l.bad && !flagged) { flag_distorted(err, l.s, l.t); flagged = true; }
+        return bilinear_value(v0, v1, v2, v3, l.s, l.t);
+    }
+    const int d = l.n0 - l.c;   // a missing corner: the nearest grid point, one of the four
+    return d == 0 ? v0 : d == nX ? v1 : d == 1 ? v2 : v3;
+}
+// d(f) at a location: a level of (T, Y, X)
+template <bool BIL>
+__device__ __forceinline__ float down(const Loc& l, const float* __restrict__ f, const int nX, bool& flagged, int* __restrict__ err) {
+    if(BIL && l.inside) return in_box(l, f[l.c], f[l.c + nX], f[l.c + 1], f[l.c + nX + 1], nX, flagged, err);
+    return l.n0 >= 0 ? f[l.n0] : NAN;   // outside the domain: nearest neighbour
+}
+
+// values [nt][nG] -> out [nt][nq]: a location per thread, unit-stride writes across lanes per level (as k_bilinear / k_gather_levels)
+template <bool BIL>
+__global__ __launch_bounds__(256) void k_plan_apply(const int4* __restrict__ rec, const int* __restrict__ nn, const int nq, const int nX,
+                                                    const size_t nG, const float* __restrict__ values, const int nt,
+                                                    float* __restrict__ out, int* __restrict__ err) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if(q >= nq) return;
+    const Loc l = load_loc<BIL>(rec, nn, q);
+    bool flagged = false;
+    for(int k = 0; k < nt; ++k) out[(size_t)k * nq + q] = down<BIL>(l, values + (size_t)k * nG, nX, flagged, err);
+}
+
+// values [nG][E] -> out [nq][E] (gridpp's cube layout, the member index innermost): G lanes per location, 64 / G locations per wave;
+// lane j of a group takes V members at V j, V (j + G), ...: every corner is read as runs of V G contiguous floats and the output run is
+// written with unit stride across the group.  The four-corner validity test is per member.  V = 2 (one 8-byte access per lane; E even,
+// both arrays 8-byte aligned) is the measured winner for Bilinear, V = 1 serves every other case.
+template <int V> struct VecOf;
+template <> struct VecOf<1> { using type = float; };
+template <> struct VecOf<2> { using type = float2; };
+template <bool BIL, int G, int V>
+__global__ __launch_bounds__(256) void k_plan_apply_cube(const int4* __restrict__ rec, const int* __restrict__ nn, const int nq,
+                                                         const int nX, const float* __restrict__ values, const int E,
+                                                         float* __restrict__ out, int* __restrict__ err) {
+    using vec = typename VecOf<V>::type;
+    const size_t g = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+    if(g >= (size_t)nq) return;
+    const int q = (int)g, lane = threadIdx.x % G;
+    const Loc l = load_loc<BIL>(rec, nn, q);
+    bool flagged = false;
+    float* __restrict__ o = out + (size_t)q * E;
+    for(int e = lane * V; e < E; e += G * V) {
+        union { vec v; float f[V]; } a0, a1, a2, a3, r;
+        if(BIL && l.inside) {
+            const float* __restrict__ f = values + (size_t)l.c * E + e;
+            a0.v = *reinterpret_cast<const vec*>(f); a1.v = *reinterpret_cast<const vec*>(f + (size_t)nX * E);
+            a2.v = *reinterpret_cast<const vec*>(f + E); a3.v = *reinterpret_cast<const vec*>(f + (size_t)(nX + 1) * E);
+#pragma unroll
+            for(int u = 0; u < V; ++u) r.f[u] = in_box(l, a0.f[u], a1.f[u], a2.f[u], a3.f[u], nX, flagged, err);
+        }
+        else if(l.n0 >= 0) r.v = *reinterpret_cast<const vec*>(values + (size_t)l.n0 * E + e);   // outside the domain: nearest neighbour
+        else {
+#pragma unroll
+            for(int u = 0; u < V; ++u) r.f[u] = NAN;
+        }
+        *reinterpret_cast<vec*>(o + e) = r.v;
+    }
+}
+
+struct GradientArgs {
+    const int4* rec; const int* nn; int nq, nX;
+    const float* values; const float* egrad; const float* lgrad;   // [nt][n_in]; egrad / lgrad NULL = term absent
+    int nt; size_t n_in;
+    const float* ielev; const float* ilaf;               // input grid [n_in]
+    const float* oelev; const float* olaf;               // output locations [nq]
+    float elev_gradient;                                 // simple_gradient's scalar
+    int full;                                            // 0: simple_gradient, 1: full_gradient
+    float* out;                                          // [nt][nq]
+    int* err;
+};
+
+// k_downscale (downscale.hip) with d(f) read from the record.  A gradient whose term is switched off at a location is still downscaled
+// by the reference and may raise there: its corners are read only where the weights are bad and nothing has raised yet.
+template <bool BIL>
+__global__ __launch_bounds__(256) void k_plan_gradient(const GradientArgs a) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if(q >= a.nq) return;
+    const Loc l = load_loc<BIL>(a.rec, a.nn, q);
+    bool flagged = false;
+    auto d = [&](const float* __restrict__ f) -> float { return down<BIL>(l, f, a.nX, flagged, a.err); };
+    const size_t nq = a.nq;
+    if(!a.full) {   // simple_gradient.cpp: out = d(values) + (oelev - d(ielevs)) * elev_gradient, no validity test
+        const float elev_corr = (a.oelev[q] - d(a.ielev)) * a.elev_gradient;
+        for(int k = 0; k < a.nt; ++k) a.out[(size_t)k * nq + q] = d(a.values + (size_t)k * a.n_in) + elev_corr;
+        return;
+    }
+    // gradient.cpp:56-81: a term counts where the output's and the downscaled input's elevation (laf) are both valid
+    float ediff = 0, ldiff = 0;
+    bool euse = false, luse = false;
+    if(a.egrad) {
+        const float oe = a.oelev[q], ie = d(a.ielev);
+        euse = dev_valid(oe) && dev_valid(ie);
+        ediff = oe - ie;
+    }
+    if(a.lgrad) {
+        const float ol = a.olaf[q], il = d(a.ilaf);
+        luse = dev_valid(ol) && dev_valid(il);
+        ldiff = ol - il;
+    }
+    for(int k = 0; k < a.nt; ++k) {
+        const size_t off = (size_t)k * a.n_in;
+        const float v = d(a.values + off);
+        float laf_corr = 0, elev_corr = 0;
+        if(a.lgrad) {
+            if(luse) laf_corr = d(a.lgrad + off) * ldiff;
+            else if(BIL && l.bad && !flagged) (void)d(a.lgrad + off);
+        }
+        if(a.egrad) {
+            if(euse) elev_corr = d(a.egrad + off) * ediff;
+            else if(BIL && l.bad && !flagged) (void)d(a.egrad + off);
+        }
+        a.out[(size_t)k * nq + q] = v + (laf_corr + elev_corr);
+    }
+}
+
+__global__ void k_plan_fill_nan(float* out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i < n) out[i] = NAN;
+}
+
+int group_of(int E) {   // as ensemble_downscale.hip: the smallest of 4 ... 64 with E <= 4 G
+    for(int g = 4; g < 64; g *= 2) if(E <= 4 * g) return g;
+    return 64;
+}
+
+}   // namespace
+
+struct gpp_downscale_plan {
+    int downscaler = 0, nY = 0, nX = 0, nq = 0;
+    size_t n_in = 0;
+    long long distorted = 0;
+    DevBuf<int4> rec;                        // Bilinear
+    DevBuf<int> nn;                          // Nearest
+    DevBuf<float> ielev, ilaf, oelev, olaf;  // copies of the two sets' elevations and land area fractions (the gradient methods)
+    DevBuf<int> err;
+    long long bytes() const {
+        return (long long)(rec.cap * sizeof(int4) + (nn.cap + err.cap) * sizeof(int) + (ielev.cap + ilaf.cap + oelev.cap + olaf.cap) * sizeof(float));
+    }
+};
+
+namespace {
+
+void copy_field(DevBuf<float>& dst, const float* src, size_t n) {
+    dst.get(n);
+    if(n) GPP_HIP(hipMemcpyAsync(dst.p, src, n * sizeof(float), hipMemcpyDeviceToDevice, stream()));
+}
+
+// What the entry points of a plan share once their own checks have passed: the output, an all-NaN result for an empty input grid
+// (nearest.cpp:132-134, bilinear.cpp:37-39), and the error of a distorted box after the kernel.
+struct PlanCall {
+    gpp_downscale_plan* p;
+    OutField o;
+    bool done = false;
+    PlanCall(gpp_downscale_plan* plan, const float* values, float* out, size_t nout, int mem) : p(plan) {
+        if(!out) invalid("out is NULL");
+        o.bind(out, nout, mem);
+        if(p->n_in == 0) {
+            hipLaunchKernelGGL(k_plan_fill_nan, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream(), o.d, nout);
+            GPP_HIP(hipGetLastError());
+            o.finish();
+            GPP_HIP(hipStreamSynchronize(stream()));
+            done = true;
+            return;
+        }
+        if(!values) invalid("values is NULL");
+        p->err.get(4);
+        GPP_HIP(hipMemsetAsync(p->err.p, 0, 4 * sizeof(int), stream()));
+    }
+    void finish() {
+        GPP_HIP(hipGetLastError());
+        int herr[4];
+        GPP_HIP(hipMemcpyAsync(herr, p->err.p, sizeof(herr), hipMemcpyDeviceToHost, stream()));
+        o.finish();
+        GPP_HIP(hipStreamSynchronize(stream()));
+        bilinear_check_distorted(herr);
+    }
+};
+
+void plan_gradient(gpp_downscale_plan* p, const float* values, int nt, const float* egrad, const float* lgrad, float elev_gradient, int full,
+                   float* out, int mem) {
+    if(!p) invalid("plan handle is NULL");
+    if(nt < 0) invalid("negative number of time levels");
+    if(p->nq == 0 || nt == 0) return;
+    ensure_device();
+    mem &= ~GPP_ASYNC;
+    PlanCall call(p, values, out, (size_t)nt * p->nq, mem);
+    if(call.done) return;
+    const size_t nin = (size_t)nt * p->n_in;
+    InField v, eg, lg;
+    v.bind(values, nin, mem);
+    eg.bind(egrad, nin, mem);
+    lg.bind(lgrad, nin, mem);
+    GradientArgs a;
+    a.rec = p->rec.p; a.nn = p->nn.p; a.nq = p->nq; a.nX = p->nX;
+    a.values = v.d; a.egrad = eg.d; a.lgrad = lg.d;
+    a.nt = nt; a.n_in = p->n_in;
+    a.ielev = p->ielev.p; a.ilaf = p->ilaf.p; a.oelev = p->oelev.p; a.olaf = p->olaf.p;
+    a.elev_gradient = elev_gradient;
+    a.full = full;
+    a.out = call.o.d; a.err = p->err.p;
+    const dim3 grid((p->nq + 255) / 256), block(256);
+    if(p->downscaler == 1) hipLaunchKernelGGL(k_plan_gradient<true>, grid, block, 0, stream(), a);
+    else hipLaunchKernelGGL(k_plan_gradient<false>, grid, block, 0, stream(), a);
+    call.finish();
+}
+
+}   // namespace
+
+extern "C" int gpp_downscale_plan_create(gpp_points* igrid, gpp_points* to, int downscaler, gpp_downscale_plan** plan) {
+    GPP_TRY
+    if(!igrid || !to || !plan) invalid("grid / points / plan handle is NULL");
+    if(igrid->n > 0 && igrid->nx <= 0) invalid("the input must be a Grid");
+    if(downscaler != 0 && downscaler != 1) invalid("Invalid downscaler");   // downscaling.cpp:16-17
+    if(downscaler == 0 && igrid->type != to->type) invalid("Coordinate types must be the same");   // as gpp_nearest_levels
+    ensure_device();
+    std::unique_ptr<gpp_downscale_plan> p(new gpp_downscale_plan);
+    p->downscaler = downscaler; p->nY = igrid->ny; p->nX = igrid->nx; p->nq = to->n; p->n_in = (size_t)igrid->n;
+    const int nq = to->n;
+    if(nq > 0 && igrid->n > 0) {
+        igrid->to_device();
+        to->to_device();
+        copy_field(p->ielev, igrid->d_elev.p, p->n_in); copy_field(p->ilaf, igrid->d_laf.p, p->n_in);
+        copy_field(p->oelev, to->d_elev.p, nq); copy_field(p->olaf, to->d_laf.p, nq);
+        if(downscaler == 0) {
+            p->nn.get(nq);
+            gpp_nearest_device(igrid, to->d_x.p, to->d_y.p, to->d_z.p, nq, 1, p->nn.p);
+        }
+        else {
+            to->latlon_to_device();
+            igrid->latlon_to_device();
+            DevBuf<int> idx;
+            DevBuf<unsigned long long> count;
+            idx.get(nq); count.get(1);
+            p->rec.get(nq);
+            GPP_HIP(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), stream()));
+            gpp_nearest_device(igrid, to->d_x.p, to->d_y.p, to->d_z.p, nq, 1, idx.p);
+            hipLaunchKernelGGL(k_plan_build, dim3((nq + 255) / 256), dim3(256), 0, stream(), igrid->d_lat.p, igrid->d_lon.p, igrid->ny, igrid->nx,
+                               idx.p, to->d_lat.p, to->d_lon.p, nq, p->rec.p, count.p);
+            GPP_HIP(hipGetLastError());
+            unsigned long long h = 0;
+            GPP_HIP(hipMemcpyAsync(&h, count.p, sizeof(h), hipMemcpyDeviceToHost, stream()));
+            GPP_HIP(hipStreamSynchronize(stream()));
+            p->distorted = (long long)h;
+        }
+        GPP_HIP(hipStreamSynchronize(stream()));
+    }
+    *plan = p.release();
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_destroy(gpp_downscale_plan* plan) {
+    GPP_TRY
+    delete plan;
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_info(const gpp_downscale_plan* plan, long long* locations, long long* cells, int* downscaler, long long* bytes,
+                                       long long* distorted) {
+    GPP_TRY
+    if(!plan) invalid("plan handle is NULL");
+    if(locations) *locations = plan->nq;
+    if(cells) *cells = (long long)plan->n_in;
+    if(downscaler) *downscaler = plan->downscaler;
+    if(bytes) *bytes = plan->bytes();
+    if(distorted) *distorted = plan->distorted;
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_apply(gpp_downscale_plan* plan, const float* values, int nt, float* out, int mem) {
+    GPP_TRY
+    if(!plan) invalid("plan handle is NULL");
+    if(nt < 0) invalid("negative number of time levels");
+    if(plan->nq == 0 || nt == 0) return GPP_OK;
+    ensure_device();
+    mem &= ~GPP_ASYNC;
+    PlanCall call(plan, values, out, (size_t)nt * plan->nq, mem);
+    if(call.done) return GPP_OK;
+    InField v;
+    v.bind(values, (size_t)nt * plan->n_in, mem);
+    const dim3 grid((plan->nq + 255) / 256), block(256);
+    if(plan->downscaler == 1)
+        hipLaunchKernelGGL(k_plan_apply<true>, grid, block, 0, stream(), (const int4*)plan->rec.p, (const int*)nullptr, plan->nq, plan->nX, plan->n_in,
+                           v.d, nt, call.o.d, plan->err.p);
+    else
+        hipLaunchKernelGGL(k_plan_apply<false>, grid, block, 0, stream(), (const int4*)nullptr, (const int*)plan->nn.p, plan->nq, plan->nX, plan->n_in,
+                           v.d, nt, call.o.d, plan->err.p);
+    call.finish();
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_apply_cube(gpp_downscale_plan* plan, const float* values, int ne, float* out, int mem) {
+    GPP_TRY
+    if(!plan) invalid("plan handle is NULL");
+    if(ne < 0) invalid("negative number of members");
+    if(plan->nq == 0 || ne == 0) return GPP_OK;
+    ensure_device();
+    mem &= ~GPP_ASYNC;
+    PlanCall call(plan, values, out, (size_t)ne * plan->nq, mem);
+    if(call.done) return GPP_OK;
+    InField v;
+    v.bind(values, (size_t)ne * plan->n_in, mem);
+    const bool bil = plan->downscaler == 1;
+    // 8-byte accesses where every row of members starts on an 8-byte boundary: measured faster than scalar ones for Bilinear on both
+    // geometries of DESIGN.md 4.19, not for Nearest (and 16-byte ones only on one of the two)
+    const bool wide = bil && ne % 2 == 0 && ((uintptr_t)v.d | (uintptr_t)call.o.d) % 8 == 0;
+    const int G = group_of(wide ? ne / 2 : ne);
+    const size_t blocks = ((size_t)plan->nq + 256 / G - 1) / (256 / G);
+    if(blocks > (size_t)INT_MAX) invalid("too many output locations for this many members");
+    const dim3 grid((unsigned)blocks), block(256);
+#define GPP_CUBE(G_)                                                                                                                      \
+    if(wide) hipLaunchKernelGGL((k_plan_apply_cube<true, G_, 2>), grid, block, 0, stream(), (const int4*)plan->rec.p, (const int*)nullptr, \
+                                plan->nq, plan->nX, v.d, ne, call.o.d, plan->err.p);                                                       \
+    else if(bil) hipLaunchKernelGGL((k_plan_apply_cube<true, G_, 1>), grid, block, 0, stream(), (const int4*)plan->rec.p,                  \
+                                    (const int*)nullptr, plan->nq, plan->nX, v.d, ne, call.o.d, plan->err.p);                              \
+    else hipLaunchKernelGGL((k_plan_apply_cube<false, G_, 1>), grid, block, 0, stream(), (const int4*)nullptr, (const int*)plan->nn.p,     \
+                            plan->nq, plan->nX, v.d, ne, call.o.d, plan->err.p)
+    switch(G) {
+        case 4: GPP_CUBE(4); break;
+        case 8: GPP_CUBE(8); break;
+        case 16: GPP_CUBE(16); break;
+        case 32: GPP_CUBE(32); break;
+        default: GPP_CUBE(64); break;
+    }
+#undef GPP_CUBE
+    call.finish();
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_simple_gradient(gpp_downscale_plan* plan, const float* values, int nt, float elev_gradient, float* out, int mem) {
+    GPP_TRY
+    plan_gradient(plan, values, nt, nullptr, nullptr, elev_gradient, 0, out, mem);
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_full_gradient(gpp_downscale_plan* plan, const float* values, int nt, const float* elev_gradient,
+                                                const float* laf_gradient, float* out, int mem) {
+    GPP_TRY
+    plan_gradient(plan, values, nt, elev_gradient, laf_gradient, 0, 1, out, mem);
+    return GPP_OK;
+    GPP_CATCH
+}

@@ -736,6 +736,32 @@ int gpp_oi_gain_info(const gpp_oi_gain* gain, long long* cells, int* stations, i
 int gpp_oi_gain_selection(gpp_oi_gain* gain, int* counts, int* indices, double* weights, int mem);
 int gpp_oi_gain_destroy(gpp_oi_gain* gain);
 
+/* ---- the reusable downscaling plan (no counterpart in the reference; gridpp_amd/csrc/downscale_plan.hip) -------------
+ * nearest, bilinear, simple_gradient and full_gradient start with the same value-independent work: the nearest grid point of every output
+ * location and, for Bilinear, its box (Grid::get_box) and the weights (s, t).  A plan holds the result -- 4 bytes per output location for
+ * Nearest, one 16-byte record for Bilinear -- and downscales any number of fields with it; every result is, bit for bit, that of the
+ * direct call on the same inputs.  A plan copies what it needs (the records, and the elevations and land area fractions of both sets for
+ * the gradient methods), so the Grid / Points it was built from may be destroyed first.  GPP_ASYNC is ignored here. */
+typedef struct gpp_downscale_plan gpp_downscale_plan;
+/* igrid: a Grid; to: a Grid or Points; downscaler: 0 Nearest, 1 Bilinear.  GPP_EINVAL before any device work: a NULL handle, an input that
+ * is no Grid, "Invalid downscaler", and for Nearest "Coordinate types must be the same".  A box whose weights leave [0, 1] never fails the
+ * construction: it is counted (gpp_downscale_plan_info: distorted), and an apply raises "Problem with bilinear interpolation..."
+ * (GPP_ERUNTIME) exactly where the direct call would -- when one of the fields it downscales has four valid corners at such a location. */
+int gpp_downscale_plan_create(gpp_points* igrid, gpp_points* to, int downscaler, gpp_downscale_plan** plan);
+/* values [nt][Y * X] -> out [nt][locations]: gpp_nearest_levels / gpp_bilinear.  `mem` as everywhere (GPP_HOST_F64 for values). */
+int gpp_downscale_plan_apply(gpp_downscale_plan* plan, const float* values, int nt, float* out, int mem);
+/* values [Y * X][ne] -> out [locations][ne] (gridpp's cube layout, the member index innermost): plane e is gpp_nearest_levels /
+ * gpp_bilinear of plane e; for Bilinear the four-corner validity test is per member and location.  Any ne >= 0. */
+int gpp_downscale_plan_apply_cube(gpp_downscale_plan* plan, const float* values, int ne, float* out, int mem);
+/* gpp_simple_gradient / gpp_full_gradient with the plan's geometries and downscaler (elev_gradient / laf_gradient NULL: term absent) */
+int gpp_downscale_plan_simple_gradient(gpp_downscale_plan* plan, const float* values, int nt, float elev_gradient, float* out, int mem);
+int gpp_downscale_plan_full_gradient(gpp_downscale_plan* plan, const float* values, int nt, const float* elev_gradient,
+                                     const float* laf_gradient, float* out, int mem);
+/* any pointer may be NULL; cells: points of the input grid; bytes: the HBM the plan holds; distorted: locations whose weights leave [0, 1] */
+int gpp_downscale_plan_info(const gpp_downscale_plan* plan, long long* locations, long long* cells, int* downscaler, long long* bytes,
+                            long long* distorted);
+int gpp_downscale_plan_destroy(gpp_downscale_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif
