@@ -1283,6 +1283,7 @@ class DownscalingPlan:
         self._h, self.downscaler = handle, downscaler
         self._ishape, self._n_in = tuple(igrid.size()), igrid._n
         self._oshape, self._out_grid = _out_shape(output), isinstance(output, Grid)
+        self._itype, self._otype = igrid.get_coordinate_type(), output.get_coordinate_type()   # (a Bilinear plan may span two)
 
     def __del__(self):
         try:
@@ -1341,6 +1342,91 @@ class DownscalingPlan:
         return _gradient_run(lib().gpp_downscale_plan_full_gradient, (h,), self._n_in, values, [g for g in (egrad, lgrad) if g is not None],
                              oshape, empty, f64, _ptr(egrad), _ptr(lgrad))
 
+    # ---- gradients on gridpp's cube layout ----
+    def _cube(self, name, values, f64):
+        """the (Y, X, E) values of a cube method -> (values, output shape)"""
+        values = _m.field(values, f64=f64)
+        shp = _shape(values)
+        if len(shp) != 3:
+            raise RuntimeError("%s: values must be 3-D (Y, X, E)" % name)
+        if shp[:2] != self._ishape:
+            raise ValueError("Grid size is not the same as values")
+        return values, self._oshape + (shp[2],)
+
+    def simple_gradient_cube(self, values, elev_gradient):
+        """An ensemble in gridpp's cube layout, (Y, X, E) -> (oY, oX, E) or (N, E): plane [..., e] is simple_gradient(igrid, output,
+        values[..., e], elev_gradient, downscaler), bit for bit.  elev_gradient is a scalar."""
+        h = self._handle()
+        f64 = _wants_f64(values)
+        values, oshape = self._cube("simple_gradient_cube", values, f64)
+        if int(np.prod(oshape)) == 0:
+            return _empty_like_field(oshape, values)
+        return _m.run(lib().gpp_downscale_plan_simple_gradient_cube, h, _ptr(values), oshape[-1], float(elev_gradient), out_shape=oshape,
+                      like=values, mem=_m.flags(f64, values))
+
+    def full_gradient_cube(self, values, elev_gradient, laf_gradient):
+        """An ensemble in gridpp's cube layout, (Y, X, E) -> (oY, oX, E) or (N, E): plane [..., e] is full_gradient(igrid, output,
+        values[..., e], elev_gradient_e, laf_gradient_e, downscaler), bit for bit.  Each gradient is (Y, X), one field shared by the
+        members, or (Y, X, E), a field per member, or empty ([] or None): the term is absent.  The two may take different forms."""
+        h = self._handle()
+        f64 = _wants_f64(values, elev_gradient, laf_gradient)
+        values, oshape = self._cube("full_gradient_cube", values, f64)
+        vshape = _shape(values)
+        grads = []
+        # the laf gradient first, as gradient.cpp:13-20
+        for g, what in ((laf_gradient, "Laf gradient is the wrong size"), (elev_gradient, "Elevation gradient is the wrong size")):
+            g = _m.field(g, f64=f64)
+            if g is None or (g.numel() if _is_dev(g) else g.size) == 0:
+                grads.append((None, 1))
+            elif _shape(g) == vshape[:2]:
+                grads.append((g, 1))
+            elif _shape(g) == vshape:
+                grads.append((g, vshape[2]))
+            else:
+                raise ValueError(what)
+        (lgrad, lmembers), (egrad, emembers) = grads
+        present = [g for g in (egrad, lgrad) if g is not None]
+        _mem(values, *present)
+        if int(np.prod(oshape)) == 0:
+            return _empty_like_field(oshape, values)
+        return _m.run(lib().gpp_downscale_plan_full_gradient_cube, h, _ptr(values), vshape[2], _ptr(egrad), emembers, _ptr(lgrad), lmembers,
+                      out_shape=oshape, like=values, mem=_m.flags(f64, values, *present))
+
+    # ---- the ensemble downscalers with the plan's nearest grid points: no search (DESIGN.md 4.20) ----
+    def _ens(self, name, cubes, threshold, comparison_operator):
+        h = self._handle()
+        if not self._out_grid:
+            raise TypeError("%s: the plan's output must be a Grid" % name)
+        return (h,) + _ens_checks(name, self._ishape, self._n_in, self._oshape, self._itype == self._otype, cubes, threshold,
+                                  comparison_operator)
+
+    def _ens_run(self, entry, h, cubes, ne, threshold, f64, *args):
+        if int(np.prod(self._oshape)) == 0:
+            return _empty_like_field(self._oshape, threshold)
+        return _m.run(entry, h, *[_ptr(c) for c in cubes], int(ne), _ptr(threshold), *args, out_shape=self._oshape, like=threshold,
+                      mem=_m.flags(f64, threshold, *cubes))
+
+    def downscale_probability(self, ivalues, threshold, comparison_operator):
+        """downscale_probability(igrid, ogrid, ivalues, threshold, comparison_operator), bit for bit, for a plan built to a Grid."""
+        h, cubes, threshold, ne, f64 = self._ens("downscale_probability", [ivalues], threshold, comparison_operator)
+        return self._ens_run(lib().gpp_downscale_plan_probability, h, cubes, ne, threshold, f64, int(comparison_operator))
+
+    def _mask_threshold(self, name, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator, statistic, quantile):
+        h, cubes, threshold, ne, f64 = self._ens(name, [ivalues_true, ivalues_false, threshold_values], threshold, comparison_operator)
+        _mask_statistic_checks(statistic, quantile)
+        return self._ens_run(lib().gpp_downscale_plan_mask_threshold, h, cubes, ne, threshold, f64, int(comparison_operator), int(statistic),
+                             float(quantile))
+
+    def mask_threshold_downscale_consensus(self, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator, statistic):
+        """mask_threshold_downscale_consensus(igrid, ogrid, ...), bit for bit (RandomChoice: one of the cell's valid masked members)."""
+        return self._mask_threshold("mask_threshold_downscale_consensus", ivalues_true, ivalues_false, threshold_values, threshold,
+                                    comparison_operator, statistic, 0.0)
+
+    def mask_threshold_downscale_quantile(self, ivalues_true, ivalues_false, threshold_values, threshold, comparison_operator, quantile):
+        """mask_threshold_downscale_quantile(igrid, ogrid, ...), bit for bit."""
+        return self._mask_threshold("mask_threshold_downscale_quantile", ivalues_true, ivalues_false, threshold_values, threshold,
+                                    comparison_operator, Quantile, quantile)
+
     def _info(self):
         locations, cells, nbytes, distorted = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
         downscaler = C.c_int()
@@ -1390,6 +1476,12 @@ def _ens_setup(name, igrid, ogrid, cubes, threshold, comparison_operator):
     (cubes, threshold, ne, f64).  Cubes are (Y, X, E), the threshold (oY, oX)."""
     if not isinstance(igrid, Grid) or not isinstance(ogrid, Grid):
         raise TypeError("%s: igrid and ogrid must be Grids" % name)
+    return _ens_checks(name, tuple(igrid.size()), igrid._n, tuple(ogrid.size()), igrid.get_coordinate_type() == ogrid.get_coordinate_type(),
+                       cubes, threshold, comparison_operator)
+
+
+def _ens_checks(name, ishape, n_in, oshape, same_types, cubes, threshold, comparison_operator):
+    """_ens_setup once the two grids are known by their shapes (n_in: the cells of the input grid) and coordinate types"""
     f64 = _wants_f64(*cubes)
     cubes = [_m.field(a, 3, "values", f64) for a in cubes]
     threshold = _m.field(threshold, 2, "threshold", f64)
@@ -1397,15 +1489,22 @@ def _ens_setup(name, igrid, ogrid, cubes, threshold, comparison_operator):
     shp = _shape(cubes[0])
     if any(_shape(c) != shp for c in cubes[1:]):
         raise ValueError("%s: ivalues_true, ivalues_false and threshold_values must have the same shape" % name)
-    if igrid._n and shp[:2] != tuple(igrid.size()):
+    if n_in and shp[:2] != ishape:
         raise ValueError("Grid size is not the same as values")
-    if _shape(threshold) != tuple(ogrid.size()):
+    if _shape(threshold) != oshape:
         raise ValueError("Grid size is not the same as threshold")
-    if igrid.get_coordinate_type() != ogrid.get_coordinate_type():
+    if not same_types:
         raise ValueError("Coordinate types must be the same")
     if comparison_operator not in (Lt, Leq, Gt, Geq):
         raise ValueError("Invalid comparison operator")
     return cubes, threshold, shp[2], f64
+
+
+def _mask_statistic_checks(statistic, quantile):
+    if statistic not in (Mean, Min, Median, Max, Quantile, Std, Variance, Sum, Count, RandomChoice):   # src/api/util.cpp:106-108
+        raise RuntimeError("Internal error. Cannot compute statistic")
+    if statistic == Quantile and (quantile < 0 or quantile > 1):   # util.cpp:112-113
+        raise ValueError("calc_quantile: Quantile must be between 0 and 1 inclusive")
 
 
 def _ens_call(entry, igrid, ogrid, cubes, ne, threshold, f64, *args):
@@ -1426,10 +1525,7 @@ def _mask_threshold_downscale(name, igrid, ogrid, ivalues_true, ivalues_false, t
                               statistic, quantile):
     cubes, threshold, ne, f64 = _ens_setup(name, igrid, ogrid, [ivalues_true, ivalues_false, threshold_values], threshold,
                                            comparison_operator)
-    if statistic not in (Mean, Min, Median, Max, Quantile, Std, Variance, Sum, Count, RandomChoice):   # src/api/util.cpp:106-108
-        raise RuntimeError("Internal error. Cannot compute statistic")
-    if statistic == Quantile and (quantile < 0 or quantile > 1):   # util.cpp:112-113
-        raise ValueError("calc_quantile: Quantile must be between 0 and 1 inclusive")
+    _mask_statistic_checks(statistic, quantile)
     return _ens_call(lib().gpp_mask_threshold_downscale, igrid, ogrid, cubes, ne, threshold, f64, int(comparison_operator), int(statistic),
                      float(quantile))
 

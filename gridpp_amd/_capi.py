@@ -164,6 +164,10 @@ SIGNATURES = {
     "gpp_downscale_plan_apply_cube": [vp, vp, C.c_int, vp, C.c_int],
     "gpp_downscale_plan_simple_gradient": [vp, vp, C.c_int, C.c_float, vp, C.c_int],
     "gpp_downscale_plan_full_gradient": [vp, vp, C.c_int, vp, vp, vp, C.c_int],
+    "gpp_downscale_plan_simple_gradient_cube": [vp, vp, C.c_int, C.c_float, vp, C.c_int],
+    "gpp_downscale_plan_full_gradient_cube": [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_downscale_plan_probability": [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_downscale_plan_mask_threshold": [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int],
     "gpp_downscale_plan_info": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     "gpp_downscale_plan_destroy": [vp],
 }

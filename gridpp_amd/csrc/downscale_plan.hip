@@ -15,6 +15,7 @@
 // of the downscaled fields has four valid corners there (bilinear.cpp:309-313), never at construction.
 #include "common.h"
 #include "bilinear_geom.h"
+#include "ensemble_downscale.h"
 #include <climits>
 #include <memory>
 
@@ -187,6 +188,117 @@ __global__ __launch_bounds__(256) void k_plan_gradient(const GradientArgs a) {
     }
 }
 
+struct GradientCubeArgs {
+    const int4* rec; const int* nn; int nq, nX, E;
+    const float* values;                                 // [n_in][E]
+    const float* egrad; const float* lgrad;              // NULL = term absent; [n_in] shared by the members, or [n_in][E]
+    int e_members, l_members;                            // != 0: that gradient is [n_in][E]
+    const float* ielev; const float* ilaf;               // input grid [n_in]
+    const float* oelev; const float* olaf;               // output locations [nq]
+    float elev_gradient;                                 // simple_gradient's scalar
+    int full;                                            // 0: simple_gradient, 1: full_gradient
+    float* out;                                          // [nq][E]
+    int* err;
+};
+
+// d(f) of V members e ... e + V - 1 of a cube [n_in][E] at a location: k_plan_apply_cube's loads
+template <bool BIL, int V>
+__device__ __forceinline__ void down_members(const Loc& l, const float* __restrict__ f, const int E, const int e, const int nX, bool& flagged,
+                                             int* __restrict__ err, float (&r)[V]) {
+    using vec = typename VecOf<V>::type;
+    union { vec v; float f[V]; } a0, a1, a2, a3;
+    if(BIL && l.inside) {
+        const float* __restrict__ c = f + (size_t)l.c * E + e;
+        a0.v = *reinterpret_cast<const vec*>(c); a1.v = *reinterpret_cast<const vec*>(c + (size_t)nX * E);
+        a2.v = *reinterpret_cast<const vec*>(c + E); a3.v = *reinterpret_cast<const vec*>(c + (size_t)(nX + 1) * E);
+#pragma unroll
+        for(int u = 0; u < V; ++u) r[u] = in_box(l, a0.f[u], a1.f[u], a2.f[u], a3.f[u], nX, flagged, err);
+    }
+    else if(l.n0 >= 0) {   // outside the domain: nearest neighbour
+        a0.v = *reinterpret_cast<const vec*>(f + (size_t)l.n0 * E + e);
+#pragma unroll
+        for(int u = 0; u < V; ++u) r[u] = a0.f[u];
+    }
+    else {
+#pragma unroll
+        for(int u = 0; u < V; ++u) r[u] = NAN;
+    }
+}
+
+// k_plan_gradient on cubes: values [n_in][E] -> out [nq][E] with the lanes of k_plan_apply_cube.  Everything that does not depend on
+// the member -- the record, oelev - d(ielev), olaf - d(ilaf), the two `use` flags and the term of a gradient shared by the members --
+// is computed before the member loop (every lane of a group reads the same few addresses); with shared gradients the loop is
+// k_plan_apply_cube's plus one add.  PM: a gradient has a field per member and adds its four corner runs to the loop.
+template <bool BIL, int G, int V, bool PM>
+__global__ __launch_bounds__(256) void k_plan_gradient_cube(const GradientCubeArgs a) {
+    using vec = typename VecOf<V>::type;
+    const size_t g = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+    if(g >= (size_t)a.nq) return;
+    const int q = (int)g, lane = threadIdx.x % G, E = a.E;
+    const Loc l = load_loc<BIL>(a.rec, a.nn, q);
+    bool flagged = false;
+    auto d = [&](const float* __restrict__ f) -> float { return down<BIL>(l, f, a.nX, flagged, a.err); };
+    const bool e_pm = PM && a.e_members, l_pm = PM && a.l_members;
+    float ediff = 0, ldiff = 0, elev_corr = 0, laf_corr = 0, corr;
+    bool euse = false, luse = false;
+    if(!a.full) corr = (a.oelev[q] - d(a.ielev)) * a.elev_gradient;   // simple_gradient.cpp: no validity test
+    else {   // gradient.cpp:56-81, as k_plan_gradient: a switched-off gradient is still downscaled where it could be the one to raise
+        if(a.lgrad) {
+            const float ol = a.olaf[q], il = d(a.ilaf);
+            luse = dev_valid(ol) && dev_valid(il);
+            ldiff = ol - il;
+            if(!l_pm) {
+                if(luse) laf_corr = d(a.lgrad) * ldiff;
+                else if(BIL && l.bad && !flagged) (void)d(a.lgrad);
+            }
+        }
+        if(a.egrad) {
+            const float oe = a.oelev[q], ie = d(a.ielev);
+            euse = dev_valid(oe) && dev_valid(ie);
+            ediff = oe - ie;
+            if(!e_pm) {
+                if(euse) elev_corr = d(a.egrad) * ediff;
+                else if(BIL && l.bad && !flagged) (void)d(a.egrad);
+            }
+        }
+        corr = laf_corr + elev_corr;
+    }
+    float* __restrict__ o = a.out + (size_t)q * E;
+    for(int e = lane * V; e < E; e += G * V) {
+        union { vec v; float f[V]; } r;
+        float v[V];
+        down_members<BIL, V>(l, a.values, E, e, a.nX, flagged, a.err, v);
+        if(PM) {
+            float lc[V], ec[V], t[V];
+#pragma unroll
+            for(int u = 0; u < V; ++u) { lc[u] = laf_corr; ec[u] = elev_corr; }
+            if(l_pm && (luse || (BIL && l.bad && !flagged))) {
+                down_members<BIL, V>(l, a.lgrad, E, e, a.nX, flagged, a.err, t);
+#pragma unroll
+                for(int u = 0; u < V; ++u) if(luse) lc[u] = t[u] * ldiff;
+            }
+            if(e_pm && (euse || (BIL && l.bad && !flagged))) {
+                down_members<BIL, V>(l, a.egrad, E, e, a.nX, flagged, a.err, t);
+#pragma unroll
+                for(int u = 0; u < V; ++u) if(euse) ec[u] = t[u] * ediff;
+            }
+#pragma unroll
+            for(int u = 0; u < V; ++u) r.f[u] = v[u] + (lc[u] + ec[u]);
+        }
+        else {
+#pragma unroll
+            for(int u = 0; u < V; ++u) r.f[u] = v[u] + corr;
+        }
+        *reinterpret_cast<vec*>(o + e) = r.v;
+    }
+}
+
+// .x of the Bilinear records -> a plain index, for the ensemble downscalers
+__global__ __launch_bounds__(256) void k_plan_nearest_of_records(const int4* __restrict__ rec, const int nq, int* __restrict__ nn) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if(q < nq) nn[q] = rec[q].x;
+}
+
 __global__ void k_plan_fill_nan(float* out, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(i < n) out[i] = NAN;
@@ -201,10 +313,13 @@ int group_of(int E) {   // as ensemble_downscale.hip: the smallest of 4 ... 64 w
 
 struct gpp_downscale_plan {
     int downscaler = 0, nY = 0, nX = 0, nq = 0;
+    int itype = 0, otype = 0;                // the coordinate types of the two sets (the ensemble downscalers need them equal)
+    bool out_grid = false;                   // the output is a Grid (or holds nothing)
     size_t n_in = 0;
     long long distorted = 0;
     DevBuf<int4> rec;                        // Bilinear
-    DevBuf<int> nn;                          // Nearest
+    DevBuf<int> nn;                          // Nearest; for Bilinear .x of the records, extracted by the first ensemble downscaler
+    bool nn_ready = false;
     DevBuf<float> ielev, ilaf, oelev, olaf;  // copies of the two sets' elevations and land area fractions (the gradient methods)
     DevBuf<int> err;
     long long bytes() const {
@@ -289,6 +404,7 @@ extern "C" int gpp_downscale_plan_create(gpp_points* igrid, gpp_points* to, int 
     ensure_device();
     std::unique_ptr<gpp_downscale_plan> p(new gpp_downscale_plan);
     p->downscaler = downscaler; p->nY = igrid->ny; p->nX = igrid->nx; p->nq = to->n; p->n_in = (size_t)igrid->n;
+    p->itype = igrid->type; p->otype = to->type; p->out_grid = to->nx > 0 || to->n == 0;
     const int nq = to->n;
     if(nq > 0 && igrid->n > 0) {
         igrid->to_device();
@@ -298,6 +414,7 @@ extern "C" int gpp_downscale_plan_create(gpp_points* igrid, gpp_points* to, int 
         if(downscaler == 0) {
             p->nn.get(nq);
             gpp_nearest_device(igrid, to->d_x.p, to->d_y.p, to->d_z.p, nq, 1, p->nn.p);
+            p->nn_ready = true;
         }
         else {
             to->latlon_to_device();
@@ -416,6 +533,117 @@ extern "C" int gpp_downscale_plan_full_gradient(gpp_downscale_plan* plan, const 
                                                 const float* laf_gradient, float* out, int mem) {
     GPP_TRY
     plan_gradient(plan, values, nt, elev_gradient, laf_gradient, 0, 1, out, mem);
+    return GPP_OK;
+    GPP_CATCH
+}
+
+namespace {
+
+// the two cube-layout gradient entries: egrad / lgrad NULL = term absent, e_members / l_members 1 (a field shared by the members) or ne
+void plan_gradient_cube(gpp_downscale_plan* p, const float* values, int ne, const float* egrad, int e_members, const float* lgrad, int l_members,
+                        float elev_gradient, int full, float* out, int mem) {
+    if(!p) invalid("plan handle is NULL");
+    if(ne < 0) invalid("negative number of members");
+    if(p->nq == 0 || ne == 0) return;
+    if((egrad && e_members != 1 && e_members != ne) || (lgrad && l_members != 1 && l_members != ne))
+        invalid("a gradient must have 1 or ne members");
+    ensure_device();
+    mem &= ~GPP_ASYNC;
+    PlanCall call(p, values, out, (size_t)ne * p->nq, mem);
+    if(call.done) return;
+    const bool e_pm = egrad && e_members == ne && ne > 1, l_pm = lgrad && l_members == ne && ne > 1;
+    InField v, eg, lg;
+    v.bind(values, (size_t)ne * p->n_in, mem);
+    eg.bind(egrad, (e_pm ? (size_t)ne : 1) * p->n_in, mem);
+    lg.bind(lgrad, (l_pm ? (size_t)ne : 1) * p->n_in, mem);
+    GradientCubeArgs a;
+    a.rec = p->rec.p; a.nn = p->nn.p; a.nq = p->nq; a.nX = p->nX; a.E = ne;
+    a.values = v.d; a.egrad = eg.d; a.lgrad = lg.d;
+    a.e_members = e_pm; a.l_members = l_pm;
+    a.ielev = p->ielev.p; a.ilaf = p->ilaf.p; a.oelev = p->oelev.p; a.olaf = p->olaf.p;
+    a.elev_gradient = elev_gradient;
+    a.full = full;
+    a.out = call.o.d; a.err = p->err.p;
+    const bool bil = p->downscaler == 1, pm = e_pm || l_pm;
+    // 8-byte accesses under k_plan_apply_cube's condition (Bilinear, E even), for every array that is read or written in runs of members
+    uintptr_t bound = (uintptr_t)v.d | (uintptr_t)call.o.d;
+    if(e_pm) bound |= (uintptr_t)eg.d;
+    if(l_pm) bound |= (uintptr_t)lg.d;
+    const bool wide = bil && ne % 2 == 0 && bound % 8 == 0;
+    const int G = group_of(wide ? ne / 2 : ne);
+    const size_t blocks = ((size_t)p->nq + 256 / G - 1) / (256 / G);
+    if(blocks > (size_t)INT_MAX) invalid("too many output locations for this many members");
+    const dim3 grid((unsigned)blocks), block(256);
+#define GPP_GCUBE2(G_, PM_)                                                                                          \
+    if(wide) hipLaunchKernelGGL((k_plan_gradient_cube<true, G_, 2, PM_>), grid, block, 0, stream(), a);             \
+    else if(bil) hipLaunchKernelGGL((k_plan_gradient_cube<true, G_, 1, PM_>), grid, block, 0, stream(), a);         \
+    else hipLaunchKernelGGL((k_plan_gradient_cube<false, G_, 1, PM_>), grid, block, 0, stream(), a)
+#define GPP_GCUBE(G_)                                                                                                \
+    if(pm) { GPP_GCUBE2(G_, true); }                                                                                 \
+    else { GPP_GCUBE2(G_, false); }
+    switch(G) {
+        case 4: GPP_GCUBE(4); break;
+        case 8: GPP_GCUBE(8); break;
+        case 16: GPP_GCUBE(16); break;
+        case 32: GPP_GCUBE(32); break;
+        default: GPP_GCUBE(64); break;
+    }
+#undef GPP_GCUBE
+#undef GPP_GCUBE2
+    call.finish();
+}
+
+// what the planned ensemble downscalers check before the shared part of ensemble_downscale.hip; -> the index of the nearest grid points
+void check_ensemble_plan(gpp_downscale_plan* p) {
+    if(!p) invalid("plan handle is NULL");
+    if(!p->out_grid) invalid("the plan's output must be a Grid");
+    if(p->itype != p->otype) invalid("Coordinate types must be the same");
+}
+const int* plan_nearest_index(gpp_downscale_plan* p) {
+    if(!p->nn_ready) {   // a Bilinear plan: .x of its records, extracted once and kept (4 bytes per location, counted in bytes())
+        p->nn.get(p->nq);
+        hipLaunchKernelGGL(k_plan_nearest_of_records, dim3((p->nq + 255) / 256), dim3(256), 0, stream(), (const int4*)p->rec.p, p->nq, p->nn.p);
+        GPP_HIP(hipGetLastError());
+        p->nn_ready = true;
+    }
+    return p->nn.p;
+}
+
+}   // namespace
+
+extern "C" int gpp_downscale_plan_simple_gradient_cube(gpp_downscale_plan* plan, const float* values, int ne, float elev_gradient, float* out,
+                                                       int mem) {
+    GPP_TRY
+    plan_gradient_cube(plan, values, ne, nullptr, 1, nullptr, 1, elev_gradient, 0, out, mem);
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_full_gradient_cube(gpp_downscale_plan* plan, const float* values, int ne, const float* elev_gradient,
+                                                     int elev_members, const float* laf_gradient, int laf_members, float* out, int mem) {
+    GPP_TRY
+    plan_gradient_cube(plan, values, ne, elev_gradient, elev_members, laf_gradient, laf_members, 0, 1, out, mem);
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_probability(gpp_downscale_plan* plan, const float* values, int ne, const float* threshold,
+                                              int comparison_operator, float* out, int mem) {
+    GPP_TRY
+    check_ensemble_plan(plan);
+    ensemble_probability([&] { return plan_nearest_index(plan); }, plan->n_in, plan->nq, values, ne, threshold, comparison_operator, out,
+                         mem & ~GPP_ASYNC);
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_downscale_plan_mask_threshold(gpp_downscale_plan* plan, const float* ivalues_true, const float* ivalues_false,
+                                                 const float* threshold_values, int ne, const float* threshold, int comparison_operator,
+                                                 int statistic, float quantile, float* out, int mem) {
+    GPP_TRY
+    check_ensemble_plan(plan);
+    ensemble_mask_threshold([&] { return plan_nearest_index(plan); }, plan->n_in, plan->nq, ivalues_true, ivalues_false, threshold_values, ne,
+                            threshold, comparison_operator, statistic, quantile, out, mem & ~GPP_ASYNC);
     return GPP_OK;
     GPP_CATCH
 }

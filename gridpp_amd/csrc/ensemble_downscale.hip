@@ -20,6 +20,7 @@
 //                       several slabs, a ragged last one included, on a grid of a hundred cells.
 #include "common.h"
 #include "row_stats.h"
+#include "ensemble_downscale.h"
 #include <algorithm>
 
 using namespace gpp;
@@ -188,11 +189,13 @@ void check_operator(int op) {
     if(op != GPP_LT && op != GPP_LEQ && op != GPP_GT && op != GPP_GEQ) invalid("Invalid comparison operator");
 }
 
-// checks shared by the two entry points; returns false when there is nothing to compute
-void check_grids(gpp_points* igrid, gpp_points* ogrid, int ne, int op) {
+// checks of the two direct entry points (those of the ensemble itself follow in ensemble_probability / ensemble_mask_threshold)
+void check_grids(gpp_points* igrid, gpp_points* ogrid) {
     if(!igrid || !ogrid) invalid("grid is NULL");
     if(igrid->n > 0 && igrid->nx <= 0) invalid("the input must be a Grid");
     if(igrid->type != ogrid->type) invalid("Coordinate types must be the same");   // as gpp_nearest_levels
+}
+void check_ensemble(int ne, int op) {
     if(ne < 0) invalid("negative number of ensemble members");
     check_operator(op);
 }
@@ -222,27 +225,24 @@ unsigned g_seed = 0x9e3779b9u;   // RandomChoice: a different draw every call (u
 
 }   // namespace
 
-extern "C" int gpp_downscale_probability(gpp_points* igrid, gpp_points* ogrid, const float* values, int ne, const float* threshold,
-                                         int comparison_operator, float* out, int mem) {
-    GPP_TRY
-    check_grids(igrid, ogrid, ne, comparison_operator);
-    const int nq = ogrid->n;
-    if(nq == 0) return GPP_OK;
+void gpp::ensemble_probability(const NearestIndex& index, size_t n_in, int nq, const float* values, int ne, const float* threshold,
+                               int comparison_operator, float* out, int mem) {
+    check_ensemble(ne, comparison_operator);
+    if(nq == 0) return;
     if(!out) invalid("out is NULL");
     ensure_device();
     OutField o;
     o.bind(out, nq, mem);
-    if(igrid->n == 0 || ne == 0) {   // no nearest cell (as gpp_nearest_levels) / count == 0 (:53-55)
+    if(n_in == 0 || ne == 0) {   // no nearest cell (as gpp_nearest_levels) / count == 0 (:53-55)
         fill(o, nq, NAN);
-        return GPP_OK;
+        return;
     }
     if(!values || !threshold) invalid("values / threshold is NULL");
     InField v, th;
-    v.bind(values, (size_t)igrid->n * ne, mem);
+    v.bind(values, n_in * ne, mem);
     th.bind(threshold, nq, mem);
-    DevBuf<int> idx;
-    nearest_index(igrid, ogrid, idx);
-#define GPP_PROB(G) hipLaunchKernelGGL(k_ens_probability<G>, dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx.p, v.d, ne, th.d, nq, comparison_operator, o.d)
+    const int* idx = index();
+#define GPP_PROB(G) hipLaunchKernelGGL(k_ens_probability<G>, dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, v.d, ne, th.d, nq, comparison_operator, o.d)
     switch(group_of(ne)) {
         case 4: GPP_PROB(4); break;
         case 8: GPP_PROB(8); break;
@@ -254,15 +254,12 @@ extern "C" int gpp_downscale_probability(gpp_points* igrid, gpp_points* ogrid, c
     GPP_HIP(hipGetLastError());
     o.finish();
     GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
-    GPP_CATCH
 }
 
-extern "C" int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid, const float* ivalues_true, const float* ivalues_false,
-                                            const float* threshold_values, int ne, const float* threshold, int comparison_operator,
-                                            int statistic, float quantile, float* out, int mem) {
-    GPP_TRY
-    check_grids(igrid, ogrid, ne, comparison_operator);
+void gpp::ensemble_mask_threshold(const NearestIndex& index, size_t n_in, int nq, const float* ivalues_true, const float* ivalues_false,
+                                  const float* threshold_values, int ne, const float* threshold, int comparison_operator, int statistic,
+                                  float quantile, float* out, int mem) {
+    check_ensemble(ne, comparison_operator);
     switch(statistic) {   // util.cpp:19-110
         case GPP_MEAN: case GPP_MIN: case GPP_MEDIAN: case GPP_MAX: case GPP_QUANTILE: case GPP_STD: case GPP_VARIANCE:
         case GPP_SUM: case GPP_COUNT: case GPP_RANDOMCHOICE: break;
@@ -270,28 +267,26 @@ extern "C" int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid
     }
     if(statistic == GPP_QUANTILE && (quantile < 0 || quantile > 1))   // util.cpp:112-113 (a NaN passes and gives NaN)
         invalid("calc_quantile: Quantile must be between 0 and 1 inclusive");
-    const int nq = ogrid->n;
-    if(nq == 0) return GPP_OK;
+    if(nq == 0) return;
     if(!out) invalid("out is NULL");
     ensure_device();
     OutField o;
     o.bind(out, nq, mem);
-    if(igrid->n == 0 || ne == 0) {   // no nearest cell: all missing; no member: calc_statistic of nothing (Count -> 0)
-        fill(o, nq, (igrid->n > 0 && statistic == GPP_COUNT) ? 0.0f : NAN);
-        return GPP_OK;
+    if(n_in == 0 || ne == 0) {   // no nearest cell: all missing; no member: calc_statistic of nothing (Count -> 0)
+        fill(o, nq, (n_in > 0 && statistic == GPP_COUNT) ? 0.0f : NAN);
+        return;
     }
     if(!ivalues_true || !ivalues_false || !threshold_values || !threshold) invalid("a field is NULL");
-    const size_t nin = (size_t)igrid->n * ne;
+    const size_t nin = n_in * ne;
     InField vt, vf, tv, th;
     vt.bind(ivalues_true, nin, mem);
     vf.bind(ivalues_false, nin, mem);
     tv.bind(threshold_values, nin, mem);
     th.bind(threshold, nq, mem);
-    DevBuf<int> idx;
-    nearest_index(igrid, ogrid, idx);
+    const int* idx = index();
     const unsigned seed = (g_seed = g_seed * 1664525u + 1013904223u);
     if(ne <= GPP_ENSEMBLE_ROW_CAP) {
-#define GPP_MASK(G, CAP) hipLaunchKernelGGL((k_ens_mask<G, CAP>), dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx.p, vt.d, vf.d, tv.d, ne, \
+#define GPP_MASK(G, CAP) hipLaunchKernelGGL((k_ens_mask<G, CAP>), dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, vt.d, vf.d, tv.d, ne, \
                                             th.d, nq, comparison_operator, statistic, quantile, seed, o.d)
         switch(group_of(ne)) {
             case 4: GPP_MASK(4, 16); break;
@@ -309,7 +304,7 @@ extern "C" int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid
         scratch.get((size_t)slab * ne);
         for(int q0 = 0; q0 < nq; q0 += slab) {
             const int nc = std::min(slab, nq - q0);
-            hipLaunchKernelGGL(k_ens_mask_rows, dim3((nc + 3) / 4), dim3(256), 0, stream(), idx.p, vt.d, vf.d, tv.d, ne, th.d, q0, nc,
+            hipLaunchKernelGGL(k_ens_mask_rows, dim3((nc + 3) / 4), dim3(256), 0, stream(), idx, vt.d, vf.d, tv.d, ne, th.d, q0, nc,
                                comparison_operator, scratch.p);
             hipLaunchKernelGGL(k_ens_rows_result, dim3((nc + 255) / 256), dim3(256), 0, stream(), (const float*)scratch.p, ne, q0, nc, statistic,
                                quantile, seed, o.d);
@@ -318,6 +313,27 @@ extern "C" int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid
     }
     o.finish();
     GPP_HIP(hipStreamSynchronize(stream()));
+}
+
+extern "C" int gpp_downscale_probability(gpp_points* igrid, gpp_points* ogrid, const float* values, int ne, const float* threshold,
+                                         int comparison_operator, float* out, int mem) {
+    GPP_TRY
+    check_grids(igrid, ogrid);
+    DevBuf<int> idx;
+    ensemble_probability([&] { nearest_index(igrid, ogrid, idx); return (const int*)idx.p; }, (size_t)igrid->n, ogrid->n, values, ne, threshold,
+                         comparison_operator, out, mem);
+    return GPP_OK;
+    GPP_CATCH
+}
+
+extern "C" int gpp_mask_threshold_downscale(gpp_points* igrid, gpp_points* ogrid, const float* ivalues_true, const float* ivalues_false,
+                                            const float* threshold_values, int ne, const float* threshold, int comparison_operator,
+                                            int statistic, float quantile, float* out, int mem) {
+    GPP_TRY
+    check_grids(igrid, ogrid);
+    DevBuf<int> idx;
+    ensemble_mask_threshold([&] { nearest_index(igrid, ogrid, idx); return (const int*)idx.p; }, (size_t)igrid->n, ogrid->n, ivalues_true,
+                            ivalues_false, threshold_values, ne, threshold, comparison_operator, statistic, quantile, out, mem);
     return GPP_OK;
     GPP_CATCH
 }

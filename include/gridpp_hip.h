@@ -757,6 +757,22 @@ int gpp_downscale_plan_apply_cube(gpp_downscale_plan* plan, const float* values,
 int gpp_downscale_plan_simple_gradient(gpp_downscale_plan* plan, const float* values, int nt, float elev_gradient, float* out, int mem);
 int gpp_downscale_plan_full_gradient(gpp_downscale_plan* plan, const float* values, int nt, const float* elev_gradient,
                                      const float* laf_gradient, float* out, int mem);
+/* The gradient methods on gridpp's cube layout: values [Y * X][ne] -> out [locations][ne]; plane e is gpp_simple_gradient /
+ * gpp_full_gradient of plane e, bit for bit.  A gradient is NULL (term absent), one field [Y * X] shared by the members (`*_members` 1) or a
+ * cube [Y * X][ne] (`*_members` ne); any other count is GPP_EINVAL.  NULL handles, a negative ne, an empty input grid (all NaN), no
+ * location or no member (nothing to do) and GPP_ASYNC as gpp_downscale_plan_apply_cube. */
+int gpp_downscale_plan_simple_gradient_cube(gpp_downscale_plan* plan, const float* values, int ne, float elev_gradient, float* out, int mem);
+int gpp_downscale_plan_full_gradient_cube(gpp_downscale_plan* plan, const float* values, int ne, const float* elev_gradient, int elev_members,
+                                          const float* laf_gradient, int laf_members, float* out, int mem);
+/* gpp_downscale_probability / gpp_mask_threshold_downscale with the nearest input cells of a plan whose output is a Grid, bit for bit
+ * (RandomChoice draws anew every call) and without a search.  GPP_EINVAL before any device work: a NULL handle, a plan built for Points,
+ * "Coordinate types must be the same" (a Bilinear plan may span two), then the checks of the direct entries in their order.  A Bilinear
+ * plan extracts the nearest grid points of its records on the first such call and keeps them: 4 more bytes per location in `bytes`. */
+int gpp_downscale_plan_probability(gpp_downscale_plan* plan, const float* values, int ne, const float* threshold, int comparison_operator,
+                                   float* out, int mem);
+int gpp_downscale_plan_mask_threshold(gpp_downscale_plan* plan, const float* ivalues_true, const float* ivalues_false,
+                                      const float* threshold_values, int ne, const float* threshold, int comparison_operator, int statistic,
+                                      float quantile, float* out, int mem);
 /* any pointer may be NULL; cells: points of the input grid; bytes: the HBM the plan holds; distorted: locations whose weights leave [0, 1] */
 int gpp_downscale_plan_info(const gpp_downscale_plan* plan, long long* locations, long long* cells, int* downscaler, long long* bytes,
                             long long* distorted);
