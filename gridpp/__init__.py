@@ -45,10 +45,12 @@ else:
     # rows, ensemble copula coupling and the CRPS): gridpp_amd.calc_ranks, gridpp_amd.sort_rows, gridpp_amd.reorder_by_ranks, gridpp_amd.calc_crps.
     # downscaling_plan and its DownscalingPlan have none either (the nearest grid point, box and weights of every output
     # location computed once per pair of geometries and applied to any number of fields): gridpp_amd.downscaling_plan.
+    # neighbourhood_members and calc_gradient_members have none either (a spatial filter and the gradient of every member of a
+    # (Y, X, E) cube without a permute): gridpp_amd.neighbourhood_members, gridpp_amd.calc_gradient_members.
     for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve",
                   "optimal_interpolation_gain", "OiGain", "calc_quantiles", "quantile_mapping_curves",
                   "neighbourhood_quantiles_fast", "neighbourhood_cdf", "calc_ranks", "sort_rows", "reorder_by_ranks", "calc_crps",
-                  "downscaling_plan", "DownscalingPlan"):
+                  "downscaling_plan", "DownscalingPlan", "neighbourhood_members", "calc_gradient_members"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

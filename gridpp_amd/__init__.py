@@ -1875,6 +1875,59 @@ def neighbourhood_cdf(input, thresholds, halfwidth):
                   mem=_m.flags(f64, arr, thr))
 
 
+def neighbourhood_members(input, halfwidth, statistic):
+    """A spatial filter of every member of a cube (no counterpart in the reference, whose neighbourhood(vec3) pools the
+    members into one field): (Y, X, E) -> (Y, X, E) float32, plane [..., e] = neighbourhood(input[..., e], halfwidth, statistic), without a
+    permute of the cube.  Mean, Sum, Count, Min, Max, Std and Variance at any halfwidth >= 0, windows wider than the field included; invalid
+    values (NaN, +-Inf) are left out and a window without a valid value gives NaN (Count: 0).
+
+    input: numpy (float64 is cast on the device) or a torch CUDA tensor (then the result is one).  Median and RandomChoice raise ValueError:
+    order statistics per member are not supported.  Quantile, a negative halfwidth: neighbourhood's errors.  A cube with a zero dimension
+    gives an empty cube of that shape."""
+    f64 = _wants_f64(input)
+    arr = _m.field(input, 3, "input", f64)
+    if halfwidth < 0:
+        raise ValueError("Half width must be > 0")
+    if statistic == Quantile:
+        raise ValueError("Use neighbourhood_quantile for computing neighbourhood quantiles")
+    for stat, name in ((Median, "Median"), (RandomChoice, "RandomChoice")):
+        if statistic == stat:
+            raise ValueError("neighbourhood_members does not compute the statistic %s: order statistics per member are not supported" % name)
+    if statistic not in (Mean, Sum, Count, Min, Max, Std, Variance):
+        raise ValueError("neighbourhood_members: unknown statistic")
+    ny, nx, ne = _shape(arr)
+    if ny * nx * ne == 0:
+        return _m._empty_like_field((ny, nx, ne), arr)
+    return _m.run(lib().gpp_neighbourhood_members, _ptr(arr), ny, nx, ne, int(halfwidth), int(statistic), out_shape=(ny, nx, ne), like=arr,
+                  mem=_m.flags(f64, arr))
+
+
+def calc_gradient_members(base, values, gradient_type, halfwidth, num_min=2, min_range=MV, default_gradient=0):
+    """calc_gradient of every member of a cube (no counterpart in the reference): values (Y, X, E) -> (Y, X, E) float32,
+    plane [..., e] = calc_gradient(base_e, values[..., e], ...), the layout plan.full_gradient_cube takes its gradients in.  base is (Y, X),
+    one field shared by the members (elevation), or (Y, X, E), a field per member.  MinMax and LinearRegression; the checks and their
+    messages are calc_gradient's.  numpy (float64 is cast on the device) or torch CUDA tensors (then the result is one)."""
+    f64 = _wants_f64(base, values)
+    base, values = _m.field(base, None, "base", f64), _m.field(values, 3, "values", f64)
+    if halfwidth <= 0:
+        raise ValueError("Halwidth cannot be <= 0; must be positive integer")
+    if is_valid(min_range) and min_range < 0:
+        raise ValueError("min_range must be >= 0")
+    if num_min < 0:
+        raise ValueError("num_min must be >= 0")
+    bshape = _shape(base)
+    if len(bshape) > 0 and bshape[0] == 0:
+        raise ValueError("base input has no size")
+    ny, nx, ne = _shape(values)
+    if bshape not in ((ny, nx), (ny, nx, ne)):
+        raise ValueError("base is not the same size as values")
+    if gradient_type not in (MinMax, LinearRegression):
+        raise ValueError("unknown gradient type")
+    return _m.run(lib().gpp_calc_gradient_members, _ptr(base), 1 if len(bshape) == 2 else ne, _ptr(values), ny, nx, ne, int(gradient_type),
+                  int(halfwidth), int(num_min), float(min_range), float(default_gradient), out_shape=(ny, nx, ne), like=values,
+                  mem=_m.flags(f64, base, values))
+
+
 def neighbourhood_ens(input, halfwidth, statistic):   # deprecated aliases (neighbourhood.cpp:541-552), with the reference's message
     future_deprecation_warning("neighbourhood_ens", "neighbourhood")
     return neighbourhood(input, halfwidth, statistic)

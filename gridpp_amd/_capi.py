@@ -132,6 +132,8 @@ SIGNATURES = {
     "gpp_neighbourhood_quantile_fast": [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int],
     "gpp_neighbourhood_quantiles_fast": [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int],
     "gpp_neighbourhood_cdf": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int],
+    "gpp_neighbourhood_members": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
+    "gpp_calc_gradient_members": [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int],
     "gpp_window": [vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int],
     "gpp_calc_score_table": [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp],
     "gpp_calc_score": [vp, vp, C.c_longlong, C.c_float, C.c_float, C.c_int, fp, C.c_int],

@@ -288,6 +288,15 @@ void reset_winners(DevBuf<int>& winner, size_t n) {
 
 }   // namespace
 
+// k_gradient_regression over any number of elements, for members.hip: the per-member LinearRegression gradient of a cube ends in the kernel of the 2-D call itself
+namespace gpp {
+void gradient_regression_launch(const float* mX, const float* mY, const float* mXX, const float* mXY, const float* cnt, size_t n, int num_min,
+                                float min_range, float default_gradient, float* out) {
+    hipLaunchKernelGGL(k_gradient_regression, dim3(blocks(n)), dim3(256), 0, stream(), mX, mY, mXX, mXY, cnt, n, num_min, min_range, default_gradient, out);
+    GPP_HIP(hipGetLastError());
+}
+}   // namespace gpp
+
 extern "C" int gpp_fill(gpp_points* igrid, const float* input, gpp_points* points, const float* radii, float value, int outside, float* out, int mem) {
     GPP_TRY
     if(!igrid || !points) invalid("grid / points is NULL");

@@ -1556,6 +1556,14 @@ struct QfCall : Fields {
 };
 }   // namespace
 
+// k_std_finish over any number of elements, for members.hip: the per-member Std / Variance of a cube ends in the kernel of the 2-D call itself
+namespace gpp {
+void std_finish_launch(const float* mean, const float* mean2, long n, int is_std, float* out) {
+    hipLaunchKernelGGL(k_std_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), mean, mean2, n, is_std, out);
+    GPP_HIP(hipGetLastError());
+}
+}   // namespace gpp
+
 extern "C" int gpp_neighbourhood(const float* input, int ny, int nx, int ne, int is3d, int halfwidth, int statistic, float* out, int mem) {
     GPP_TRY
     NbhCall c{{}, input, ny, nx, ne, is3d, halfwidth, statistic, out, mem};

@@ -473,6 +473,21 @@ int gpp_neighbourhood_quantiles_fast(const float* input, int ny, int nx, int ne,
  * field or nt == 0 returns GPP_OK and writes nothing; a NULL pointer is GPP_EINVAL.  Same passes, paths and overrides as above. */
 int gpp_neighbourhood_cdf(const float* input, int ny, int nx, int ne, int is3d, int halfwidth,
                           const float* thresholds, int nt, float* out, int mem);
+/* A spatial filter of every member, no counterpart in the reference (gridpp_amd.neighbourhood_members): input and out are
+ * [ny][nx][ne] with ne contiguous, plane e of out = gpp_neighbourhood of plane e of input as a 2-D field.  Mean, Sum, Count, Min, Max, Std and
+ * Variance at any halfwidth >= 0.  Checked in this order, before any device work: halfwidth < 0 is GPP_EINVAL ("Half width must be > 0");
+ * GPP_QUANTILE is GPP_EINVAL with gpp_neighbourhood's message; GPP_MEDIAN and GPP_RANDOMCHOICE are GPP_EINVAL (order statistics per member are
+ * not supported); an empty cube returns GPP_OK and writes nothing; a NULL pointer is GPP_EINVAL.  input / out follow `mem` (GPP_HOST_F64: input).
+ * Mean / Sum / Count (and Std / Variance through them) run in one kernel out of LDS where halfwidth * ne <= 1024 and in two passes over bands of rows
+ * otherwise (csrc/members.hip); the path overrides GPP_MEMBERS_TWO_PASS (the two-pass form everywhere), GPP_MEMBERS_BAND_ROWS (rows of a band) and
+ * GPP_MEMBERS_SEG_ROWS (rows a workgroup of the fused form marches down) choose between them; the result does not depend on the path. */
+int gpp_neighbourhood_members(const float* input, int ny, int nx, int ne, int halfwidth, int statistic, float* out, int mem);
+/* gpp_calc_gradient of every member (gridpp_amd.calc_gradient_members): values and out are [ny][nx][ne]; base is [ny][nx]
+ * (base_members == 1: one field shared by the members) or [ny][nx][ne] (base_members == ne).  Plane e of out = gpp_calc_gradient(base_e, plane e
+ * of values, ...).  The checks of gpp_calc_gradient in its order with its messages, then base_members outside {1, ne} ("base is not the same size
+ * as values"), all GPP_EINVAL before any device work.  base / values / out follow `mem` (GPP_HOST_F64: base and values). */
+int gpp_calc_gradient_members(const float* base, int base_members, const float* values, int ny, int nx, int ne, int gradient_type, int halfwidth,
+                              int num_min, float min_range, float default_gradient, float* out, int mem);
 
 /* ---- per-row statistics (src/api/util.cpp) -------------------------------------
  * array is [rows][len]; one result per row. */
