@@ -47,10 +47,13 @@ else:
     # location computed once per pair of geometries and applied to any number of fields): gridpp_amd.downscaling_plan.
     # neighbourhood_members and calc_gradient_members have none either (a spatial filter and the gradient of every member of a
     # (Y, X, E) cube without a permute): gridpp_amd.neighbourhood_members, gridpp_amd.calc_gradient_members.
+    # fractions_skill_score and its FssResult have none either (the Fractions Skill Score of a field or an ensemble cube for a
+    # table of thresholds x half widths from one pass over the inputs): gridpp_amd.fractions_skill_score.
     for _name in ("local_distribution_correction", "Gamma", "gamma_inv", "get_optimal_threshold", "metric_optimizer_curve",
                   "optimal_interpolation_gain", "OiGain", "calc_quantiles", "quantile_mapping_curves",
                   "neighbourhood_quantiles_fast", "neighbourhood_cdf", "calc_ranks", "sort_rows", "reorder_by_ranks", "calc_crps",
-                  "downscaling_plan", "DownscalingPlan", "neighbourhood_members", "calc_gradient_members"):
+                  "downscaling_plan", "DownscalingPlan", "neighbourhood_members", "calc_gradient_members",
+                  "fractions_skill_score", "FssResult"):
         globals().pop(_name, None)
     __version__ = getattr(_impl, "__version__", None)
     implementation = "gridpp_amd"

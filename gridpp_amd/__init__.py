@@ -12,6 +12,7 @@ arguments may be anything numpy can convert (host path: staged through HBM by th
 library) or torch CUDA tensors (device path: the kernels read/write the tensors'
 HBM directly and a torch tensor is returned).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -2270,6 +2271,69 @@ def neighbourhood_score(grid, points, fcst, ref, half_width, metric, threshold):
         raise ValueError("Grid size is not the same as forecast values")
     return _m.run(lib().gpp_neighbourhood_score, grid._h, points._h, _ptr(f), _ptr(r), int(half_width), metric, float(threshold),
                   out_shape=(ny, nx), like=f, mem=_m.flags(f64, f))
+
+
+# ---- the Fractions Skill Score (no counterpart in the reference) ----
+FssResult = collections.namedtuple("FssResult", ["fss", "fbs", "fbs_worst", "cells"])
+
+
+def _fss_value(fbs, fbs_worst):
+    """GPP_FSS_VALUE of include/gridpp_hip.h, elementwise: 1 - fbs / fbs_worst in float64, NaN where fbs_worst == 0"""
+    fbs, fbs_worst = np.asarray(fbs, np.float64), np.asarray(fbs_worst, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(fbs_worst == 0, np.nan, 1.0 - fbs / fbs_worst)
+
+
+def fractions_skill_score(fcst, ref, thresholds, halfwidths, comparison_operator=Gt):
+    """The Fractions Skill Score (Roberts & Lean 2008; for an ensemble the neighbourhood ensemble probability of Schwartz & Sobash 2017)
+    of `fcst` against `ref` for every threshold and every half width from one call (no counterpart in the reference):
+    FssResult(fss, fbs, fbs_worst, cells), host numpy whatever the inputs are -- fss, fbs and fbs_worst float64 of shape (T, H), cells
+    int64 of shape (H,).
+
+    fcst: (Y, X), or an ensemble cube (Y, X, E); ref: (Y, X); numpy arrays of any dtype, or both torch CUDA tensors.  thresholds: a 1-D
+    host sequence (+-Inf allowed, NaN is not); halfwidths: a 1-D host sequence of ints >= 0; comparison_operator: Lt, Leq, Gt or Geq
+    (Gt is what calc_score and neighbourhood_score use).
+
+    A cell counts where ref is valid (not NaN, not +-Inf) and fcst has a valid member; m = its valid members, k = those with
+    `member op threshold`, o = `ref op threshold`.  Over the window [y +- h] x [x +- h] clipped to the grid (the window of
+    neighbourhood) n, M, K, O are the exact sums of 1, m, k, o over the counting cells.  Every cell with n > 0 contributes, whether it
+    counts itself or not: Ff = K / M, Fo = O / n, fbs += (Ff - Fo)^2, fbs_worst += Ff^2 + Fo^2, in float64; cells[h] is their number.
+    fss = 1 - fbs / fbs_worst, NaN where fbs_worst == 0 (no event in either field).  Ff is the POOLED member fraction of the window: the
+    mean of the per-cell ensemble probabilities k / m wherever every counting cell has the same number of valid members; where they
+    differ, a cell weighs by the members it has.
+
+    To pool over cases (dates), add the sums, not the scores: 1 - sum(fbs) / sum(fbs_worst).
+
+    The result is bit-identical from call to call.  Errors, all before any device work and in this order: RuntimeError for a wrong number
+    of dimensions; ValueError where ref is not (Y, X) of fcst, thresholds or halfwidths are not 1-D, a threshold is NaN, a half width is
+    no integer or negative, the operator is none of the four, or one field is a device tensor and the other is not.  T == 0, H == 0 and an empty field
+    need no device (an empty field: zeros, NaN fss, cells == 0; without a threshold cells is 0 too)."""
+    f, ny, nx, ne, is3d, _ = _field23(fcst, "fcst")
+    r = _m.field(ref, 2, "ref")
+    if _shape(r) != (ny, nx) and not (ny * nx == 0 and int(np.prod(_shape(r))) == 0):
+        raise ValueError("fractions_skill_score: ref must have the shape (Y, X) of fcst")
+    thr, hws = np.asarray(thresholds), np.asarray(halfwidths)
+    if thr.ndim != 1:
+        raise ValueError("fractions_skill_score: thresholds must have 1 dimension")
+    if hws.ndim != 1:
+        raise ValueError("fractions_skill_score: halfwidths must have 1 dimension")
+    thr = np.ascontiguousarray(thr, np.float32)
+    if np.isnan(thr).any():
+        raise ValueError("fractions_skill_score: a threshold is NaN")
+    if hws.size and hws.dtype.kind not in "iub":
+        raise ValueError("fractions_skill_score: halfwidths must be integers")
+    if hws.size and hws.min() < 0:
+        raise ValueError("Half width must be > 0")
+    if comparison_operator not in (Lt, Leq, Gt, Geq):
+        raise ValueError("Invalid comparison operator")
+    mem = _m.flags(False, f, r)
+    hws = np.ascontiguousarray(np.minimum(hws, 2 ** 31 - 1), np.int32)   # (no window is wider than the field)
+    nt, nh = int(thr.size), int(hws.size)
+    fbs, worst, cells = np.zeros((nt, nh), np.float64), np.zeros((nt, nh), np.float64), np.zeros(nh, np.int64)
+    if nt and nh and ny * nx * ne:
+        check(lib().gpp_fractions_skill_score(_ptr(f), _ptr(r), ny, nx, ne, is3d, _ptr(thr), nt, _ptr(hws), nh, int(comparison_operator),
+                                              _ptr(fbs), _ptr(worst), _ptr(cells), mem))
+    return FssResult(_fss_value(fbs, worst), fbs, worst, cells)
 
 
 # ---- the optimal forecast threshold (src/api/metric_optimizer.cpp:105-184; DESIGN.md 4.13) ----

@@ -14,6 +14,7 @@ MEM_HOST, MEM_DEVICE, ASYNC, HOST_F64, Q_HOST = 0, 1, 2, 4, 8
 ENSEMBLE_ROW_CAP = 1024   # GPP_ENSEMBLE_ROW_CAP of include/gridpp_hip.h
 WINDOW_TILE_ROWS, WINDOW_TILE_COLS, WINDOW_FUSED_SPAN = 64, 32, 31   # GPP_WINDOW_* of include/gridpp_hip.h
 SCORE_TILE_COLS, SCORE_TILE_ROWS, SCORE_FUSED_MAXHW = 64, 32, 16   # GPP_SCORE_* of include/gridpp_hip.h
+FSS_TILE_COLS, FSS_TILE_ROWS, FSS_FUSED_MAXHW = 64, 32, 16   # GPP_FSS_* of include/gridpp_hip.h
 POINTWISE_BLOCK, POINTWISE_MAX_BLOCKS = 256, 2048   # GPP_POINTWISE_* of include/gridpp_hip.h
 GAMMA_BLOCK, GAMMA_MAX_BLOCKS = 256, 2048   # GPP_GAMMA_* of include/gridpp_hip.h
 MO_TILE_ITEMS, MO_GROUP = 2048, 4   # GPP_MO_* of include/gridpp_hip.h
@@ -138,6 +139,7 @@ SIGNATURES = {
     "gpp_calc_score_table": [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp],
     "gpp_calc_score": [vp, vp, C.c_longlong, C.c_float, C.c_float, C.c_int, fp, C.c_int],
     "gpp_neighbourhood_score": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int],
+    "gpp_fractions_skill_score": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int],
     "gpp_get_optimal_threshold": [vp, vp, C.c_longlong, C.c_float, C.c_int, fp, C.c_int],
     "gpp_metric_optimizer_curve": [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp, ip, C.c_int],
     "gpp_dewpoint": [vp, vp, C.c_longlong, vp, C.c_int],

@@ -580,6 +580,29 @@ int gpp_calc_score(const float* ref, const float* fcst, long long n, float thres
 #define GPP_SCORE_FUSED_MAXHW 16    /* the ring of the fused kernel holds 32 + 2 * 16 rows; (2 * 16 + 1)^2 = 1089 < 65536 */
 int gpp_neighbourhood_score(gpp_points* grid, gpp_points* points, const float* fcst, const float* ref, int half_width, int metric,
                             float threshold, float* out, int mem);
+/* The Fractions Skill Score for nt thresholds x nh half widths in one call, no counterpart in the reference (gridpp_amd.fractions_skill_score;
+ * DESIGN.md 4.22).  fcst is [ny][nx] (is3d == 0, ne must be 1) or a cube [ny][nx][ne] (is3d == 1), ref is [ny][nx]; both follow `mem`
+ * (GPP_HOST_F64 is not honoured).  thresholds[nt], halfwidths[nh] and the three outputs are HOST arrays whatever `mem` says: fbs and fbs_worst
+ * are [nt][nh] doubles, cells is [nh].  A cell counts where ref is valid and fcst has a valid member; with m its valid members, k those that
+ * meet `member op threshold` and o = `ref op threshold`, a cell whose window [y +- hw] x [x +- hw] (clipped to the grid) holds n > 0 counting
+ * cells adds (K / M - O / n)^2 to fbs[t][h] and (K / M)^2 + (O / n)^2 to fbs_worst[t][h], K, M, O the exact integer sums of k, m, o over the
+ * counting cells of the window and the arithmetic double; cells[h] = the number of such cells.  The score itself is GPP_FSS_VALUE of the two
+ * sums, and of their sums over many calls when cases are pooled.  GPP_EINVAL before any device work: a negative size, ne != 1 with is3d == 0,
+ * a NULL array that would be read or written, a NaN threshold (+-Inf are legal), "Half width must be > 0" for a negative one, "Invalid
+ * comparison operator" for a value that is not GPP_LT / GPP_LEQ / GPP_GT / GPP_GEQ.  nt == 0, nh == 0 and an empty field need no device: the
+ * outputs that exist are zero.  Half widths up to GPP_FSS_FUSED_MAXHW take one fused kernel per half width (row and column pass, the four
+ * sums packed in one 64-bit word with lanes of bk, bk, bn and bn bits: bn the smallest width that holds (2 hw + 1)^2, bk = (64 - 2 bn) / 2,
+ * taken while (2 hw + 1)^2 ne < 2^bk and ne <= 32767); wider ones, larger ensembles and every call under the path override
+ * GPP_FSS_GENERAL a separable pair with 64-bit window sums (GPP_FSS_GENERAL = wide: with 64-bit row sums too, as for (2 hw + 1) ne >= 2^32).
+ * The path override GPP_FSS_FILL = n sets the workgroups per threshold the fused launch aims for (1024), as GPP_SCORE_FILL does.  Partial sums
+ * are stored per workgroup and added in a fixed order: the results are bit-identical from call to call, on either path; between the paths
+ * they differ by the order of the additions only. */
+#define GPP_FSS_TILE_COLS 64      /* output columns of a strip of the fused kernel */
+#define GPP_FSS_TILE_ROWS 32      /* rows of a chunk of the strip */
+#define GPP_FSS_FUSED_MAXHW 16    /* the ring of the fused kernel holds 32 + 2 * 16 rows */
+#define GPP_FSS_VALUE(fbs, fbs_worst) ((fbs_worst) == 0.0 ? (double)NAN : 1.0 - (double)(fbs) / (double)(fbs_worst))   /* needs <math.h> */
+int gpp_fractions_skill_score(const float* fcst, const float* ref, int ny, int nx, int ne, int is3d, const float* thresholds, int nt,
+                              const int* halfwidths, int nh, int comparison_operator, double* fbs, double* fbs_worst, long long* cells, int mem);
 
 /* ---- the optimal forecast threshold (include/gridpp.h, src/api/metric_optimizer.cpp:105-184) ----------------------------------------
  * NOT the reference's result: the reference minimises with Boost's brent_find_minima, which ends on an arbitrary point of whichever
