@@ -3,11 +3,13 @@
 //
 // One thread per output location: the nearest grid point comes from the bin index (gpp_nearest_device), the four
 // quadrants around it are tested in the reference's order, the weights (s, t) are solved once per location (they do not
-// depend on the time level) and the T levels are gathered with unit-stride writes across locations.  All float
-// expressions keep the reference's association (the build has -ffp-contract=off and correctly rounded float divide);
-// the quadratic of the general quadrilateral is solved in double exactly as bilinear.cpp:159-267 does.
+// depend on the time level) and the T levels are gathered with unit-stride writes across locations: the direct locator and
+// the level loop of downscale_loc.h, which the downscalers and the plan share.  All float expressions keep the reference's
+// association (the build has -ffp-contract=off and correctly rounded float divide); the quadratic of the general
+// quadrilateral is solved in double exactly as bilinear.cpp:159-267 does.
 #include "common.h"
-#include "bilinear_geom.h"
+#include "downscale_loc.h"
+#include "downscale_call.h"
 
 using namespace gpp;
 
@@ -20,33 +22,8 @@ __global__ __launch_bounds__(256) void k_bilinear(const float* __restrict__ glat
                                                   float* __restrict__ out, int* __restrict__ err) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if(q >= nq) return;
-    const int n0 = nn[q];
-    const float lat = qlat[q], lon = qlon[q];
-    int I1, J1, I2, J2;
-    const bool inside = get_box(glat, glon, nY, nX, n0, lat, lon, I1, J1, I2, J2);
-    const size_t nG = (size_t)nY * nX;
-    const int i0 = I1 * nX + J1, i1 = I2 * nX + J1, i2 = I1 * nX + J2, i3 = I2 * nX + J2;
-    float s = 0, t = 0;
-    bool solved = false, bad = false;
-    for(int k = 0; k < nt; ++k) {
-        const float* v = values + (size_t)k * nG;
-        float res = NAN;
-        bool done = false;
-        if(inside) {
-            const float v0 = v[i0], v1 = v[i1], v2 = v[i2], v3 = v[i3];
-            if(dev_valid(v0) && dev_valid(v1) && dev_valid(v2) && dev_valid(v3)) {
-                done = true;
-                if(!solved) {
-                    bad = weights(lon, lat, glon[i0], glon[i1], glon[i2], glon[i3], glat[i0], glat[i1], glat[i2], glat[i3], s, t);
-                    solved = true;
-                    if(bad && atomicCAS(&err[0], 0, 1) == 0) { err[1] = __float_as_int(s); err[2] = __float_as_int(t); }
-                }
-                res = bilinear_value(v0, v1, v2, v3, s, t);
-            }
-        }
-        if(!done) res = v[n0];   // outside the domain or a missing corner: nearest neighbour (bilinear.cpp:346-356)
-        out[(size_t)k * nq + q] = res;
-    }
+    DirectLoc<true> l(glat, glon, nY, nX, nn, qlat, qlon, q, err);
+    down_levels(l, values, (size_t)nY * nX, nt, out, (size_t)nq, q);
 }
 
 __global__ void k_get_box(const float* __restrict__ glat, const float* __restrict__ glon, int nY, int nX, const int* __restrict__ nn,
@@ -56,11 +33,6 @@ __global__ void k_get_box(const float* __restrict__ glat, const float* __restric
     int I1, J1, I2, J2;
     const bool inside = get_box(glat, glon, nY, nX, nn[q], qlat[q], qlon[q], I1, J1, I2, J2);
     box[5 * q + 0] = inside; box[5 * q + 1] = I1; box[5 * q + 2] = J1; box[5 * q + 3] = I2; box[5 * q + 4] = J2;
-}
-
-__global__ void k_fill_nan(float* out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = NAN;
 }
 
 __global__ void k_in_rectangle(const float* p, int* out) {
@@ -96,35 +68,19 @@ extern "C" int gpp_bilinear(gpp_points* igrid, gpp_points* to, const float* valu
     if(nt < 0) invalid("negative number of time levels");
     const int nq = to->n;
     if(nq == 0 || nt == 0) return GPP_OK;
-    const size_t nout = (size_t)nt * nq;
-    OutField o;
-    o.bind(out, nout, mem);
-    if(igrid->n == 0) {   // bilinear.cpp:37-39
-        hipLaunchKernelGGL(k_fill_nan, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream(), o.d, nout);
-        GPP_HIP(hipGetLastError());
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
-    }
-    if(!values) invalid("values is NULL");
+    DownscaleCall call((size_t)igrid->n, values, out, (size_t)nt * nq, mem);   // bilinear.cpp:37-39
+    if(call.done) return GPP_OK;
     InField v;
     v.bind(values, (size_t)nt * igrid->n, mem);
     to->to_device();
     to->latlon_to_device();
     igrid->latlon_to_device();
-    DevBuf<int> idx, err;
+    DevBuf<int> idx;
     idx.get(nq);
-    err.get(4);
-    GPP_HIP(hipMemsetAsync(err.p, 0, 4 * sizeof(int), stream()));
     gpp_nearest_device(igrid, to->d_x.p, to->d_y.p, to->d_z.p, nq, 1, idx.p);
     hipLaunchKernelGGL(k_bilinear, dim3((nq + 255) / 256), dim3(256), 0, stream(), igrid->d_lat.p, igrid->d_lon.p, igrid->ny, igrid->nx,
-                       idx.p, to->d_lat.p, to->d_lon.p, nq, v.d, nt, o.d, err.p);
-    GPP_HIP(hipGetLastError());
-    int herr[4];
-    GPP_HIP(hipMemcpyAsync(herr, err.p, sizeof(herr), hipMemcpyDeviceToHost, stream()));
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    bilinear_check_distorted(herr);
+                       idx.p, to->d_lat.p, to->d_lon.p, nq, v.d, nt, call.o.d, call.err);
+    call.finish();
     return GPP_OK;
     GPP_CATCH
 }

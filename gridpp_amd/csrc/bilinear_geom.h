@@ -1,5 +1,5 @@
-// The box search and the weights of gridpp::bilinear, shared by k_bilinear (bilinear.hip) and the downscalers
-// (downscale.hip): Grid::get_box (src/api/grid.cpp:149-229), point_in_rectangle (src/api/util.cpp:561-582) and the
+// The box search and the weights of gridpp::bilinear, shared by the direct locator (downscale_loc.h), k_get_box (bilinear.hip)
+// and k_plan_build (downscale_plan.hip): Grid::get_box (src/api/grid.cpp:149-229), point_in_rectangle (src/api/util.cpp:561-582) and the
 // weights / interpolation of src/api/bilinear.cpp:137-320.  Every float expression keeps the reference's association
 // (the build has -ffp-contract=off and correctly rounded float divide).  Internal linkage: each translation unit has
 // its own device code object.
@@ -123,7 +123,3 @@ __device__ __forceinline__ float bilinear_value(float v0, float v1, float v2, fl
 }
 
 }   // namespace
-
-// bilinear.hip: the reference's std::runtime_error "Problem with bilinear interpolation..." when a kernel flagged a box
-// whose weights leave [0, 1]: err[0] = 1, err[1..2] = bits of the offending (s, t) (bilinear.cpp:309-313)
-void bilinear_check_distorted(const int herr[4]);

@@ -170,37 +170,28 @@ struct InField {
         else { staged.upload(src, n); d = staged.p; }
     }
 };
-struct OutField {
-    Staged<float> staged;
-    float* d = nullptr;
-    float* host = nullptr;
+// An output argument of the C-ABI resolved to a device pointer: the caller's HBM pointer, or a staged buffer that finish() copies back
+template <class T>
+struct OutArray {
+    Staged<T> staged;
+    T* d = nullptr;
+    T* host = nullptr;
     size_t n = 0;
-    void bind(float* dst, size_t n_, int mem) {
+    void bind(T* dst, size_t n_, int mem) {
         n = n_;
         if(!dst) { d = nullptr; host = nullptr; return; }
         if(mem & GPP_MEM_DEVICE) { d = dst; host = nullptr; }
         else { d = staged.get(n); host = dst; }
     }
     void finish() {
-        if(host && n) GPP_HIP(hipMemcpyAsync(host, d, n * sizeof(float), hipMemcpyDeviceToHost, stream()));
+        if(host && n) GPP_HIP(hipMemcpyAsync(host, d, n * sizeof(T), hipMemcpyDeviceToHost, stream()));
     }
 };
-// the int32 form of OutField (the ranks of gpp_calc_ranks)
-struct OutInts {
-    Staged<int> staged;
-    int* d = nullptr;
-    int* host = nullptr;
-    size_t n = 0;
-    void bind(int* dst, size_t n_, int mem) {
-        n = n_;
-        if(!dst) { d = nullptr; host = nullptr; return; }
-        if(mem & GPP_MEM_DEVICE) { d = dst; host = nullptr; }
-        else { d = staged.get(n); host = dst; }
-    }
-    void finish() {
-        if(host && n) GPP_HIP(hipMemcpyAsync(host, d, n * sizeof(int), hipMemcpyDeviceToHost, stream()));
-    }
-};
+using OutField = OutArray<float>;
+using OutInts = OutArray<int>;   // the ranks of gpp_calc_ranks
+
+// runtime.hip: d[0 .. n) = v on the library stream (the one fill kernel of the library)
+void fill_f32(float* d, size_t n, float v);
 
 inline bool is_valid(float v) { return !std::isnan(v) && !std::isinf(v); }   // src/api/util.cpp:16-18
 

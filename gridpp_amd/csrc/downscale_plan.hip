@@ -7,14 +7,15 @@
 //   Nearest    int32          the nearest grid point (-1: none)
 //   Bilinear   int4, 16 B     .x the nearest grid point; .y the flat index c of corner (Y1, X1) of its box, -1 when it is in no box,
 //                             -2 - c when the weights of the box leave [0, 1] (the reference throws there); .z / .w the bits of s / t.
-// get_box always returns Y2 = Y1 + 1 and X2 = X1 + 1, so the other corners are c + nX, c + 1 and c + nX + 1, and the nearest grid point
-// is one of the four: inside a box the nearest-neighbour fallback of a field with a missing corner takes that corner's value from the
-// registers instead of a fifth load.
+// The planned locator of downscale_loc.h reads a record; d(f), the level loop and the gradient combination are the ones the direct
+// calls use, so a kernel here is a few lines around them.  Inside a box the nearest-neighbour fallback of a field with a missing
+// corner takes that corner's value from the registers instead of a fifth load (the nearest grid point is one of the four).
 //
 // The error of a distorted box keeps the condition of the direct calls: a location with bad weights raises in the apply in which one
 // of the downscaled fields has four valid corners there (bilinear.cpp:309-313), never at construction.
 #include "common.h"
-#include "bilinear_geom.h"
+#include "downscale_loc.h"
+#include "downscale_call.h"
 #include "ensemble_downscale.h"
 #include <climits>
 #include <memory>
@@ -43,47 +44,6 @@ __global__ __launch_bounds__(256) void k_plan_build(const float* __restrict__ gl
     rec[q] = make_int4(n0, code, __float_as_int(s), __float_as_int(t));
 }
 
-// A record in registers.  c >= 0: corner (Y1, X1) of the box; `bad`: its weights leave [0, 1].
-struct Loc {
-    int n0, c;
-    bool inside, bad;
-    float s, t;
-};
-template <bool BIL>
-__device__ __forceinline__ Loc load_loc(const int4* __restrict__ rec, const int* __restrict__ nn, const int q) {
-    Loc l;
-    l.c = -1; l.inside = false; l.bad = false; l.s = 0; l.t = 0;
-    if(BIL) {
-        const int4 r = rec[q];
-        l.n0 = r.x;
-        l.inside = r.y != -1;
-        l.bad = r.y < -1;
-        l.c = l.bad ? -2 - r.y : r.y;
-        l.s = __int_as_float(r.z); l.t = __int_as_float(r.w);
-    }
-    else l.n0 = nn[q];
-    return l;
-}
-__device__ __forceinline__ void flag_distorted(int* __restrict__ err, const float s, const float t) {
-    if(atomicCAS(&err[0], 0, 1) == 0) { err[1] = __float_as_int(s); err[2] = __float_as_int(t); }
-}
-// the value of a field with corners v0 = (Y1, X1), v1 = (Y2, X1), v2 = (Y1, X2), v3 = (Y2, X2) at a location inside that box
-__device__ __forceinline__ float in_box(const Loc& l, const float v0, const float v1, const float v2, const float v3, const int nX,
-                                        bool& flagged, int* __restrict__ err) {
-    if(dev_valid(v0) && dev_valid(v1) && dev_valid(v2) && dev_valid(v3)) {
-        if(l.bad && !flagged) { flag_distorted(err, l.s, l.t); flagged = true; }
-        return bilinear_value(v0, v1, v2, v3, l.s, l.t);
-    }
-    const int d = l.n0 - l.c;   // a missing corner: the nearest grid point, one of the four
-    return d == 0 ? v0 : d == nX ? v1 : d == 1 ? v2 : v3;
-}
-// d(f) at a location: a level of (T, Y, X)
-template <bool BIL>
-__device__ __forceinline__ float down(const Loc& l, const float* __restrict__ f, const int nX, bool& flagged, int* __restrict__ err) {
-    if(BIL && l.inside) return in_box(l, f[l.c], f[l.c + nX], f[l.c + 1], f[l.c + nX + 1], nX, flagged, err);
-    return l.n0 >= 0 ? f[l.n0] : NAN;   // outside the domain: nearest neighbour
-}
-
 // values [nt][nG] -> out [nt][nq]: a location per thread, unit-stride writes across lanes per level (as k_bilinear / k_gather_levels)
 template <bool BIL>
 __global__ __launch_bounds__(256) void k_plan_apply(const int4* __restrict__ rec, const int* __restrict__ nn, const int nq, const int nX,
@@ -91,18 +51,16 @@ __global__ __launch_bounds__(256) void k_plan_apply(const int4* __restrict__ rec
                                                     float* __restrict__ out, int* __restrict__ err) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if(q >= nq) return;
-    const Loc l = load_loc<BIL>(rec, nn, q);
-    bool flagged = false;
-    for(int k = 0; k < nt; ++k) out[(size_t)k * nq + q] = down<BIL>(l, values + (size_t)k * nG, nX, flagged, err);
+    PlannedLoc<BIL> l(rec, nn, q, nX, err);
+    down_levels(l, values, nG, nt, out, (size_t)nq, q);
 }
 
 // values [nG][E] -> out [nq][E] (gridpp's cube layout, the member index innermost): G lanes per location, 64 / G locations per wave;
 // lane j of a group takes V members at V j, V (j + G), ...: every corner is read as runs of V G contiguous floats and the output run is
 // written with unit stride across the group.  The four-corner validity test is per member.  V = 2 (one 8-byte access per lane; E even,
 // both arrays 8-byte aligned) is the measured winner for Bilinear, V = 1 serves every other case.
-template <int V> struct VecOf;
-template <> struct VecOf<1> { using type = float; };
-template <> struct VecOf<2> { using type = float2; };
+// The loads are PlannedLoc::down_members' written out: calling it here costs the Bilinear V = 1 kernels four VGPRs (30 -> 34).  The
+// occupancy would stay 8 waves per SIMD; the rule that a refactor leaves every kernel's registers as they were decided it, not a timing.
 template <bool BIL, int G, int V>
 __global__ __launch_bounds__(256) void k_plan_apply_cube(const int4* __restrict__ rec, const int* __restrict__ nn, const int nq,
                                                          const int nX, const float* __restrict__ values, const int E,
@@ -111,8 +69,7 @@ __global__ __launch_bounds__(256) void k_plan_apply_cube(const int4* __restrict_
     const size_t g = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
     if(g >= (size_t)nq) return;
     const int q = (int)g, lane = threadIdx.x % G;
-    const Loc l = load_loc<BIL>(rec, nn, q);
-    bool flagged = false;
+    PlannedLoc<BIL> l(rec, nn, q, nX, err);
     float* __restrict__ o = out + (size_t)q * E;
     for(int e = lane * V; e < E; e += G * V) {
         union { vec v; float f[V]; } a0, a1, a2, a3, r;
@@ -121,7 +78,7 @@ __global__ __launch_bounds__(256) void k_plan_apply_cube(const int4* __restrict_
             a0.v = *reinterpret_cast<const vec*>(f); a1.v = *reinterpret_cast<const vec*>(f + (size_t)nX * E);
             a2.v = *reinterpret_cast<const vec*>(f + E); a3.v = *reinterpret_cast<const vec*>(f + (size_t)(nX + 1) * E);
 #pragma unroll
-            for(int u = 0; u < V; ++u) r.f[u] = in_box(l, a0.f[u], a1.f[u], a2.f[u], a3.f[u], nX, flagged, err);
+            for(int u = 0; u < V; ++u) r.f[u] = l.in_box(a0.f[u], a1.f[u], a2.f[u], a3.f[u]);
         }
         else if(l.n0 >= 0) r.v = *reinterpret_cast<const vec*>(values + (size_t)l.n0 * E + e);   // outside the domain: nearest neighbour
         else {
@@ -132,134 +89,48 @@ __global__ __launch_bounds__(256) void k_plan_apply_cube(const int4* __restrict_
     }
 }
 
-struct GradientArgs {
+struct GradientArgs : GradientFields {   // values, egrad, lgrad [nt][n_in], out [nt][nq]
     const int4* rec; const int* nn; int nq, nX;
-    const float* values; const float* egrad; const float* lgrad;   // [nt][n_in]; egrad / lgrad NULL = term absent
     int nt; size_t n_in;
-    const float* ielev; const float* ilaf;               // input grid [n_in]
-    const float* oelev; const float* olaf;               // output locations [nq]
-    float elev_gradient;                                 // simple_gradient's scalar
-    int full;                                            // 0: simple_gradient, 1: full_gradient
-    float* out;                                          // [nt][nq]
-    int* err;
 };
 
-// k_downscale (downscale.hip) with d(f) read from the record.  A gradient whose term is switched off at a location is still downscaled
-// by the reference and may raise there: its corners are read only where the weights are bad and nothing has raised yet.
+// k_downscale (downscale.hip) with d(f) read from the record
 template <bool BIL>
 __global__ __launch_bounds__(256) void k_plan_gradient(const GradientArgs a) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if(q >= a.nq) return;
-    const Loc l = load_loc<BIL>(a.rec, a.nn, q);
-    bool flagged = false;
-    auto d = [&](const float* __restrict__ f) -> float { return down<BIL>(l, f, a.nX, flagged, a.err); };
-    const size_t nq = a.nq;
-    if(!a.full) {   // simple_gradient.cpp: out = d(values) + (oelev - d(ielevs)) * elev_gradient, no validity test
-        const float elev_corr = (a.oelev[q] - d(a.ielev)) * a.elev_gradient;
-        for(int k = 0; k < a.nt; ++k) a.out[(size_t)k * nq + q] = d(a.values + (size_t)k * a.n_in) + elev_corr;
-        return;
-    }
-    // gradient.cpp:56-81: a term counts where the output's and the downscaled input's elevation (laf) are both valid
-    float ediff = 0, ldiff = 0;
-    bool euse = false, luse = false;
-    if(a.egrad) {
-        const float oe = a.oelev[q], ie = d(a.ielev);
-        euse = dev_valid(oe) && dev_valid(ie);
-        ediff = oe - ie;
-    }
-    if(a.lgrad) {
-        const float ol = a.olaf[q], il = d(a.ilaf);
-        luse = dev_valid(ol) && dev_valid(il);
-        ldiff = ol - il;
-    }
-    for(int k = 0; k < a.nt; ++k) {
-        const size_t off = (size_t)k * a.n_in;
-        const float v = d(a.values + off);
-        float laf_corr = 0, elev_corr = 0;
-        if(a.lgrad) {
-            if(luse) laf_corr = d(a.lgrad + off) * ldiff;
-            else if(BIL && l.bad && !flagged) (void)d(a.lgrad + off);
-        }
-        if(a.egrad) {
-            if(euse) elev_corr = d(a.egrad + off) * ediff;
-            else if(BIL && l.bad && !flagged) (void)d(a.egrad + off);
-        }
-        a.out[(size_t)k * nq + q] = v + (laf_corr + elev_corr);
-    }
+    PlannedLoc<BIL> l(a.rec, a.nn, q, a.nX, a.err);
+    gradient_levels(l, a, a.n_in, a.nt, (size_t)a.nq, q);
 }
 
-struct GradientCubeArgs {
+struct GradientCubeArgs : GradientFields {   // values [n_in][E], out [nq][E]; egrad / lgrad [n_in] shared by the members, or [n_in][E]
     const int4* rec; const int* nn; int nq, nX, E;
-    const float* values;                                 // [n_in][E]
-    const float* egrad; const float* lgrad;              // NULL = term absent; [n_in] shared by the members, or [n_in][E]
-    int e_members, l_members;                            // != 0: that gradient is [n_in][E]
-    const float* ielev; const float* ilaf;               // input grid [n_in]
-    const float* oelev; const float* olaf;               // output locations [nq]
-    float elev_gradient;                                 // simple_gradient's scalar
-    int full;                                            // 0: simple_gradient, 1: full_gradient
-    float* out;                                          // [nq][E]
-    int* err;
+    int e_members, l_members;                // != 0: that gradient is [n_in][E]
 };
 
-// d(f) of V members e ... e + V - 1 of a cube [n_in][E] at a location: k_plan_apply_cube's loads
-template <bool BIL, int V>
-__device__ __forceinline__ void down_members(const Loc& l, const float* __restrict__ f, const int E, const int e, const int nX, bool& flagged,
-                                             int* __restrict__ err, float (&r)[V]) {
-    using vec = typename VecOf<V>::type;
-    union { vec v; float f[V]; } a0, a1, a2, a3;
-    if(BIL && l.inside) {
-        const float* __restrict__ c = f + (size_t)l.c * E + e;
-        a0.v = *reinterpret_cast<const vec*>(c); a1.v = *reinterpret_cast<const vec*>(c + (size_t)nX * E);
-        a2.v = *reinterpret_cast<const vec*>(c + E); a3.v = *reinterpret_cast<const vec*>(c + (size_t)(nX + 1) * E);
-#pragma unroll
-        for(int u = 0; u < V; ++u) r[u] = in_box(l, a0.f[u], a1.f[u], a2.f[u], a3.f[u], nX, flagged, err);
-    }
-    else if(l.n0 >= 0) {   // outside the domain: nearest neighbour
-        a0.v = *reinterpret_cast<const vec*>(f + (size_t)l.n0 * E + e);
-#pragma unroll
-        for(int u = 0; u < V; ++u) r[u] = a0.f[u];
-    }
-    else {
-#pragma unroll
-        for(int u = 0; u < V; ++u) r[u] = NAN;
-    }
-}
-
 // k_plan_gradient on cubes: values [n_in][E] -> out [nq][E] with the lanes of k_plan_apply_cube.  Everything that does not depend on
-// the member -- the record, oelev - d(ielev), olaf - d(ilaf), the two `use` flags and the term of a gradient shared by the members --
-// is computed before the member loop (every lane of a group reads the same few addresses); with shared gradients the loop is
-// k_plan_apply_cube's plus one add.  PM: a gradient has a field per member and adds its four corner runs to the loop.
+// the member -- the record, the two terms (gradient_term) and the correction of a gradient shared by the members -- is computed before
+// the member loop (every lane of a group reads the same few addresses); with shared gradients the loop is k_plan_apply_cube's plus one
+// add.  PM: a gradient has a field per member and adds its four corner runs to the loop.
 template <bool BIL, int G, int V, bool PM>
 __global__ __launch_bounds__(256) void k_plan_gradient_cube(const GradientCubeArgs a) {
     using vec = typename VecOf<V>::type;
     const size_t g = (size_t)blockIdx.x * (256 / G) + threadIdx.x / G;
     if(g >= (size_t)a.nq) return;
     const int q = (int)g, lane = threadIdx.x % G, E = a.E;
-    const Loc l = load_loc<BIL>(a.rec, a.nn, q);
-    bool flagged = false;
-    auto d = [&](const float* __restrict__ f) -> float { return down<BIL>(l, f, a.nX, flagged, a.err); };
+    PlannedLoc<BIL> l(a.rec, a.nn, q, a.nX, a.err);
     const bool e_pm = PM && a.e_members, l_pm = PM && a.l_members;
-    float ediff = 0, ldiff = 0, elev_corr = 0, laf_corr = 0, corr;
-    bool euse = false, luse = false;
-    if(!a.full) corr = (a.oelev[q] - d(a.ielev)) * a.elev_gradient;   // simple_gradient.cpp: no validity test
-    else {   // gradient.cpp:56-81, as k_plan_gradient: a switched-off gradient is still downscaled where it could be the one to raise
+    float elev_corr = 0, laf_corr = 0, corr;
+    GradientTerm et, lt;
+    if(!a.full) corr = (a.oelev[q] - l.down(a.ielev)) * a.elev_gradient;   // simple_gradient.cpp: no validity test
+    else {
         if(a.lgrad) {
-            const float ol = a.olaf[q], il = d(a.ilaf);
-            luse = dev_valid(ol) && dev_valid(il);
-            ldiff = ol - il;
-            if(!l_pm) {
-                if(luse) laf_corr = d(a.lgrad) * ldiff;
-                else if(BIL && l.bad && !flagged) (void)d(a.lgrad);
-            }
+            lt = gradient_term(l, a.olaf, a.ilaf, q);
+            if(!l_pm) laf_corr = gradient_corr(l, lt, a.lgrad);
         }
         if(a.egrad) {
-            const float oe = a.oelev[q], ie = d(a.ielev);
-            euse = dev_valid(oe) && dev_valid(ie);
-            ediff = oe - ie;
-            if(!e_pm) {
-                if(euse) elev_corr = d(a.egrad) * ediff;
-                else if(BIL && l.bad && !flagged) (void)d(a.egrad);
-            }
+            et = gradient_term(l, a.oelev, a.ielev, q);
+            if(!e_pm) elev_corr = gradient_corr(l, et, a.egrad);
         }
         corr = laf_corr + elev_corr;
     }
@@ -267,20 +138,20 @@ __global__ __launch_bounds__(256) void k_plan_gradient_cube(const GradientCubeAr
     for(int e = lane * V; e < E; e += G * V) {
         union { vec v; float f[V]; } r;
         float v[V];
-        down_members<BIL, V>(l, a.values, E, e, a.nX, flagged, a.err, v);
-        if(PM) {
+        l.template down_members<V>(a.values, E, e, v);
+        if(PM) {   // gradient_corr per member
             float lc[V], ec[V], t[V];
 #pragma unroll
             for(int u = 0; u < V; ++u) { lc[u] = laf_corr; ec[u] = elev_corr; }
-            if(l_pm && (luse || (BIL && l.bad && !flagged))) {
-                down_members<BIL, V>(l, a.lgrad, E, e, a.nX, flagged, a.err, t);
+            if(l_pm && (lt.use || l.may_still_raise())) {
+                l.template down_members<V>(a.lgrad, E, e, t);
 #pragma unroll
-                for(int u = 0; u < V; ++u) if(luse) lc[u] = t[u] * ldiff;
+                for(int u = 0; u < V; ++u) if(lt.use) lc[u] = t[u] * lt.diff;
             }
-            if(e_pm && (euse || (BIL && l.bad && !flagged))) {
-                down_members<BIL, V>(l, a.egrad, E, e, a.nX, flagged, a.err, t);
+            if(e_pm && (et.use || l.may_still_raise())) {
+                l.template down_members<V>(a.egrad, E, e, t);
 #pragma unroll
-                for(int u = 0; u < V; ++u) if(euse) ec[u] = t[u] * ediff;
+                for(int u = 0; u < V; ++u) if(et.use) ec[u] = t[u] * et.diff;
             }
 #pragma unroll
             for(int u = 0; u < V; ++u) r.f[u] = v[u] + (lc[u] + ec[u]);
@@ -297,16 +168,6 @@ __global__ __launch_bounds__(256) void k_plan_gradient_cube(const GradientCubeAr
 __global__ __launch_bounds__(256) void k_plan_nearest_of_records(const int4* __restrict__ rec, const int nq, int* __restrict__ nn) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if(q < nq) nn[q] = rec[q].x;
-}
-
-__global__ void k_plan_fill_nan(float* out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = NAN;
-}
-
-int group_of(int E) {   // as ensemble_downscale.hip: the smallest of 4 ... 64 with E <= 4 G
-    for(int g = 4; g < 64; g *= 2) if(E <= 4 * g) return g;
-    return 64;
 }
 
 }   // namespace
@@ -334,37 +195,6 @@ void copy_field(DevBuf<float>& dst, const float* src, size_t n) {
     if(n) GPP_HIP(hipMemcpyAsync(dst.p, src, n * sizeof(float), hipMemcpyDeviceToDevice, stream()));
 }
 
-// What the entry points of a plan share once their own checks have passed: the output, an all-NaN result for an empty input grid
-// (nearest.cpp:132-134, bilinear.cpp:37-39), and the error of a distorted box after the kernel.
-struct PlanCall {
-    gpp_downscale_plan* p;
-    OutField o;
-    bool done = false;
-    PlanCall(gpp_downscale_plan* plan, const float* values, float* out, size_t nout, int mem) : p(plan) {
-        if(!out) invalid("out is NULL");
-        o.bind(out, nout, mem);
-        if(p->n_in == 0) {
-            hipLaunchKernelGGL(k_plan_fill_nan, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream(), o.d, nout);
-            GPP_HIP(hipGetLastError());
-            o.finish();
-            GPP_HIP(hipStreamSynchronize(stream()));
-            done = true;
-            return;
-        }
-        if(!values) invalid("values is NULL");
-        p->err.get(4);
-        GPP_HIP(hipMemsetAsync(p->err.p, 0, 4 * sizeof(int), stream()));
-    }
-    void finish() {
-        GPP_HIP(hipGetLastError());
-        int herr[4];
-        GPP_HIP(hipMemcpyAsync(herr, p->err.p, sizeof(herr), hipMemcpyDeviceToHost, stream()));
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        bilinear_check_distorted(herr);
-    }
-};
-
 void plan_gradient(gpp_downscale_plan* p, const float* values, int nt, const float* egrad, const float* lgrad, float elev_gradient, int full,
                    float* out, int mem) {
     if(!p) invalid("plan handle is NULL");
@@ -372,7 +202,7 @@ void plan_gradient(gpp_downscale_plan* p, const float* values, int nt, const flo
     if(p->nq == 0 || nt == 0) return;
     ensure_device();
     mem &= ~GPP_ASYNC;
-    PlanCall call(p, values, out, (size_t)nt * p->nq, mem);
+    DownscaleCall call(p->n_in, values, out, (size_t)nt * p->nq, mem, &p->err);
     if(call.done) return;
     const size_t nin = (size_t)nt * p->n_in;
     InField v, eg, lg;
@@ -386,7 +216,7 @@ void plan_gradient(gpp_downscale_plan* p, const float* values, int nt, const flo
     a.ielev = p->ielev.p; a.ilaf = p->ilaf.p; a.oelev = p->oelev.p; a.olaf = p->olaf.p;
     a.elev_gradient = elev_gradient;
     a.full = full;
-    a.out = call.o.d; a.err = p->err.p;
+    a.out = call.o.d; a.err = call.err;
     const dim3 grid((p->nq + 255) / 256), block(256);
     if(p->downscaler == 1) hipLaunchKernelGGL(k_plan_gradient<true>, grid, block, 0, stream(), a);
     else hipLaunchKernelGGL(k_plan_gradient<false>, grid, block, 0, stream(), a);
@@ -467,17 +297,17 @@ extern "C" int gpp_downscale_plan_apply(gpp_downscale_plan* plan, const float* v
     if(plan->nq == 0 || nt == 0) return GPP_OK;
     ensure_device();
     mem &= ~GPP_ASYNC;
-    PlanCall call(plan, values, out, (size_t)nt * plan->nq, mem);
+    DownscaleCall call(plan->n_in, values, out, (size_t)nt * plan->nq, mem, &plan->err);
     if(call.done) return GPP_OK;
     InField v;
     v.bind(values, (size_t)nt * plan->n_in, mem);
     const dim3 grid((plan->nq + 255) / 256), block(256);
     if(plan->downscaler == 1)
         hipLaunchKernelGGL(k_plan_apply<true>, grid, block, 0, stream(), (const int4*)plan->rec.p, (const int*)nullptr, plan->nq, plan->nX, plan->n_in,
-                           v.d, nt, call.o.d, plan->err.p);
+                           v.d, nt, call.o.d, call.err);
     else
         hipLaunchKernelGGL(k_plan_apply<false>, grid, block, 0, stream(), (const int4*)nullptr, (const int*)plan->nn.p, plan->nq, plan->nX, plan->n_in,
-                           v.d, nt, call.o.d, plan->err.p);
+                           v.d, nt, call.o.d, call.err);
     call.finish();
     return GPP_OK;
     GPP_CATCH
@@ -490,7 +320,7 @@ extern "C" int gpp_downscale_plan_apply_cube(gpp_downscale_plan* plan, const flo
     if(plan->nq == 0 || ne == 0) return GPP_OK;
     ensure_device();
     mem &= ~GPP_ASYNC;
-    PlanCall call(plan, values, out, (size_t)ne * plan->nq, mem);
+    DownscaleCall call(plan->n_in, values, out, (size_t)ne * plan->nq, mem, &plan->err);
     if(call.done) return GPP_OK;
     InField v;
     v.bind(values, (size_t)ne * plan->n_in, mem);
@@ -502,21 +332,15 @@ extern "C" int gpp_downscale_plan_apply_cube(gpp_downscale_plan* plan, const flo
     const size_t blocks = ((size_t)plan->nq + 256 / G - 1) / (256 / G);
     if(blocks > (size_t)INT_MAX) invalid("too many output locations for this many members");
     const dim3 grid((unsigned)blocks), block(256);
-#define GPP_CUBE(G_)                                                                                                                      \
-    if(wide) hipLaunchKernelGGL((k_plan_apply_cube<true, G_, 2>), grid, block, 0, stream(), (const int4*)plan->rec.p, (const int*)nullptr, \
-                                plan->nq, plan->nX, v.d, ne, call.o.d, plan->err.p);                                                       \
-    else if(bil) hipLaunchKernelGGL((k_plan_apply_cube<true, G_, 1>), grid, block, 0, stream(), (const int4*)plan->rec.p,                  \
-                                    (const int*)nullptr, plan->nq, plan->nX, v.d, ne, call.o.d, plan->err.p);                              \
-    else hipLaunchKernelGGL((k_plan_apply_cube<false, G_, 1>), grid, block, 0, stream(), (const int4*)nullptr, (const int*)plan->nn.p,     \
-                            plan->nq, plan->nX, v.d, ne, call.o.d, plan->err.p)
-    switch(G) {
-        case 4: GPP_CUBE(4); break;
-        case 8: GPP_CUBE(8); break;
-        case 16: GPP_CUBE(16); break;
-        case 32: GPP_CUBE(32); break;
-        default: GPP_CUBE(64); break;
-    }
-#undef GPP_CUBE
+    const int4* rec = bil ? plan->rec.p : nullptr;
+    const int* nn = bil ? nullptr : plan->nn.p;
+    dispatch_group(G, [&](auto g_) {
+        constexpr int G_ = decltype(g_)::value;
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, stream(), rec, nn, plan->nq, plan->nX, v.d, ne, call.o.d, call.err); };
+        if(wide) launch(k_plan_apply_cube<true, G_, 2>);
+        else if(bil) launch(k_plan_apply_cube<true, G_, 1>);
+        else launch(k_plan_apply_cube<false, G_, 1>);
+    });
     call.finish();
     return GPP_OK;
     GPP_CATCH
@@ -549,7 +373,7 @@ void plan_gradient_cube(gpp_downscale_plan* p, const float* values, int ne, cons
         invalid("a gradient must have 1 or ne members");
     ensure_device();
     mem &= ~GPP_ASYNC;
-    PlanCall call(p, values, out, (size_t)ne * p->nq, mem);
+    DownscaleCall call(p->n_in, values, out, (size_t)ne * p->nq, mem, &p->err);
     if(call.done) return;
     const bool e_pm = egrad && e_members == ne && ne > 1, l_pm = lgrad && l_members == ne && ne > 1;
     InField v, eg, lg;
@@ -563,7 +387,7 @@ void plan_gradient_cube(gpp_downscale_plan* p, const float* values, int ne, cons
     a.ielev = p->ielev.p; a.ilaf = p->ilaf.p; a.oelev = p->oelev.p; a.olaf = p->olaf.p;
     a.elev_gradient = elev_gradient;
     a.full = full;
-    a.out = call.o.d; a.err = p->err.p;
+    a.out = call.o.d; a.err = call.err;
     const bool bil = p->downscaler == 1, pm = e_pm || l_pm;
     // 8-byte accesses under k_plan_apply_cube's condition (Bilinear, E even), for every array that is read or written in runs of members
     uintptr_t bound = (uintptr_t)v.d | (uintptr_t)call.o.d;
@@ -574,22 +398,13 @@ void plan_gradient_cube(gpp_downscale_plan* p, const float* values, int ne, cons
     const size_t blocks = ((size_t)p->nq + 256 / G - 1) / (256 / G);
     if(blocks > (size_t)INT_MAX) invalid("too many output locations for this many members");
     const dim3 grid((unsigned)blocks), block(256);
-#define GPP_GCUBE2(G_, PM_)                                                                                          \
-    if(wide) hipLaunchKernelGGL((k_plan_gradient_cube<true, G_, 2, PM_>), grid, block, 0, stream(), a);             \
-    else if(bil) hipLaunchKernelGGL((k_plan_gradient_cube<true, G_, 1, PM_>), grid, block, 0, stream(), a);         \
-    else hipLaunchKernelGGL((k_plan_gradient_cube<false, G_, 1, PM_>), grid, block, 0, stream(), a)
-#define GPP_GCUBE(G_)                                                                                                \
-    if(pm) { GPP_GCUBE2(G_, true); }                                                                                 \
-    else { GPP_GCUBE2(G_, false); }
-    switch(G) {
-        case 4: GPP_GCUBE(4); break;
-        case 8: GPP_GCUBE(8); break;
-        case 16: GPP_GCUBE(16); break;
-        case 32: GPP_GCUBE(32); break;
-        default: GPP_GCUBE(64); break;
-    }
-#undef GPP_GCUBE
-#undef GPP_GCUBE2
+    dispatch_group(G, [&](auto g_) {
+        constexpr int G_ = decltype(g_)::value;
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, stream(), a); };
+        if(wide) launch(pm ? k_plan_gradient_cube<true, G_, 2, true> : k_plan_gradient_cube<true, G_, 2, false>);
+        else if(bil) launch(pm ? k_plan_gradient_cube<true, G_, 1, true> : k_plan_gradient_cube<true, G_, 1, false>);
+        else launch(pm ? k_plan_gradient_cube<false, G_, 1, true> : k_plan_gradient_cube<false, G_, 1, false>);
+    });
     call.finish();
 }
 

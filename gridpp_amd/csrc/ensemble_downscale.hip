@@ -18,6 +18,9 @@
 //   k_ens_rows_result   slab and one thread per cell runs the same row functions on its row from memory.  A slab holds 2^26
 //                       masked members; GPP_ENSEMBLE_SLAB (a path override) sets another number, so that the tests run
 //                       several slabs, a ragged last one included, on a grid of a hundred cells.
+//
+// The group size (group_of) and its way into a template argument (dispatch_group) are in ensemble_downscale.h, shared with the
+// cube-layout kernels of a plan (downscale_plan.hip); the NaN / Count fills go through fill_f32 (runtime.hip).
 #include "common.h"
 #include "row_stats.h"
 #include "ensemble_downscale.h"
@@ -172,18 +175,10 @@ __global__ __launch_bounds__(256) void k_ens_rows_result(const float* __restrict
     out[q0 + c] = row_result(scratch + (size_t)c * E, E, statistic, quantile, q0 + c, seed);
 }
 
-__global__ void k_ens_fill(float* out, size_t n, float v) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = v;
-}
-
 unsigned blocks_for(int nq, int G) { return (unsigned)(((long long)nq * G + 255) / 256); }
 
-// lanes per cell: the smallest group whose lanes read at most four members each
-int group_of(int E) {
-    for(int g = 4; g < 64; g *= 2) if(E <= 4 * g) return g;
-    return 64;
-}
+// members the LDS row of a group of G lanes holds: the four per lane that group_of allows, the whole cap for the largest group
+constexpr int row_cap(int G) { return G == 64 ? GPP_ENSEMBLE_ROW_CAP : 4 * G; }
 
 void check_operator(int op) {
     if(op != GPP_LT && op != GPP_LEQ && op != GPP_GT && op != GPP_GEQ) invalid("Invalid comparison operator");
@@ -201,8 +196,7 @@ void check_ensemble(int ne, int op) {
 }
 
 void fill(OutField& o, size_t n, float v) {
-    hipLaunchKernelGGL(k_ens_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), o.d, n, v);
-    GPP_HIP(hipGetLastError());
+    fill_f32(o.d, n, v);
     o.finish();
     GPP_HIP(hipStreamSynchronize(stream()));
 }
@@ -242,15 +236,10 @@ void gpp::ensemble_probability(const NearestIndex& index, size_t n_in, int nq, c
     v.bind(values, n_in * ne, mem);
     th.bind(threshold, nq, mem);
     const int* idx = index();
-#define GPP_PROB(G) hipLaunchKernelGGL(k_ens_probability<G>, dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, v.d, ne, th.d, nq, comparison_operator, o.d)
-    switch(group_of(ne)) {
-        case 4: GPP_PROB(4); break;
-        case 8: GPP_PROB(8); break;
-        case 16: GPP_PROB(16); break;
-        case 32: GPP_PROB(32); break;
-        default: GPP_PROB(64); break;
-    }
-#undef GPP_PROB
+    dispatch_group(group_of(ne), [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        hipLaunchKernelGGL(k_ens_probability<G>, dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, v.d, ne, th.d, nq, comparison_operator, o.d);
+    });
     GPP_HIP(hipGetLastError());
     o.finish();
     GPP_HIP(hipStreamSynchronize(stream()));
@@ -286,16 +275,11 @@ void gpp::ensemble_mask_threshold(const NearestIndex& index, size_t n_in, int nq
     const int* idx = index();
     const unsigned seed = (g_seed = g_seed * 1664525u + 1013904223u);
     if(ne <= GPP_ENSEMBLE_ROW_CAP) {
-#define GPP_MASK(G, CAP) hipLaunchKernelGGL((k_ens_mask<G, CAP>), dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, vt.d, vf.d, tv.d, ne, \
-                                            th.d, nq, comparison_operator, statistic, quantile, seed, o.d)
-        switch(group_of(ne)) {
-            case 4: GPP_MASK(4, 16); break;
-            case 8: GPP_MASK(8, 32); break;
-            case 16: GPP_MASK(16, 64); break;
-            case 32: GPP_MASK(32, 128); break;
-            default: GPP_MASK(64, GPP_ENSEMBLE_ROW_CAP); break;
-        }
-#undef GPP_MASK
+        dispatch_group(group_of(ne), [&](auto g) {
+            constexpr int G = decltype(g)::value;
+            hipLaunchKernelGGL((k_ens_mask<G, row_cap(G)>), dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, vt.d, vf.d, tv.d, ne, th.d, nq,
+                               comparison_operator, statistic, quantile, seed, o.d);
+        });
         GPP_HIP(hipGetLastError());
     }
     else {   // slabs of at most 2^26 masked members (256 MiB)

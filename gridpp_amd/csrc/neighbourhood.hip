@@ -987,10 +987,6 @@ __global__ __launch_bounds__(256) void k_minmax_pass(const float* __restrict__ i
     }
     out[(long)y * X + x] = m;
 }
-__global__ void k_fill_nan(float* out, long n) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = NAN;
-}
 __global__ void k_square(const float* __restrict__ in, long n, float* __restrict__ out) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if(i < n) { float v = in[i]; out[i] = v * v; }
@@ -1466,7 +1462,7 @@ struct QfCall : Fields {
         if(q_on_device) GPP_HIP(hipStreamSynchronize(stream()));
         check_fetched_q();
         const long n = C * width;
-        if(n > 0) hipLaunchKernelGGL(k_fill_nan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), o.d, n);
+        if(n > 0) fill_f32(o.d, (size_t)n, NAN);
         return done();
     }
     void bind_quantile() {

@@ -196,10 +196,6 @@ __global__ void k_gather_sorted(const float* __restrict__ values, const int* __r
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i < n) out[i] = values[order[i]];
 }
-__global__ void k_fill_value(float* out, size_t n, float v) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = v;
-}
 
 void check_same_type(gpp_points* a, gpp_points* b) {
     if(!a || !b) invalid("points is NULL");
@@ -217,7 +213,7 @@ extern "C" int gpp_count(gpp_points* from, gpp_points* to, float radius, float* 
     if(!out) invalid("out is NULL");
     OutField o;
     o.bind(out, nq, mem);
-    if(from->n == 0) hipLaunchKernelGGL(k_fill_value, dim3((nq + 255) / 256), dim3(256), 0, stream(), o.d, (size_t)nq, 0.0f);
+    if(from->n == 0) fill_f32(o.d, (size_t)nq, 0.0f);
     else {
         to->to_device();
         gpp_obs_index* ix = gpp_build_obs_index(from);
@@ -248,8 +244,7 @@ extern "C" int gpp_gridding(gpp_points* to, gpp_points* from, const float* value
     DevBuf<float> val;
     if(from->n == 0) {   // every neighbour list is empty: calc_statistic of nothing (0 for Count, NaN otherwise), NaN if min_num > 0
         const float v = (min_num <= 0 && statistic == GPP_COUNT) ? 0.0f : NAN;
-        hipLaunchKernelGGL(k_fill_value, dim3((nq + 255) / 256), dim3(256), 0, stream(), o.d, (size_t)nq, v);
-        GPP_HIP(hipGetLastError());
+        fill_f32(o.d, (size_t)nq, v);
     }
     else {
         if(!values) invalid("values is NULL");
@@ -307,8 +302,7 @@ extern "C" int gpp_gridding(gpp_points* to, gpp_points* from, const float* value
 void gpp_gridding_nearest_device(gpp_points* to, gpp_points* from, const float* d_values, int min_num, int statistic, float* d_out) {
     const int no = to->n, S = from->n;
     if(S == 0) {
-        hipLaunchKernelGGL(k_fill_value, dim3((no + 255) / 256), dim3(256), 0, stream(), d_out, (size_t)no, NAN);
-        GPP_HIP(hipGetLastError());
+        fill_f32(d_out, (size_t)no, NAN);
         return;
     }
     from->to_device();
@@ -572,7 +566,7 @@ extern "C" int gpp_distance(gpp_points* from, gpp_points* to, int num, int query
     OutField o;
     o.bind(out, nq, mem);
     const int k = std::max(0, std::min(num, from->n));
-    if(k == 0) hipLaunchKernelGGL(k_fill_value, dim3((nq + 255) / 256), dim3(256), 0, stream(), o.d, (size_t)nq, 0.0f);
+    if(k == 0) fill_f32(o.d, (size_t)nq, 0.0f);
     else {
         to->to_device(); to->latlon_to_device();
         from->latlon_to_device();
@@ -762,8 +756,7 @@ extern "C" int gpp_smart(gpp_points* igrid, gpp_points* ogrid, const float* valu
     OutField o;
     o.bind(out, nq, mem);
     if(igrid->n == 0 || num <= 0) {   // no candidate / nothing kept: count == 0 (smart.cpp:59-61)
-        hipLaunchKernelGGL(k_fill_value, dim3((nq + 255) / 256), dim3(256), 0, stream(), o.d, (size_t)nq, NAN);
-        GPP_HIP(hipGetLastError());
+        fill_f32(o.d, (size_t)nq, NAN);
         o.finish();
         GPP_HIP(hipStreamSynchronize(stream()));
         return GPP_OK;

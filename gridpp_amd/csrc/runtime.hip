@@ -1,4 +1,4 @@
-// Runtime, point sets and neighbour queries of libgridpp_hip.so.
+// Runtime, point sets and neighbour queries of libgridpp_hip.so, and fill_f32 (common.h), the library's one fill-with-a-value kernel.
 #include "oi_common.h"
 #include <algorithm>
 #include <thread>
@@ -454,9 +454,14 @@ gpp_points::~gpp_points() {
     if(nn_index) gpp_free_nn_index(nn_index);
 }
 
-__global__ void k_fill_f(float* out, int n, float v) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void k_fill_f32(float* out, size_t n, float v) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(i < n) out[i] = v;
+}
+void gpp::fill_f32(float* d, size_t n, float v) {
+    if(n == 0) return;
+    hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), d, n, v);
+    GPP_HIP(hipGetLastError());
 }
 template <class T>
 static gpp_points* make_points(const T* lats, const T* lons, const T* elevs, const T* lafs, int n, int ny, int nx, int type) {
@@ -491,9 +496,9 @@ static gpp_points* make_points(const T* lats, const T* lons, const T* elevs, con
     if(done) {
         p->host_fields = false;
         if(elevs) upload_as_float(p->d_elev, elevs, n);
-        else { p->d_elev.get(n); hipLaunchKernelGGL(k_fill_f, dim3((n + 255) / 256), dim3(256), 0, stream(), p->d_elev.p, n, NAN); }
+        else fill_f32(p->d_elev.get(n), n, NAN);
         if(lafs) upload_as_float(p->d_laf, lafs, n);
-        else { p->d_laf.get(n); hipLaunchKernelGGL(k_fill_f, dim3((n + 255) / 256), dim3(256), 0, stream(), p->d_laf.p, n, NAN); }
+        else fill_f32(p->d_laf.get(n), n, NAN);
         GPP_HIP(hipGetLastError());
         GPP_HIP(hipStreamSynchronize(stream()));   // the caller's arrays may go away after this call
         p->on_device = true;
@@ -709,10 +714,6 @@ __global__ void k_gather(const float* __restrict__ values, const int* __restrict
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i < n) out[i] = idx[i] >= 0 ? values[idx[i]] : NAN;
 }
-__global__ void k_fill(float* out, int n, float v) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = v;
-}
 
 // values [nt][n_from] -> out [nt][nq]: the index is looked up once per location, the levels are gathered with unit-stride
 // writes (nearest.cpp:47-66 makes the same split "because we do not want time to be the inner loop")
@@ -722,10 +723,6 @@ __global__ void k_gather_levels(const float* __restrict__ values, const int* __r
     if(i >= nq) return;
     const int j = idx[i];
     for(int t = 0; t < nt; ++t) out[(size_t)t * nq + i] = j >= 0 ? values[(size_t)t * nfrom + j] : NAN;
-}
-__global__ void k_fill_long(float* out, size_t n, float v) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) out[i] = v;
 }
 
 extern "C" int gpp_nearest_levels(gpp_points* from, gpp_points* to, const float* values, int nt, float* out, int mem) {
@@ -738,10 +735,7 @@ extern "C" int gpp_nearest_levels(gpp_points* from, gpp_points* to, const float*
     const size_t nout = (size_t)nt * nq;
     OutField o;
     o.bind(out, nout, mem);
-    if(from->n == 0) {   // nearest.cpp:132-134
-        hipLaunchKernelGGL(k_fill_long, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, stream(), o.d, nout, NAN);
-        GPP_HIP(hipGetLastError());
-    }
+    if(from->n == 0) fill_f32(o.d, nout, NAN);   // nearest.cpp:132-134
     else {
         if(!values) invalid("values is NULL");
         InField v;

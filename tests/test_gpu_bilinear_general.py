@@ -1,5 +1,6 @@
 """bilinear and the Bilinear downscalers where every box is a general quadrilateral: k_bilinear (gridpp_amd/csrc/bilinear.hip) and
-k_downscale<true> (downscale.hip) through weights_general of bilinear_geom.h, on the cases of tests/bilinear_cases.py.
+k_downscale<true> (downscale.hip), both through the direct locator of downscale_loc.h and weights_general of bilinear_geom.h, on the
+cases of tests/bilinear_cases.py.
 tests/test_bilinear_cases_oracle.py asserts on the CPU that those cases take all three branches and both roots of the solve and
 that the oracle agrees with a float64 Newton inversion; here the device is compared with the oracle (a few float32 ulps of the
 largest value, almost all outputs bit-identical), with the Newton inversion itself, and with the oracle's box search.

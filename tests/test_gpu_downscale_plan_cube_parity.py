@@ -1,5 +1,6 @@
 """The cube-layout gradients of the reusable downscaling plan (DownscalingPlan.simple_gradient_cube / full_gradient_cube,
-k_plan_gradient_cube of gridpp_amd/csrc/downscale_plan.hip) against the direct simple_gradient / full_gradient on the np.moveaxis-ed
+k_plan_gradient_cube of gridpp_amd/csrc/downscale_plan.hip, the gradient terms of downscale_loc.h on a planned locator) against the
+direct simple_gradient / full_gradient (k_downscale: the same terms on a direct locator) on the np.moveaxis-ed
 (E, Y, X) arrays, a gradient shared by the members repeated per level: bit for bit, and raising "Problem with bilinear interpolation"
 exactly where the direct call raises.  The direct calls are pinned to the oracle by tests/test_gpu_downscaling_parity.py."""
 import functools

@@ -2,7 +2,7 @@
 float32 composition of tests/downscaling_ref.py: every field downscaled on its own, then combined.
 
 Nearest is bit-exact against the composition built on the oracle.  Bilinear is bit-exact against the composition built on
-the library's own bilinear / nearest (the fused kernel runs the same float expressions), and against the oracle within
+the library's own bilinear / nearest (the fused kernel runs the same d(f), downscale_loc.h), and against the oracle within
 a bound that scales with the magnitudes involved: the 1e-6 relative tolerance of test_gpu_bilinear_parity.py applies
 to each interpolated field, and a difference of elevations carries it as an absolute error."""
 import numpy as np
@@ -217,6 +217,43 @@ def test_missing_data():
     # an empty input grid gives all NaN
     out = gridpp.full_gradient(gridpp.Grid(), c.out, np.zeros((3, 0, 0)), [], [], gridpp.Bilinear)
     assert out.shape == (3, c.qlats.size) and np.all(np.isnan(out))
+
+
+def test_empty_input_grid_and_no_levels():
+    """what the entries do before any kernel of theirs runs: a 0 x 0 input grid gives all NaN (nearest.cpp:132-134,
+    bilinear.cpp:37-39: every sum with a missing value is missing), no levels give an empty array"""
+    import gridpp_amd as gridpp
+    rng = np.random.default_rng(12)
+    five = gridpp.Points(50 + rng.random(5), 5 + rng.random(5), rng.uniform(0, 800, 5), rng.random(5))
+    seven = gridpp.Points(50 + 2 * rng.random(7), 5 + 3 * rng.random(7), rng.uniform(0, 800, 7), rng.random(7))
+    lats, lons = _mesh("regular", 3, 4)
+    grid = gridpp.Grid(lats, lons, rng.uniform(0, 800, (3, 4)), rng.random((3, 4)))
+    empty, none = np.zeros((3, 0, 0), F32), np.zeros((0, 3, 4), F32)
+    for ds in (gridpp.Nearest, gridpp.Bilinear):
+        for out in (gridpp.simple_gradient(gridpp.Grid(), five, empty, -0.0065, ds), gridpp.full_gradient(gridpp.Grid(), five, empty, empty, empty, ds),
+                    gridpp.downscaling(gridpp.Grid(), five, empty, ds)):
+            assert out.shape == (3, 5) and out.dtype == F32 and np.all(np.isnan(out))
+        for out in (gridpp.simple_gradient(grid, seven, none, -0.0065, ds), gridpp.full_gradient(grid, seven, none, none, none, ds),
+                    gridpp.full_gradient(grid, seven, none, [], [], ds), gridpp.downscaling(grid, seven, none, ds)):
+            assert out.shape == (0, 7) and out.dtype == F32
+
+
+def test_null_output_is_an_argument_error_at_the_c_entries():
+    """the shared call shell refuses a NULL `out` before anything is launched, for the direct entries as for those of a plan"""
+    import gridpp_amd as gridpp
+    from gridpp_amd import _capi
+    lib = _capi.lib()
+    lats, lons = _mesh("regular", 3, 4)
+    grid = gridpp.Grid(lats, lons, np.ones((3, 4)), np.ones((3, 4)))
+    pts = gridpp.Points([50.5, 51.0], [5.5, 7.0], [1, 2], [0.5, 0.5])
+    v = np.ones((1, 3, 4), F32)
+    calls = [lambda: lib.gpp_bilinear(grid._h, pts._h, v.ctypes.data, 1, None, _capi.MEM_HOST)]
+    for ds in (0, 1):
+        calls.append(lambda ds=ds: lib.gpp_simple_gradient(grid._h, pts._h, v.ctypes.data, 1, -0.0065, ds, None, _capi.MEM_HOST))
+        calls.append(lambda ds=ds: lib.gpp_full_gradient(grid._h, pts._h, v.ctypes.data, 1, None, None, ds, None, _capi.MEM_HOST))
+    for call in calls:
+        assert call() == _capi.GPP_EINVAL
+        assert lib.gpp_last_error().decode() == "out is NULL"
 
 
 def test_distorted_box_raises_where_bilinear_raises():

@@ -1,6 +1,7 @@
 """simple_gradient / full_gradient, 1000 x 1000 grid -> 4000 x 4000 grid, Nearest / Bilinear, T = 1 and 24: one JSON line per case.
 
   fused_ms     the library call on torch tensors (device path), hipEvents on the torch stream around warmed calls, median
+               (fused_min_ms / fused_max_ms: the extremes of the timed samples; their difference is the spread of the measurement)
   composed_ms  the same result composed as the reference builds it (src/api/gradient.cpp:26-81): the existing nearest / bilinear on
                the stacked fields (values, gradients, elevations, lafs; T (1 or 3) + 2 levels), then a torch elementwise pass --
                measured in the same process, alternated with the fused call (the stacking itself is not timed)
@@ -114,6 +115,7 @@ for fn in ("simple", "full"):
                 th.append((time.perf_counter() - t0) * 1e3)
             f_ms = float(np.median(tf))
             print(json.dumps({"case": name, "grid": "%d^2 -> %d^2" % (NI, NO), "T": T, "fused_ms": round(f_ms, 3),
+                              "fused_min_ms": round(min(tf), 3), "fused_max_ms": round(max(tf), 3),
                               "composed_ms": round(float(np.median(tc)), 3), "speedup": round(float(np.median(tc)) / f_ms, 2),
                               "bytes": nbytes, "GBps": round(nbytes / f_ms / 1e6, 1), "share_of_8TBps": round(nbytes / PEAK / (f_ms / 1e3), 3),
                               "host_ms": round(float(np.median(th)), 2), "bit_equal_to_composed": same, "reps": args.reps}), flush=True)

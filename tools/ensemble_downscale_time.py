@@ -2,6 +2,7 @@
 timing of smart: one JSON line per case.
 
   fused_ms        the library call on torch tensors (device path), hipEvents on the torch stream around warmed calls, median
+                  (fused_min_ms / fused_max_ms: the extremes of the timed samples; their difference is the spread of the measurement)
   composed_ms     the same product composed from what the library had before these entry points: `nearest` of the field
                   arange(Y X) for the index (exact below 2^24 cells), then gather + compare + reduce in torch -- measured in the
                   same process, alternated with the fused call.  The composed Mean sums in torch's order and the composed Median is
@@ -104,6 +105,7 @@ for NI in (1000, 4000):
         dbytes = distinct * 4 * E * ncubes + NO * NO * 16
         rbytes = NO * NO * 4 * E * ncubes + NO * NO * 16
         print(json.dumps({"case": case, "grid": "%d^2 x %d -> %d^2" % (NI, E, NO), "fused_ms": round(f_ms, 3), "composed_ms": round(c_ms, 3),
+                          "fused_min_ms": round(min(tf), 3), "fused_max_ms": round(max(tf), 3),
                           "speedup": round(c_ms / f_ms, 2), "distinct_cells": distinct, "distinct_bytes": dbytes, "requested_bytes": rbytes,
                           "share_of_8TBps_distinct": round(dbytes / PEAK / (f_ms / 1e3), 3),
                           "share_of_8TBps_requested": round(rbytes / PEAK / (f_ms / 1e3), 3),
