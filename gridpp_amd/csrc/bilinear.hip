@@ -78,8 +78,7 @@ extern "C" int gpp_bilinear(gpp_points* igrid, gpp_points* to, const float* valu
     DevBuf<int> idx;
     idx.get(nq);
     gpp_nearest_device(igrid, to->d_x.p, to->d_y.p, to->d_z.p, nq, 1, idx.p);
-    hipLaunchKernelGGL(k_bilinear, dim3((nq + 255) / 256), dim3(256), 0, stream(), igrid->d_lat.p, igrid->d_lon.p, igrid->ny, igrid->nx,
-                       idx.p, to->d_lat.p, to->d_lon.p, nq, v.d, nt, call.o.d, call.err);
+    launch(k_bilinear, blocks_of(nq), 256, 0, igrid->d_lat.p, igrid->d_lon.p, igrid->ny, igrid->nx, idx.p, to->d_lat.p, to->d_lon.p, nq, v.d, nt, call.o.d, call.err);
     call.finish();
     return GPP_OK;
     GPP_CATCH
@@ -104,9 +103,7 @@ extern "C" int gpp_grid_get_box(gpp_points* grid, const float* qlats, const floa
     idx.get(nq); box.get((size_t)5 * nq);
     grid->latlon_to_device();
     gpp_nearest_device(grid, dx.p, dy.p, dz.p, nq, 1, idx.p);
-    hipLaunchKernelGGL(k_get_box, dim3((nq + 255) / 256), dim3(256), 0, stream(), grid->d_lat.p, grid->d_lon.p, grid->ny, grid->nx, idx.p,
-                       dlat.p, dlon.p, nq, box.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_get_box, blocks_of(nq), 256, 0, grid->d_lat.p, grid->d_lon.p, grid->ny, grid->nx, idx.p, dlat.p, dlon.p, nq, box.p);
     std::vector<int> h((size_t)5 * nq);
     GPP_HIP(hipMemcpyAsync(h.data(), box.p, sizeof(int) * h.size(), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));
@@ -126,8 +123,7 @@ extern "C" int gpp_point_in_rectangle(const float corners_latlon[8], float lat, 
     DevBuf<int> r;
     d.upload(h, 10);
     r.get(1);
-    hipLaunchKernelGGL(k_in_rectangle, dim3(1), dim3(1), 0, stream(), d.p, r.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_in_rectangle, 1, 1, 0, d.p, r.p);
     GPP_HIP(hipMemcpyAsync(inside, r.p, sizeof(int), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));
     return GPP_OK;

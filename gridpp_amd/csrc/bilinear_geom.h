@@ -4,8 +4,7 @@
 // (the build has -ffp-contract=off and correctly rounded float divide).  Internal linkage: each translation unit has
 // its own device code object.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cmath>
+#include "common.h"
 
 namespace {
 
@@ -113,8 +112,6 @@ __device__ bool weights(float x, float y, float x0, float x1, float x2, float x3
     if(s <= 0 && (double)s >= -0.15) s = 0;
     return !(s >= 0 && s <= 1 && t >= 0 && t <= 1);
 }
-
-__device__ __forceinline__ bool dev_valid(float v) { return !isnan(v) && !isinf(v); }
 
 // bilinear.cpp:137-153 with the corners as get_box names them: v0 = (Y1, X1), v1 = (Y2, X1), v2 = (Y1, X2), v3 = (Y2, X2)
 __device__ __forceinline__ float bilinear_value(float v0, float v1, float v2, float v3, float s, float t) {

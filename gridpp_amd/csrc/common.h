@@ -70,6 +70,24 @@ hipStream_t stream3();  // and a third (status copies of deferred calls)
 hipStream_t stream2();  // a second one: work that runs BESIDE the library stream inside one call (ordered against it with events)
 void ensure_device();   // throws GPP_ENODEVICE when no GPU is visible
 
+// ---- launches ------------------------------------------------------------------
+// The one way to start a kernel: on the library stream (launch) or on a given one (launch_on), the launch error checked at once.  The kernel's parameter pack
+// is deduced from the function pointer and the arguments are passed on as they are, so they convert at the call as they would in kernel<<<...>>>(args...)
+// (int -> long, T* -> const T*; a literal 0 is an int by then: write (const float*)nullptr).
+template <class... P, class... A>
+inline void launch_on(hipStream_t s, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, A&&... args) {
+    kernel<<<grid, block, lds_bytes, s>>>(static_cast<A&&>(args)...);
+    GPP_HIP(hipGetLastError());
+}
+template <class... P, class... A>
+inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, A&&... args) {
+    launch_on(stream(), kernel, grid, block, lds_bytes, static_cast<A&&>(args)...);
+}
+inline size_t blocks_of(size_t n, size_t per = 256) { return (n + per - 1) / per; }                     // the flat grid of n items
+inline unsigned grid_capped(size_t items, size_t cap) { return (unsigned)(items < cap ? items : cap); }   // the grid of a kernel that strides over it beyond `cap`
+inline unsigned magic_div(int d) { return (unsigned)((1ull << 32) / (unsigned)d + 1); }                   // x / d == umulhi(x, magic_div(d)) for the small x of a tile (not for d == 1, where it does not fit)
+inline int pow2_at_least(int len) { int p = 2; while(p < len) p <<= 1; return p; }                        // the padded length of a bitonic network: a power of two >= len, at least 2
+
 void stage_release_all();   // (runtime.hip: the pool of staging buffers, see Staged below)
 template <class T>
 struct DevBuf {   // owning HBM buffer, grows on demand, never shrinks
@@ -162,8 +180,7 @@ struct InField {
             Staged<double> wide;
             wide.upload(reinterpret_cast<const double*>(src), n);
             staged.get(n);
-            if(n) hipLaunchKernelGGL(k_stage_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), wide.p, n, staged.p);
-            GPP_HIP(hipGetLastError());
+            if(n) launch(k_stage_f64, blocks_of(n), 256, 0, wide.p, n, staged.p);
             GPP_HIP(hipStreamSynchronize(stream()));   // `wide` is released here
             d = staged.p;
         }
@@ -190,12 +207,30 @@ struct OutArray {
 using OutField = OutArray<float>;
 using OutInts = OutArray<int>;   // the ranks of gpp_calc_ranks
 
+// The tail of an entry point: every bound output on its way back (in argument order), the library stream drained (staging buffers go back to the pool after it)
+template <class... O>
+inline int finish_call(O&... outs) {
+    (outs.finish(), ...);
+    GPP_HIP(hipStreamSynchronize(stream()));
+    return GPP_OK;
+}
+
 // runtime.hip: d[0 .. n) = v on the library stream (the one fill kernel of the library)
 void fill_f32(float* d, size_t n, float v);
 
 inline bool is_valid(float v) { return !std::isnan(v) && !std::isinf(v); }   // src/api/util.cpp:16-18
 
 }   // namespace gpp
+
+// ---- device helpers -------------------------------------------------------------
+__device__ __forceinline__ bool dev_valid(float v) { return !isnan(v) && !isinf(v); }   // src/api/util.cpp:16-18
+// A workgroup barrier that orders LDS accesses only.  __syncthreads also waits for every global load and store of the wave; the call sites say what that would
+// stall in their kernel.
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 
 // ---- point set ---------------------------------------------------------------
 struct gpp_obs_index;   // oi.hip: bin-sorted observation block

@@ -200,8 +200,7 @@ void launch_shared(const float* in, long long nvec, const float* cx, const float
     const long long cap = (long long)compute_units() * 2;
     const unsigned blocks = (unsigned)std::min(want, cap);
     const size_t lds = LDS ? (size_t)2 * nc * sizeof(float) : 0;
-    hipLaunchKernelGGL((k_curve_shared<LDS, VEC>), dim3(blocks), dim3(SHARED_BLOCK), lds, stream(), in, nvec, cx, cy, nc, pb, pa, sorted, interp, out);
-    GPP_HIP(hipGetLastError());
+    launch(k_curve_shared<LDS, VEC>, blocks, SHARED_BLOCK, lds, in, nvec, cx, cy, nc, pb, pa, sorted, interp, out);
 }
 
 // values `in` (n of them, `mem`) through the host curve (cx -> cy): apply_curve (interp = 0: cx = curve_fcst, cy = curve_ref) or interpolate
@@ -229,14 +228,13 @@ void run_shared(const float* in, long long n, const float* cx, const float* cy, 
         launch_shared<false, 4>(v.d, n4, c.p, c.p + nc, nc, pb, pa, sorted, interp, o.d);
         launch_shared<false, 1>(v.d + 4 * n4, n - 4 * n4, c.p, c.p + nc, nc, pb, pa, sorted, interp, o.d + 4 * n4);
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
+    finish_call(o);
 }
 
 template <int G, int W>
 void launch_field(const float* in, const float* ref, const float* fcst, long long ncell, int nc, int pb, int pa, float* out) {
-    const long long blocks = (ncell * G + 255) / 256;
-    hipLaunchKernelGGL((k_apply_curve_field<G, W>), dim3((unsigned)blocks), dim3(256), 0, stream(), in, ref, fcst, ncell, nc, pb, pa, out);
+    const long long blocks = blocks_of(ncell * G);
+    launch(k_apply_curve_field<G, W>, (unsigned)blocks, 256, 0, in, ref, fcst, ncell, nc, pb, pa, out);
 }
 template <int W>
 void launch_field_w(const float* in, const float* ref, const float* fcst, long long ncell, int nc, int pb, int pa, float* out) {
@@ -250,7 +248,6 @@ void launch_field_w(const float* in, const float* ref, const float* fcst, long l
         case 32: launch_field<32, W>(in, ref, fcst, ncell, nc, pb, pa, out); break;
         default: launch_field<64, W>(in, ref, fcst, ncell, nc, pb, pa, out); break;
     }
-    GPP_HIP(hipGetLastError());
 }
 
 }   // namespace
@@ -305,9 +302,7 @@ extern "C" int gpp_apply_curve_field(const float* fcst, const float* curve_ref, 
     if(nc % 4 == 0 && a % 16 == 0) launch_field_w<4>(v.d, r.d, f.d, ncell, nc, policy_below, policy_above, o.d);
     else if(nc % 2 == 0 && a % 8 == 0) launch_field_w<2>(v.d, r.d, f.d, ncell, nc, policy_below, policy_above, o.d);
     else launch_field_w<1>(v.d, r.d, f.d, ncell, nc, policy_below, policy_above, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 

@@ -72,9 +72,9 @@ void downscale(gpp_points* igrid, gpp_points* to, const float* values, int nt, c
     a.elev_gradient = elev_gradient;
     a.full = full;
     a.out = call.o.d; a.err = call.err;
-    const dim3 grid((nq + 255) / 256), block(256);
-    if(downscaler == 1) hipLaunchKernelGGL(k_downscale<true>, grid, block, 0, stream(), a);
-    else hipLaunchKernelGGL(k_downscale<false>, grid, block, 0, stream(), a);
+    const dim3 grid(blocks_of(nq)), block(256);
+    if(downscaler == 1) launch(k_downscale<true>, grid, block, 0, a);
+    else launch(k_downscale<false>, grid, block, 0, a);
     call.finish();
 }
 

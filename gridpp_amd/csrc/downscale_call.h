@@ -21,8 +21,7 @@ struct DownscaleCall {
         o.bind(out, nout, mem);
         if(n_in == 0) {
             fill_f32(o.d, nout, NAN);
-            o.finish();
-            GPP_HIP(hipStreamSynchronize(stream()));
+            finish_call(o);
             done = true;
             return;
         }
@@ -31,11 +30,9 @@ struct DownscaleCall {
         GPP_HIP(hipMemsetAsync(err, 0, 4 * sizeof(int), stream()));
     }
     void finish() {   // after the launch
-        GPP_HIP(hipGetLastError());
         int herr[4];
         GPP_HIP(hipMemcpyAsync(herr, err, sizeof(herr), hipMemcpyDeviceToHost, stream()));
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
+        finish_call(o);
         bilinear_check_distorted(herr);
     }
 };

@@ -217,9 +217,9 @@ void plan_gradient(gpp_downscale_plan* p, const float* values, int nt, const flo
     a.elev_gradient = elev_gradient;
     a.full = full;
     a.out = call.o.d; a.err = call.err;
-    const dim3 grid((p->nq + 255) / 256), block(256);
-    if(p->downscaler == 1) hipLaunchKernelGGL(k_plan_gradient<true>, grid, block, 0, stream(), a);
-    else hipLaunchKernelGGL(k_plan_gradient<false>, grid, block, 0, stream(), a);
+    const dim3 grid(blocks_of(p->nq)), block(256);
+    if(p->downscaler == 1) launch(k_plan_gradient<true>, grid, block, 0, a);
+    else launch(k_plan_gradient<false>, grid, block, 0, a);
     call.finish();
 }
 
@@ -255,9 +255,7 @@ extern "C" int gpp_downscale_plan_create(gpp_points* igrid, gpp_points* to, int 
             p->rec.get(nq);
             GPP_HIP(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), stream()));
             gpp_nearest_device(igrid, to->d_x.p, to->d_y.p, to->d_z.p, nq, 1, idx.p);
-            hipLaunchKernelGGL(k_plan_build, dim3((nq + 255) / 256), dim3(256), 0, stream(), igrid->d_lat.p, igrid->d_lon.p, igrid->ny, igrid->nx,
-                               idx.p, to->d_lat.p, to->d_lon.p, nq, p->rec.p, count.p);
-            GPP_HIP(hipGetLastError());
+            launch(k_plan_build, blocks_of(nq), 256, 0, igrid->d_lat.p, igrid->d_lon.p, igrid->ny, igrid->nx, idx.p, to->d_lat.p, to->d_lon.p, nq, p->rec.p, count.p);
             unsigned long long h = 0;
             GPP_HIP(hipMemcpyAsync(&h, count.p, sizeof(h), hipMemcpyDeviceToHost, stream()));
             GPP_HIP(hipStreamSynchronize(stream()));
@@ -301,13 +299,11 @@ extern "C" int gpp_downscale_plan_apply(gpp_downscale_plan* plan, const float* v
     if(call.done) return GPP_OK;
     InField v;
     v.bind(values, (size_t)nt * plan->n_in, mem);
-    const dim3 grid((plan->nq + 255) / 256), block(256);
+    const dim3 grid(blocks_of(plan->nq)), block(256);
     if(plan->downscaler == 1)
-        hipLaunchKernelGGL(k_plan_apply<true>, grid, block, 0, stream(), (const int4*)plan->rec.p, (const int*)nullptr, plan->nq, plan->nX, plan->n_in,
-                           v.d, nt, call.o.d, call.err);
+        launch(k_plan_apply<true>, grid, block, 0, (const int4*)plan->rec.p, (const int*)nullptr, plan->nq, plan->nX, plan->n_in, v.d, nt, call.o.d, call.err);
     else
-        hipLaunchKernelGGL(k_plan_apply<false>, grid, block, 0, stream(), (const int4*)nullptr, (const int*)plan->nn.p, plan->nq, plan->nX, plan->n_in,
-                           v.d, nt, call.o.d, call.err);
+        launch(k_plan_apply<false>, grid, block, 0, (const int4*)nullptr, (const int*)plan->nn.p, plan->nq, plan->nX, plan->n_in, v.d, nt, call.o.d, call.err);
     call.finish();
     return GPP_OK;
     GPP_CATCH
@@ -336,10 +332,10 @@ extern "C" int gpp_downscale_plan_apply_cube(gpp_downscale_plan* plan, const flo
     const int* nn = bil ? nullptr : plan->nn.p;
     dispatch_group(G, [&](auto g_) {
         constexpr int G_ = decltype(g_)::value;
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, stream(), rec, nn, plan->nq, plan->nX, v.d, ne, call.o.d, call.err); };
-        if(wide) launch(k_plan_apply_cube<true, G_, 2>);
-        else if(bil) launch(k_plan_apply_cube<true, G_, 1>);
-        else launch(k_plan_apply_cube<false, G_, 1>);
+        auto go = [&](auto kernel) { launch(kernel, grid, block, 0, rec, nn, plan->nq, plan->nX, v.d, ne, call.o.d, call.err); };
+        if(wide) go(k_plan_apply_cube<true, G_, 2>);
+        else if(bil) go(k_plan_apply_cube<true, G_, 1>);
+        else go(k_plan_apply_cube<false, G_, 1>);
     });
     call.finish();
     return GPP_OK;
@@ -400,10 +396,10 @@ void plan_gradient_cube(gpp_downscale_plan* p, const float* values, int ne, cons
     const dim3 grid((unsigned)blocks), block(256);
     dispatch_group(G, [&](auto g_) {
         constexpr int G_ = decltype(g_)::value;
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, stream(), a); };
-        if(wide) launch(pm ? k_plan_gradient_cube<true, G_, 2, true> : k_plan_gradient_cube<true, G_, 2, false>);
-        else if(bil) launch(pm ? k_plan_gradient_cube<true, G_, 1, true> : k_plan_gradient_cube<true, G_, 1, false>);
-        else launch(pm ? k_plan_gradient_cube<false, G_, 1, true> : k_plan_gradient_cube<false, G_, 1, false>);
+        auto go = [&](auto kernel) { launch(kernel, grid, block, 0, a); };
+        if(wide) go(pm ? k_plan_gradient_cube<true, G_, 2, true> : k_plan_gradient_cube<true, G_, 2, false>);
+        else if(bil) go(pm ? k_plan_gradient_cube<true, G_, 1, true> : k_plan_gradient_cube<true, G_, 1, false>);
+        else go(pm ? k_plan_gradient_cube<false, G_, 1, true> : k_plan_gradient_cube<false, G_, 1, false>);
     });
     call.finish();
 }
@@ -417,8 +413,7 @@ void check_ensemble_plan(gpp_downscale_plan* p) {
 const int* plan_nearest_index(gpp_downscale_plan* p) {
     if(!p->nn_ready) {   // a Bilinear plan: .x of its records, extracted once and kept (4 bytes per location, counted in bytes())
         p->nn.get(p->nq);
-        hipLaunchKernelGGL(k_plan_nearest_of_records, dim3((p->nq + 255) / 256), dim3(256), 0, stream(), (const int4*)p->rec.p, p->nq, p->nn.p);
-        GPP_HIP(hipGetLastError());
+        launch(k_plan_nearest_of_records, blocks_of(p->nq), 256, 0, (const int4*)p->rec.p, p->nq, p->nn.p);
         p->nn_ready = true;
     }
     return p->nn.p;

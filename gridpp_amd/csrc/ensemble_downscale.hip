@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_ens_probability(const int* __restrict__
         const float th = threshold[cell];
         for(int k = lane; k < E; k += G) {
             const float m = row[k];
-            if(nv(m)) { ++count; total += compare(m, th, op) ? 1 : 0; }
+            if(dev_valid(m)) { ++count; total += compare(m, th, op) ? 1 : 0; }
         }
     }
     count = group_sum<G>(count);
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void k_ens_probability(const int* __restrict__
 __device__ __forceinline__ float masked_member(const float* __restrict__ vt, const float* __restrict__ vf, const float* __restrict__ tv,
                                                size_t i, float th, int op) {
     const float t = tv[i];
-    if(!nv(t)) return NAN;
+    if(!dev_valid(t)) return NAN;
     return compare(t, th, op) ? vt[i] : vf[i];
 }
 
@@ -88,7 +88,7 @@ __device__ float row_result(const float* row, int n, int statistic, float quanti
     if(statistic == GPP_MEDIAN) return row_quantile(row, n, 0.5f);   // util.cpp:96-105
     if(statistic == GPP_RANDOMCHOICE) {   // util.cpp:74-95 uses rand(); any valid member is a correct draw
         int N = 0;
-        for(int i = 0; i < n; i++) if(nv(row[i])) N++;
+        for(int i = 0; i < n; i++) if(dev_valid(row[i])) N++;
         return N > 0 ? row_kth(row, n, (int)(cell_hash(cell, seed) % (unsigned)N)) : NAN;
     }
     return row_statistic(row, n, statistic);
@@ -102,12 +102,12 @@ __device__ __forceinline__ void group_kth2(const float* row, int n, int k0, int 
     unsigned b0 = 0, b1 = 0;
     for(int i = lane; i < n; i += G) {
         const float v = row[i];
-        if(!nv(v)) continue;
+        if(!dev_valid(v)) continue;
         const unsigned oi = f2ord(v);
         int rank = 0;
         for(int j = 0; j < n; j++) {
             const float w = row[j];
-            if(!nv(w)) continue;
+            if(!dev_valid(w)) continue;
             const unsigned oj = f2ord(w);
             rank += (oj < oi || (oj == oi && j < i)) ? 1 : 0;
         }
@@ -138,9 +138,9 @@ __global__ __launch_bounds__(256) void k_ens_mask(const int* __restrict__ nn, co
     const bool median = statistic == GPP_MEDIAN;
     const float q = median ? 0.5f : quantile;
     float value;
-    if((statistic == GPP_QUANTILE || median) && nv(q) && q != 0 && q != 1) {   // row_quantile (util.cpp:111-178) with the group
+    if((statistic == GPP_QUANTILE || median) && dev_valid(q) && q != 0 && q != 1) {   // row_quantile (util.cpp:111-178) with the group
         int N = 0;
-        for(int k = lane; k < n; k += G) N += nv(row[k]) ? 1 : 0;
+        for(int k = lane; k < n; k += G) N += dev_valid(row[k]) ? 1 : 0;
         N = group_sum<G>(N);
         value = NAN;
         if(N > 0) {   // (the same in every lane of the group)
@@ -175,8 +175,6 @@ __global__ __launch_bounds__(256) void k_ens_rows_result(const float* __restrict
     out[q0 + c] = row_result(scratch + (size_t)c * E, E, statistic, quantile, q0 + c, seed);
 }
 
-unsigned blocks_for(int nq, int G) { return (unsigned)(((long long)nq * G + 255) / 256); }
-
 // members the LDS row of a group of G lanes holds: the four per lane that group_of allows, the whole cap for the largest group
 constexpr int row_cap(int G) { return G == 64 ? GPP_ENSEMBLE_ROW_CAP : 4 * G; }
 
@@ -197,8 +195,7 @@ void check_ensemble(int ne, int op) {
 
 void fill(OutField& o, size_t n, float v) {
     fill_f32(o.d, n, v);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
+    finish_call(o);
 }
 
 void nearest_index(gpp_points* igrid, gpp_points* ogrid, DevBuf<int>& idx) {
@@ -238,11 +235,9 @@ void gpp::ensemble_probability(const NearestIndex& index, size_t n_in, int nq, c
     const int* idx = index();
     dispatch_group(group_of(ne), [&](auto g) {
         constexpr int G = decltype(g)::value;
-        hipLaunchKernelGGL(k_ens_probability<G>, dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, v.d, ne, th.d, nq, comparison_operator, o.d);
+        launch(k_ens_probability<G>, blocks_of((size_t)nq * G), 256, 0, idx, v.d, ne, th.d, nq, comparison_operator, o.d);
     });
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
+    finish_call(o);
 }
 
 void gpp::ensemble_mask_threshold(const NearestIndex& index, size_t n_in, int nq, const float* ivalues_true, const float* ivalues_false,
@@ -277,10 +272,8 @@ void gpp::ensemble_mask_threshold(const NearestIndex& index, size_t n_in, int nq
     if(ne <= GPP_ENSEMBLE_ROW_CAP) {
         dispatch_group(group_of(ne), [&](auto g) {
             constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((k_ens_mask<G, row_cap(G)>), dim3(blocks_for(nq, G)), dim3(256), 0, stream(), idx, vt.d, vf.d, tv.d, ne, th.d, nq,
-                               comparison_operator, statistic, quantile, seed, o.d);
+            launch(k_ens_mask<G, row_cap(G)>, blocks_of((size_t)nq * G), 256, 0, idx, vt.d, vf.d, tv.d, ne, th.d, nq, comparison_operator, statistic, quantile, seed, o.d);
         });
-        GPP_HIP(hipGetLastError());
     }
     else {   // slabs of at most 2^26 masked members (256 MiB)
         const int slab = (int)std::max<long long>(1, std::min<long long>(nq, slab_members() / ne));
@@ -288,15 +281,11 @@ void gpp::ensemble_mask_threshold(const NearestIndex& index, size_t n_in, int nq
         scratch.get((size_t)slab * ne);
         for(int q0 = 0; q0 < nq; q0 += slab) {
             const int nc = std::min(slab, nq - q0);
-            hipLaunchKernelGGL(k_ens_mask_rows, dim3((nc + 3) / 4), dim3(256), 0, stream(), idx, vt.d, vf.d, tv.d, ne, th.d, q0, nc,
-                               comparison_operator, scratch.p);
-            hipLaunchKernelGGL(k_ens_rows_result, dim3((nc + 255) / 256), dim3(256), 0, stream(), (const float*)scratch.p, ne, q0, nc, statistic,
-                               quantile, seed, o.d);
-            GPP_HIP(hipGetLastError());
+            launch(k_ens_mask_rows, (nc + 3) / 4, 256, 0, idx, vt.d, vf.d, tv.d, ne, th.d, q0, nc, comparison_operator, scratch.p);
+            launch(k_ens_rows_result, blocks_of(nc), 256, 0, (const float*)scratch.p, ne, q0, nc, statistic, quantile, seed, o.d);
         }
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
+    finish_call(o);
 }
 
 extern "C" int gpp_downscale_probability(gpp_points* igrid, gpp_points* ogrid, const float* values, int ne, const float* threshold,

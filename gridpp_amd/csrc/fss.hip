@@ -33,6 +33,7 @@
 // bk = 21, E <= 1925.  Lane sums are sums of non-negative terms that fit, and a sliding difference takes out only what was put in, so no lane
 // ever borrows from its neighbour.
 #include "common.h"
+#include "march_geom.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -57,12 +58,10 @@ constexpr int FS_RUN = 32;                          // outputs per thread of the
 constexpr int FS_TB = 8;                            // thresholds k_fss_count carries in registers
 constexpr int FS_EC = 16;                           // members of a cell that go through LDS together
 constexpr int FS_EP = FS_EC + 1;                    // pitch of a cell's members in LDS
-constexpr int FS_MAXBLOCKS = 2048;                  // workgroups of the general path's kernels
+constexpr int FS_MAXBLOCKS = 2048;                  // workgroups of the general path's kernels (of a field with cells: the entry point returns before them otherwise)
 static_assert(FS_C + 2 * FS_MAXHW <= FS_RING && (FS_RING & (FS_RING - 1)) == 0, "the ring holds every row that a pending output needs");
 static_assert(FS_C * FS_WT % FS_THREADS == 0 && FS_THREADS == 8 * FS_C && FS_THREADS == 4 * FS_W && FS_W == 64 && FS_C == 32, "thread layout");
 static_assert(FS_P % 2 == 1 && FS_RP % 2 == 1, "odd pitches");
-
-__device__ __forceinline__ bool dev_valid(float v) { return !isnan(v) && !isinf(v); }   // util.cpp:16-18
 
 // `v op t` for a valid v and a t that is no NaN: Gt as it stands, Lt with the sides swapped, Leq and Geq as the negation of those two
 __device__ __forceinline__ bool dev_raw(float v, float t, int swap) { return swap ? t > v : v > t; }
@@ -328,8 +327,6 @@ __global__ __launch_bounds__(256) void k_fss_reduce(const double* __restrict__ p
     }
 }
 
-unsigned grid_for(size_t items) { return (unsigned)std::min<size_t>(std::max<size_t>(items, 1), (size_t)FS_MAXBLOCKS); }
-
 // the widths of the march's lanes for this half width; false where the packed form does not hold (see the head of this file)
 bool packed_form(int hw, int E, int Y, int X, int* bk, int* bn) {
     if(hw > FS_MAXHW || E > 32767 || Y > (1 << 30) || X > (1 << 30)) return false;
@@ -354,18 +351,12 @@ struct FssCall {
 
     template <class CT>
     void count(const float* d_thr, int nt, bool first) {
-        const unsigned blocks = grid_for((C + 255) / 256);
-        for(int t0 = 0; t0 < nt; t0 += FS_TB) {
-            hipLaunchKernelGGL((k_fss_count<CT>), dim3(blocks), dim3(256), 0, stream(), fcst, ref, C, E, d_thr + t0, std::min(FS_TB, nt - t0), swap, neg,
-                               first && t0 == 0 ? 1 : 0, (CT*)mp.p, (CT*)kp.p + (size_t)t0 * C);
-            GPP_HIP(hipGetLastError());
-        }
+        for(int t0 = 0; t0 < nt; t0 += FS_TB)
+            launch(k_fss_count<CT>, grid_capped(blocks_of(C), FS_MAXBLOCKS), 256, 0, fcst, ref, C, E, d_thr + t0, std::min(FS_TB, nt - t0), swap, neg, first && t0 == 0 ? 1 : 0,
+                   (CT*)mp.p, (CT*)kp.p + (size_t)t0 * C);
     }
     void classify(const float* d_thr, int nt, bool first, bool is3d) {
-        if(!is3d) {
-            hipLaunchKernelGGL(k_fss_classify, dim3(grid_for((C + 255) / 256)), dim3(256), 0, stream(), fcst, ref, C, d_thr, nt, swap, neg, mp.p, kp.p);
-            GPP_HIP(hipGetLastError());
-        }
+        if(!is3d) launch(k_fss_classify, grid_capped(blocks_of(C), FS_MAXBLOCKS), 256, 0, fcst, ref, C, d_thr, nt, swap, neg, mp.p, kp.p);
         else if(ctb == 1) count<unsigned char>(d_thr, nt, first);
         else if(ctb == 2) count<unsigned short>(d_thr, nt, first);
         else count<unsigned>(d_thr, nt, first);
@@ -375,32 +366,24 @@ struct FssCall {
     size_t march(int hw, int nt, int bk, int bn) {
         const int strips = (X + FS_W - 1) / FS_W;
         const long fill = path_env("GPP_FSS_FILL") ? std::max(1, atoi(path_env("GPP_FSS_FILL"))) : 1024;   // (tests: workgroups per threshold the launch aims for)
-        const int segs = (int)std::max(1L, std::min((fill + strips - 1) / strips, (long)(Y + FS_C - 1) / FS_C));
-        int SH = ((Y + segs - 1) / segs + FS_C - 1) / FS_C * FS_C;
-        while((Y + SH - 1) / SH > 65535) SH += FS_C;
-        const int nseg = (Y + SH - 1) / SH;
-        const size_t nblk = (size_t)strips * nseg;
+        const MarchSegments sg = march_segments(Y, FS_C, std::max(1L, (fill + strips - 1) / strips));
+        const size_t nblk = (size_t)strips * sg.segs;
         parts.get(2 * nblk * nt);
         pcnt.get(nblk);
-        hipLaunchKernelGGL((k_fss_march<CT>), dim3(strips, nseg, nt), dim3(FS_THREADS), 0, stream(), (const CT*)mp.p, (const CT*)kp.p, C, Y, X, hw, SH, bk, bn,
-                           parts.p, parts.p + nblk * nt, pcnt.p);
-        GPP_HIP(hipGetLastError());
+        launch(k_fss_march<CT>, dim3(strips, sg.segs, nt), FS_THREADS, 0, (const CT*)mp.p, (const CT*)kp.p, C, Y, X, hw, sg.SH, bk, bn, parts.p, parts.p + nblk * nt, pcnt.p);
         return nblk;
     }
 
     template <class CT, class RT>
     size_t general(long long hw, int nt) {
-        const size_t nblk = grid_for(((size_t)X * (((size_t)Y + FS_RUN - 1) / FS_RUN) + 255) / 256);
+        const size_t nblk = grid_capped(blocks_of((size_t)X * (((size_t)Y + FS_RUN - 1) / FS_RUN)), FS_MAXBLOCKS);
         parts.get(2 * nblk * nt);
         pcnt.get(nblk);
         rows.get(C * sizeof(FsRow<RT>));
         for(int t = 0; t < nt; t++) {
-            hipLaunchKernelGGL((k_fss_rows<CT, RT>), dim3(grid_for(((size_t)Y * (((size_t)X + FS_RUN - 1) / FS_RUN) + 255) / 256)), dim3(256), 0, stream(),
-                               (const CT*)mp.p, (const CT*)kp.p + (size_t)t * C, Y, X, hw, (FsRow<RT>*)rows.p);
-            GPP_HIP(hipGetLastError());
-            hipLaunchKernelGGL((k_fss_cols<RT>), dim3((unsigned)nblk), dim3(256), 0, stream(), (const FsRow<RT>*)rows.p, Y, X, hw, (size_t)t * nblk, parts.p,
-                               parts.p + nblk * nt, t == 0 ? pcnt.p : (u64*)nullptr);
-            GPP_HIP(hipGetLastError());
+            launch(k_fss_rows<CT, RT>, grid_capped(blocks_of((size_t)Y * (((size_t)X + FS_RUN - 1) / FS_RUN)), FS_MAXBLOCKS), 256, 0, (const CT*)mp.p,
+                   (const CT*)kp.p + (size_t)t * C, Y, X, hw, (FsRow<RT>*)rows.p);
+            launch(k_fss_cols<RT>, (unsigned)nblk, 256, 0, (const FsRow<RT>*)rows.p, Y, X, hw, (size_t)t * nblk, parts.p, parts.p + nblk * nt, t == 0 ? pcnt.p : (u64*)nullptr);
         }
         return nblk;
     }
@@ -419,9 +402,7 @@ struct FssCall {
             const bool wide = (force && !strcmp(force, "wide")) || (u64)std::min<long long>(2 * hw + 1, X) * (u64)E >= (1ull << 32);
             nblk = ctb == 1 ? general_ct<unsigned char>(hw, nt, wide) : ctb == 2 ? general_ct<unsigned short>(hw, nt, wide) : general_ct<unsigned>(hw, nt, wide);
         }
-        hipLaunchKernelGGL(k_fss_reduce, dim3(nt), dim3(256), 0, stream(), (const double*)parts.p, (const double*)(parts.p + nblk * nt), (const u64*)pcnt.p, nblk,
-                           d_fbs, d_worst, stride, d_cells);
-        GPP_HIP(hipGetLastError());
+        launch(k_fss_reduce, nt, 256, 0, (const double*)parts.p, (const double*)(parts.p + nblk * nt), (const u64*)pcnt.p, nblk, d_fbs, d_worst, stride, d_cells);
     }
 };
 

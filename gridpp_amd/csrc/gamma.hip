@@ -54,11 +54,6 @@ struct GammaWorkspace {
 };
 thread_local GammaWorkspace g_gamma;
 
-unsigned blocks_for(long long n) {
-    const long long want = (n + GPP_GAMMA_BLOCK - 1) / GPP_GAMMA_BLOCK;
-    return (unsigned)(want < GPP_GAMMA_MAX_BLOCKS ? want : GPP_GAMMA_MAX_BLOCKS);
-}
-
 // the inputs of a call (`mem`) as device pointers: the caller's, or staged float32 / float64 copies
 template <int NIN>
 struct DeviceInputs {
@@ -127,9 +122,9 @@ extern "C" int gpp_gamma_inv(const float* levels, const float* shape, const floa
     o.bind(out, (size_t)n, mem);
     unsigned long long* status = g_gamma.status.get(1);
     GPP_HIP(hipMemsetAsync(status, 0xFF, sizeof(unsigned long long), stream()));
-    if(in.f64) hipLaunchKernelGGL(k_gamma_inv<true>, dim3(blocks_for(n)), dim3(GPP_GAMMA_BLOCK), 0, stream(), in.p[0], in.p[1], in.p[2], n, o.d, status);
-    else hipLaunchKernelGGL(k_gamma_inv<false>, dim3(blocks_for(n)), dim3(GPP_GAMMA_BLOCK), 0, stream(), in.p[0], in.p[1], in.p[2], n, o.d, status);
-    GPP_HIP(hipGetLastError());
+    const unsigned grid = grid_capped(blocks_of(n, GPP_GAMMA_BLOCK), GPP_GAMMA_MAX_BLOCKS);
+    if(in.f64) launch(k_gamma_inv<true>, grid, GPP_GAMMA_BLOCK, 0, in.p[0], in.p[1], in.p[2], n, o.d, status);
+    else launch(k_gamma_inv<false>, grid, GPP_GAMMA_BLOCK, 0, in.p[0], in.p[1], in.p[2], n, o.d, status);
     o.finish();
     unsigned long long word = ~0ull;
     GPP_HIP(hipMemcpyAsync(&word, status, sizeof(word), hipMemcpyDeviceToHost, stream()));
@@ -152,19 +147,16 @@ extern "C" int gpp_gamma_transform(const float* in, long long n, int backward, f
     DeviceInputs<1> src(arrays, n, mem);
     OutField o;
     o.bind(out, (size_t)n, mem);
-    const dim3 grid(blocks_for(n)), block(GPP_GAMMA_BLOCK);
+    const dim3 grid(grid_capped(blocks_of(n, GPP_GAMMA_BLOCK), GPP_GAMMA_MAX_BLOCKS)), block(GPP_GAMMA_BLOCK);
     if(backward) {
-        if(src.f64) hipLaunchKernelGGL((k_gamma_transform<true, true>), grid, block, 0, stream(), src.p[0], n, g, o.d);
-        else hipLaunchKernelGGL((k_gamma_transform<true, false>), grid, block, 0, stream(), src.p[0], n, g, o.d);
+        if(src.f64) launch(k_gamma_transform<true, true>, grid, block, 0, src.p[0], n, g, o.d);
+        else launch(k_gamma_transform<true, false>, grid, block, 0, src.p[0], n, g, o.d);
     }
     else {
-        if(src.f64) hipLaunchKernelGGL((k_gamma_transform<false, true>), grid, block, 0, stream(), src.p[0], n, g, o.d);
-        else hipLaunchKernelGGL((k_gamma_transform<false, false>), grid, block, 0, stream(), src.p[0], n, g, o.d);
+        if(src.f64) launch(k_gamma_transform<false, true>, grid, block, 0, src.p[0], n, g, o.d);
+        else launch(k_gamma_transform<false, false>, grid, block, 0, src.p[0], n, g, o.d);
     }
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 

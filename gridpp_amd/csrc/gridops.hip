@@ -20,8 +20,6 @@ using namespace gpp;
 
 namespace {
 
-__device__ __forceinline__ bool gv(float v) { return !isnan(v) && !isinf(v); }
-
 struct GridIx {
     const float4* sgeo;
     const float2* smeta;
@@ -119,8 +117,8 @@ __global__ void k_fill_missing_lines(const float* __restrict__ v, int Y, int X, 
     for(int k = 0; k < len; ++k) {
         const float curr = v[base + k * step];
         float r = NAN;
-        if(!gv(curr)) {
-            if(next < k) for(next = k; next < len; ++next) if(gv(v[base + next * step])) break;
+        if(!dev_valid(curr)) {
+            if(next < k) for(next = k; next < len; ++next) if(dev_valid(v[base + next * step])) break;
             if(next < len) {
                 const float vl = v[base + last * step], vn = v[base + next * step];
                 r = (vl) + (vn - vl) * (float)(k - last) / (float)(next - last);
@@ -144,7 +142,7 @@ __global__ __launch_bounds__(256) void k_fill_missing_rows(const float* __restri
     __syncthreads();
     const int seg = (X + 255) / 256, i0 = tid * seg, i1 = min(i0 + seg, X);
     int sl = -1, sf = 0x7fffffff;
-    for(int i = i0; i < i1; ++i) if(gv(s_v[i])) { sl = i; if(sf == 0x7fffffff) sf = i; }
+    for(int i = i0; i < i1; ++i) if(dev_valid(s_v[i])) { sl = i; if(sf == 0x7fffffff) sf = i; }
     s_last[tid] = sl; s_first[tid] = sf;
     __syncthreads();
     // exclusive prefix max of s_last, exclusive suffix min of s_first (256 entries: one short loop per thread)
@@ -152,13 +150,13 @@ __global__ __launch_bounds__(256) void k_fill_missing_rows(const float* __restri
     for(int t = 0; t < tid; ++t) before = max(before, s_last[t]);
     for(int t = tid + 1; t < 256; ++t) after = min(after, s_first[t]);
     int nx = after;
-    for(int i = i1 - 1; i >= i0; --i) { if(gv(s_v[i])) nx = i; s_next[i] = nx; }
+    for(int i = i1 - 1; i >= i0; --i) { if(dev_valid(s_v[i])) nx = i; s_next[i] = nx; }
     int last = before < 0 ? 0 : before;   // fill.cpp:49,86: `last` starts at 0 whether or not that element is valid
     float* orow = res + (size_t)y * X;
     for(int i = i0; i < i1; ++i) {
         const float curr = s_v[i];
         float r = NAN;
-        if(!gv(curr)) {
+        if(!dev_valid(curr)) {
             const int next = s_next[i];
             if(next < X) {
                 const float vl = s_v[last], vn = s_v[next];
@@ -183,8 +181,8 @@ __global__ void k_fill_missing_merge(const float* __restrict__ ry, const float* 
     if(i >= n) return;
     int count = 0;
     float total = 0;
-    if(gv(ry[i])) { total += ry[i]; count++; }
-    if(gv(rx[i])) { total += rx[i]; count++; }
+    if(dev_valid(ry[i])) { total += ry[i]; count++; }
+    if(dev_valid(rx[i])) { total += rx[i]; count++; }
     out[i] = count > 0 ? total / (float)count : NAN;
 }
 
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(256) void k_neighbourhood_search(const float* __res
     if(c >= (long)nY * nX) return;
     const int y = (int)(c / nX), x = (int)(c - (long)y * nX);
     const float here = search[c];
-    if(!gv(here) || (apply && apply[c] == 0)) { out[c] = array[c]; return; }
+    if(!dev_valid(here) || (apply && apply[c] == 0)) { out[c] = array[c]; return; }
     const bool active = !apply || apply[c] == 1;
     float nearest_target = NAN, accum = 0;
     long inear = 0;
@@ -206,11 +204,11 @@ __global__ __launch_bounds__(256) void k_neighbourhood_search(const float* __res
             for(int xx = max(0, x - halfwidth); xx <= min(nX - 1, x + halfwidth); ++xx) {
                 const long n = (long)yy * nX + xx;
                 const float s = search[n], a = array[n];
-                if(!gv(s) || !gv(a)) continue;
+                if(!dev_valid(s) || !dev_valid(a)) continue;
                 if(s >= tmin && s <= tmax) { counter++; accum = accum + a; }
                 else if(counter > 0) continue;
                 else if(fabsf(s - here) >= delta) {
-                    if(!gv(nearest_target)) { nearest_target = s; inear = n; }
+                    if(!dev_valid(nearest_target)) { nearest_target = s; inear = n; }
                     else {
                         const float cur = fminf(fabsf(s - tmin), fabsf(s - tmax));
                         const float best = fminf(fabsf(nearest_target - tmin), fabsf(nearest_target - tmax));
@@ -220,7 +218,7 @@ __global__ __launch_bounds__(256) void k_neighbourhood_search(const float* __res
             }
     float r;
     if(counter > 0) r = accum / (float)counter;
-    else if(gv(nearest_target)) r = array[inear];
+    else if(dev_valid(nearest_target)) r = array[inear];
     else r = array[c];
     out[c] = r;
 }
@@ -238,13 +236,13 @@ __global__ __launch_bounds__(256) void k_gradient_minmax(const float* __restrict
         for(int xx = max(0, x - halfwidth); xx <= min(nX - 1, x + halfwidth); ++xx) {
             const long n = (long)yy * nX + xx;
             const float b = base[n];
-            if(!gv(b) || !gv(values[n])) continue;
-            if(!gv(cmax) || b > cmax) { cmax = b; imax = n; }
-            if(!gv(cmin) || b < cmin) { cmin = b; imin = n; }
+            if(!dev_valid(b) || !dev_valid(values[n])) continue;
+            if(!dev_valid(cmax) || b > cmax) { cmax = b; imax = n; }
+            if(!dev_valid(cmin) || b < cmin) { cmin = b; imin = n; }
             count++;
         }
     float r = default_gradient;
-    if(!(count < num_min || !gv(cmax) || !gv(cmin) || fabsf(cmax - cmin) <= min_range)) r = (values[imax] - values[imin]) / (cmax - cmin);
+    if(!(count < num_min || !dev_valid(cmax) || !dev_valid(cmin) || fabsf(cmax - cmin) <= min_range)) r = (values[imax] - values[imin]) / (cmax - cmin);
     out[c] = r;
 }
 // calc_gradient.cpp:79-98: the four moment fields and the validity mask
@@ -253,7 +251,7 @@ __global__ void k_gradient_moments(const float* __restrict__ base, const float* 
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= n) return;
     const float b = base[i], v = values[i];
-    const bool good = gv(b) && gv(v);
+    const bool good = dev_valid(b) && dev_valid(v);
     b0[i] = good ? b : NAN;
     v0[i] = good ? v : NAN;
     bb[i] = good ? b * b : NAN;
@@ -268,22 +266,20 @@ __global__ void k_gradient_regression(const float* __restrict__ mX, const float*
     if(i >= n) return;
     float r = default_gradient;
     const float var = mXX[i] - mX[i] * mX[i];
-    if(cnt[i] >= (float)num_min && gv(mXX[i]) && gv(mXY[i]) && gv(mX[i]) && var != 0) {
+    if(cnt[i] >= (float)num_min && dev_valid(mXX[i]) && dev_valid(mXY[i]) && dev_valid(mX[i]) && var != 0) {
         bool valid_range = true;
-        if(gv(min_range)) {
+        if(dev_valid(min_range)) {
             const float range = sqrtf(var);
-            if(!gv(range) || range < min_range) valid_range = false;
+            if(!dev_valid(range) || range < min_range) valid_range = false;
         }
         if(valid_range) r = (mXY[i] - mX[i] * mY[i]) / var;
     }
     out[i] = r;
 }
 
-inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
-
 void reset_winners(DevBuf<int>& winner, size_t n) {
     winner.get(n);
-    hipLaunchKernelGGL(k_set_int, dim3(blocks(n)), dim3(256), 0, stream(), winner.p, n, -1);
+    launch(k_set_int, blocks_of(n), 256, 0, winner.p, n, -1);
 }
 
 }   // namespace
@@ -292,8 +288,7 @@ void reset_winners(DevBuf<int>& winner, size_t n) {
 namespace gpp {
 void gradient_regression_launch(const float* mX, const float* mY, const float* mXX, const float* mXY, const float* cnt, size_t n, int num_min,
                                 float min_range, float default_gradient, float* out) {
-    hipLaunchKernelGGL(k_gradient_regression, dim3(blocks(n)), dim3(256), 0, stream(), mX, mY, mXX, mXY, cnt, n, num_min, min_range, default_gradient, out);
-    GPP_HIP(hipGetLastError());
+    launch(k_gradient_regression, blocks_of(n), 256, 0, mX, mY, mXX, mXY, cnt, n, num_min, min_range, default_gradient, out);
 }
 }   // namespace gpp
 
@@ -312,25 +307,15 @@ extern "C" int gpp_fill(gpp_points* igrid, const float* input, gpp_points* point
     o.bind(out, n, mem);
     DevBuf<int> winner;
     reset_winners(winner, n);
+    DevBuf<float> drad;   // (outlives the launches that read it)
     if(np > 0) {
         points->to_device();
-        DevBuf<float> drad;
         drad.upload(radii, np);
         gpp_obs_index* ix = gpp_build_obs_index(igrid);
-        hipLaunchKernelGGL(k_circle_winners, dim3(blocks(np)), dim3(256), 0, stream(), grid_ix(ix), points->d_x.p, points->d_y.p, points->d_z.p,
-                           (const float*)nullptr, drad.p, np, 0, 0.0f, winner.p);
-        GPP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_apply_winners, dim3(blocks(n)), dim3(256), 0, stream(), winner.p, in.d, (const float*)nullptr, value, outside ? 2 : 1, n, o.d);
-        GPP_HIP(hipGetLastError());
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        launch(k_circle_winners, blocks_of(np), 256, 0, grid_ix(ix), points->d_x.p, points->d_y.p, points->d_z.p, (const float*)nullptr, drad.p, np, 0, 0.0f, winner.p);
     }
-    hipLaunchKernelGGL(k_apply_winners, dim3(blocks(n)), dim3(256), 0, stream(), winner.p, in.d, (const float*)nullptr, value, outside ? 2 : 1, n, o.d);
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    launch(k_apply_winners, blocks_of(n), 256, 0, winner.p, in.d, (const float*)nullptr, value, outside ? 2 : 1, n, o.d);
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -344,29 +329,22 @@ extern "C" int gpp_fill_missing(const float* values, int ny, int nx, float* out,
     InField in; OutField o;
     in.bind(values, n, mem);
     o.bind(out, n, mem);
-    DevBuf<float> ry, rx;
+    DevBuf<float> ry, rx, vt, rxt;   // (they outlive the launches)
     ry.get(n); rx.get(n);
     if(nx <= FM_MAXX && ny <= FM_MAXX && !path_env("GPP_FILL_MISSING_LINES")) {
         // rows directly; columns as the rows of the transposed field
-        DevBuf<float> vt, rxt;
         vt.get(n); rxt.get(n);
-        hipLaunchKernelGGL(k_fill_missing_rows, dim3(ny), dim3(256), 0, stream(), in.d, ny, nx, ry.p);
-        hipLaunchKernelGGL(k_transpose, dim3((nx + 31) / 32, (ny + 31) / 32), dim3(256), 0, stream(), in.d, ny, nx, vt.p);
-        hipLaunchKernelGGL(k_fill_missing_rows, dim3(nx), dim3(256), 0, stream(), vt.p, nx, ny, rxt.p);
-        hipLaunchKernelGGL(k_transpose, dim3((ny + 31) / 32, (nx + 31) / 32), dim3(256), 0, stream(), rxt.p, nx, ny, rx.p);
-        hipLaunchKernelGGL(k_fill_missing_merge, dim3(blocks(n)), dim3(256), 0, stream(), ry.p, rx.p, n, o.d);
-        GPP_HIP(hipGetLastError());
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));   // vt / rxt die here
-        return GPP_OK;
+        launch(k_fill_missing_rows, ny, 256, 0, in.d, ny, nx, ry.p);
+        launch(k_transpose, dim3((nx + 31) / 32, (ny + 31) / 32), 256, 0, in.d, ny, nx, vt.p);
+        launch(k_fill_missing_rows, nx, 256, 0, vt.p, nx, ny, rxt.p);
+        launch(k_transpose, dim3((ny + 31) / 32, (nx + 31) / 32), 256, 0, rxt.p, nx, ny, rx.p);
     }
-    hipLaunchKernelGGL(k_fill_missing_lines, dim3(blocks(ny)), dim3(256), 0, stream(), in.d, ny, nx, 0, ry.p);
-    hipLaunchKernelGGL(k_fill_missing_lines, dim3(blocks(nx)), dim3(256), 0, stream(), in.d, ny, nx, 1, rx.p);
-    hipLaunchKernelGGL(k_fill_missing_merge, dim3(blocks(n)), dim3(256), 0, stream(), ry.p, rx.p, n, o.d);
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    else {
+        launch(k_fill_missing_lines, blocks_of(ny), 256, 0, in.d, ny, nx, 0, ry.p);
+        launch(k_fill_missing_lines, blocks_of(nx), 256, 0, in.d, ny, nx, 1, rx.p);
+    }
+    launch(k_fill_missing_merge, blocks_of(n), 256, 0, ry.p, rx.p, n, o.d);
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -400,23 +378,17 @@ extern "C" int gpp_doping(gpp_points* igrid, const float* background, gpp_points
         if(radii) {
             drad.upload(radii, np);
             gpp_obs_index* ix = gpp_build_obs_index(igrid);
-            hipLaunchKernelGGL(k_circle_winners, dim3(blocks(np)), dim3(256), 0, stream(), grid_ix(ix), points->d_x.p, points->d_y.p, points->d_z.p,
-                               points->d_elev.p, drad.p, np, check, max_elev_diff, winner.p);
+            launch(k_circle_winners, blocks_of(np), 256, 0, grid_ix(ix), points->d_x.p, points->d_y.p, points->d_z.p, points->d_elev.p, drad.p, np, check, max_elev_diff, winner.p);
         }
         else {
             dhw.upload(halfwidth, np);
             nn.get(np);
             gpp_nearest_device(igrid, points->d_x.p, points->d_y.p, points->d_z.p, np, 1, nn.p);
-            hipLaunchKernelGGL(k_square_winners, dim3(blocks(np)), dim3(256), 0, stream(), nn.p, points->d_elev.p, dhw.p, np, igrid->d_elev.p,
-                               igrid->ny, igrid->nx, check, max_elev_diff, winner.p);
+            launch(k_square_winners, blocks_of(np), 256, 0, nn.p, points->d_elev.p, dhw.p, np, igrid->d_elev.p, igrid->ny, igrid->nx, check, max_elev_diff, winner.p);
         }
-        GPP_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_apply_winners, dim3(blocks(n)), dim3(256), 0, stream(), winner.p, bg.d, obs.d, 0.0f, 0, n, o.d);
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    launch(k_apply_winners, blocks_of(n), 256, 0, winner.p, bg.d, obs.d, 0.0f, 0, n, o.d);
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -440,12 +412,8 @@ extern "C" int gpp_neighbourhood_search(const float* array, const float* search_
         if(mem & GPP_MEM_DEVICE) ap = apply_array;
         else { dapply.upload(apply_array, n); ap = dapply.p; }
     }
-    hipLaunchKernelGGL(k_neighbourhood_search, dim3(blocks(n)), dim3(256), 0, stream(), a.d, s.d, ny, nx, halfwidth, search_target_min,
-                       search_target_max, search_delta, ap, o.d);
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    launch(k_neighbourhood_search, blocks_of(n), 256, 0, a.d, s.d, ny, nx, halfwidth, search_target_min, search_target_max, search_delta, ap, o.d);
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -465,29 +433,19 @@ extern "C" int gpp_calc_gradient(const float* base, const float* values, int ny,
     b.bind(base, n, mem);
     v.bind(values, n, mem);
     o.bind(out, n, mem);
-    if(gradient_type == GPP_GRADIENT_MINMAX) {
-        hipLaunchKernelGGL(k_gradient_minmax, dim3(blocks(n)), dim3(256), 0, stream(), b.d, v.d, ny, nx, halfwidth, num_min, min_range, default_gradient, o.d);
-        GPP_HIP(hipGetLastError());
-    }
+    DevBuf<float> buf;   // (the moment fields of the regression: they outlive the launches)
+    if(gradient_type == GPP_GRADIENT_MINMAX) launch(k_gradient_minmax, blocks_of(n), 256, 0, b.d, v.d, ny, nx, halfwidth, num_min, min_range, default_gradient, o.d);
     else {
-        DevBuf<float> buf;
         buf.get(n * 10);
         float *b0 = buf.p, *v0 = b0 + n, *bb = b0 + 2 * n, *bv = b0 + 3 * n, *ok = b0 + 4 * n;
         float *mX = b0 + 5 * n, *mY = b0 + 6 * n, *mXX = b0 + 7 * n, *mXY = b0 + 8 * n, *cnt = b0 + 9 * n;
-        hipLaunchKernelGGL(k_gradient_moments, dim3(blocks(n)), dim3(256), 0, stream(), b.d, v.d, n, b0, v0, bb, bv, ok);
-        GPP_HIP(hipGetLastError());
+        launch(k_gradient_moments, blocks_of(n), 256, 0, b.d, v.d, n, b0, v0, bb, bv, ok);
         const float* src[5] = {b0, v0, bb, bv, ok};
         float* dst[5] = {mX, mY, mXX, mXY, cnt};
         for(int k = 0; k < 5; k++)   // calc_gradient.cpp:100-105: box means through the neighbourhood kernels
             if(gpp_neighbourhood(src[k], ny, nx, 1, 0, halfwidth, k == 4 ? GPP_SUM : GPP_MEAN, dst[k], GPP_MEM_DEVICE) != GPP_OK) return GPP_ERUNTIME;
-        hipLaunchKernelGGL(k_gradient_regression, dim3(blocks(n)), dim3(256), 0, stream(), mX, mY, mXX, mXY, cnt, n, num_min, min_range, default_gradient, o.d);
-        GPP_HIP(hipGetLastError());
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        launch(k_gradient_regression, blocks_of(n), 256, 0, mX, mY, mXX, mXY, cnt, n, num_min, min_range, default_gradient, o.d);
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }

@@ -229,9 +229,7 @@ extern "C" int gpp_local_distribution_correction(gpp_points* grid, const float* 
     b.bind(background, nq, mem);
     if(nS == 0) {   // no station: the background
         GPP_HIP(hipMemcpyAsync(o.d, b.d, sizeof(float) * nq, hipMemcpyDeviceToDevice, stream()));
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        return finish_call(o);
     }
     po.bind(nT > 0 ? pobs : nullptr, (size_t)nT * nS, mem);
     pb.bind(nT > 0 ? pbackground : nullptr, (size_t)nT * nS, mem);
@@ -242,9 +240,7 @@ extern "C" int gpp_local_distribution_correction(gpp_points* grid, const float* 
     cnt.get(nq);
     max_cnt.get(1);
     GPP_HIP(hipMemsetAsync(max_cnt.p, 0, sizeof(int), stream()));
-    hipLaunchKernelGGL(k_ldc_count, dim3((nq + 255) / 256), dim3(256), 0, stream(), iv, d.R, grid->d_x.p, grid->d_y.p, grid->d_z.p, nq, b.d,
-                       po.d, pb.d, nS, nT, min_points, cnt.p, max_cnt.p, o.d);
-    GPP_HIP(hipGetLastError());
+    launch(k_ldc_count, blocks_of(nq), 256, 0, iv, d.R, grid->d_x.p, grid->d_y.p, grid->d_z.p, nq, b.d, po.d, pb.d, nS, nT, min_points, cnt.p, max_cnt.p, o.d);
     DevBuf<long long> wide, offset;
     const long long total = scan_counts(cnt.p, nq, wide, offset);
     if(total > 0) {
@@ -264,27 +260,20 @@ extern "C" int gpp_local_distribution_correction(gpp_points* grid, const float* 
             const long long size = end - base;
             if(size == 0) continue;
             kr.get((size_t)size); kf.get((size_t)size);
-            hipLaunchKernelGGL(k_ldc_fill, dim3((n + 255) / 256), dim3(256), 0, stream(), iv, d, grid->d_x.p, grid->d_y.p, grid->d_z.p,
-                               grid->d_elev.p, grid->d_laf.p, q0, n, po.d, pb.d, nS, nT, (const int*)cnt.p, (const long long*)offset.p, base,
-                               kr.p, kf.p);
+            launch(k_ldc_fill, blocks_of(n), 256, 0, iv, d, grid->d_x.p, grid->d_y.p, grid->d_z.p, grid->d_elev.p, grid->d_laf.p, q0, n, po.d, pb.d, nS, nT, (const int*)cnt.p,
+                   (const long long*)offset.p, base, kr.p, kf.p);
             if(!every_cell)
-                hipLaunchKernelGGL(k_ldc_cell_lds, dim3(n), dim3(64), 0, stream(), (const u64*)kr.p, (const u64*)kf.p, (const long long*)offset.p,
-                                   base, (const int*)cnt.p, q0, b.d, min_quantile, max_quantile, o.d);
-            GPP_HIP(hipGetLastError());
+                launch(k_ldc_cell_lds, n, 64, 0, (const u64*)kr.p, (const u64*)kf.p, (const long long*)offset.p, base, (const int*)cnt.p, q0, b.d, min_quantile, max_quantile, o.d);
             if(every_cell || most > LDC_LDS_MAX) {
                 kr2.get((size_t)size); kf2.get((size_t)size);
                 sort_segments(kr.p, kr2.p, size, offset.p + q0, base, n);
                 sort_segments(kf.p, kf2.p, size, offset.p + q0, base, n);
                 ws.get(4 * ((size_t)size + n));
-                hipLaunchKernelGGL(k_ldc_cell_hbm, dim3(n), dim3(64), 0, stream(), (const u64*)kr2.p, (const u64*)kf2.p,
-                                   (const long long*)offset.p, base, (const int*)cnt.p, q0, every_cell ? 1 : 0, b.d, min_quantile, max_quantile,
-                                   ws.p, o.d);
-                GPP_HIP(hipGetLastError());
+                launch(k_ldc_cell_hbm, n, 64, 0, (const u64*)kr2.p, (const u64*)kf2.p, (const long long*)offset.p, base, (const int*)cnt.p, q0, every_cell ? 1 : 0, b.d,
+                       min_quantile, max_quantile, ws.p, o.d);
             }
         }
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }

@@ -36,8 +36,6 @@ namespace {
 #define MEM_F_T (256 * MEM_F_NC)      // ... of a strip of 3072 columns, halo included: 2 x 3072 x (8 + 2) B = 60 KiB of LDS, two workgroups per CU
 #define MEM_F_MAXH 1024               // the halo halfwidth * E the fused form takes: at least MEM_F_T - 2 * 1024 = 1024 output columns per strip
 
-__device__ __forceinline__ bool mv(float v) { return !isnan(v) && !isinf(v); }
-
 // What a pass sums: the values themselves, their float squares (Std / Variance), or one of the five moment fields of calc_gradient.cpp:79-98
 // formed on the fly from base and values (an invalid base or value makes all five invalid; the mask is 1 / 0).
 enum { SRC_VALUE = 0, SRC_SQUARE, SRC_B, SRC_V, SRC_BB, SRC_BV, SRC_OK };
@@ -54,7 +52,7 @@ __device__ __forceinline__ float source_at(const Source& s, long row, long j, in
     if(SRC == SRC_VALUE) return v;
     if(SRC == SRC_SQUARE) return v * v;
     const float b = s.base[s.base_e ? i : row * s.X + x];
-    const bool good = mv(b) && mv(v);
+    const bool good = dev_valid(b) && dev_valid(v);
     if(SRC == SRC_OK) return good ? 1.0f : 0.0f;
     if(!good) return NAN;
     return SRC == SRC_B ? b : SRC == SRC_V ? v : SRC == SRC_BB ? b * b : b * v;
@@ -71,12 +69,12 @@ __global__ __launch_bounds__(256) void k_mem_cols(Source src, int Y, long N, int
     const long lo = max(0L, (long)y0 - hw), hi = min((long)Y - 1, (long)y0 + hw);
     const int x = (int)(j / src.E);
     double s = 0; int c = 0;
-    for(long yy = lo; yy <= hi; yy++) { const float v = source_at<SRC>(src, yy, j, x); if(mv(v)) { s += (double)v; c++; } }
+    for(long yy = lo; yy <= hi; yy++) { const float v = source_at<SRC>(src, yy, j, x); if(dev_valid(v)) { s += (double)v; c++; } }
     for(int y = y0; y < y1; y++) {
         if(y > y0) {
             const long add = (long)y + hw, sub = (long)y - hw - 1;
-            if(add <= (long)Y - 1) { const float v = source_at<SRC>(src, add, j, x); if(mv(v)) { s += (double)v; c++; } }
-            if(sub >= 0) { const float v = source_at<SRC>(src, sub, j, x); if(mv(v)) { s -= (double)v; c--; } }
+            if(add <= (long)Y - 1) { const float v = source_at<SRC>(src, add, j, x); if(dev_valid(v)) { s += (double)v; c++; } }
+            if(sub >= 0) { const float v = source_at<SRC>(src, sub, j, x); if(dev_valid(v)) { s -= (double)v; c--; } }
         }
         const long o = (long)(y - ya) * N + j;
         cs[o] = s; cc[o] = c;
@@ -108,12 +106,6 @@ __global__ __launch_bounds__(256) void k_mem_rows(const double* __restrict__ cs,
         out[row + (long)x * E] = o;
     }
 }
-// a workgroup barrier that orders LDS accesses only (__syncthreads also waits for the global loads of the next row, which are meant to stay in flight)
-__device__ __forceinline__ void mem_lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 // Fused form.  Workgroup b: strip b % nstrip of W = MEM_F_T - 2 H output columns (H = hw * E), rows [y0, y1) = segment b / nstrip of SH rows of the band [ya, yb).
 // Thread t owns the columns j0 - H + t + 256 i: their window sums over the rows slide down in registers (a column or row outside the image adds nothing, so the
 // taps need no bounds), go to LDS (two buffers: one barrier per row), and output column oc sums the LDS entries oc, oc + E, ..., oc + 2 H.  The values of the
@@ -134,7 +126,7 @@ __global__ __launch_bounds__(256) void k_mem_fused(Source src, int Y, long N, in
     const long lo = max(0L, (long)y0 - hw), hi = min((long)Y - 1, (long)y0 + hw);
     for(long yy = lo; yy <= hi; yy++) {
 #pragma unroll
-        for(int i = 0; i < MEM_F_NC; i++) { const float v = ld(yy, i); if(mv(v)) { s[i] += (double)v; c[i]++; } }
+        for(int i = 0; i < MEM_F_NC; i++) { const float v = ld(yy, i); if(dev_valid(v)) { s[i] += (double)v; c[i]++; } }
     }
 #pragma unroll
     for(int i = 0; i < MEM_F_NC; i++) { va[i] = ld((long)y0 + 1 + hw, i); vs[i] = ld((long)y0 - hw, i); }   // row y0 + 1 enters / leaves
@@ -142,12 +134,12 @@ __global__ __launch_bounds__(256) void k_mem_fused(Source src, int Y, long N, in
         const int b = (y - y0) & 1;
 #pragma unroll
         for(int i = 0; i < MEM_F_NC; i++) { ls[b][tid + 256 * i] = s[i]; lc[b][tid + 256 * i] = (unsigned short)c[i]; }
-        mem_lds_barrier();
+        lds_barrier();   // (__syncthreads would also wait for the global loads of the next row, which are meant to stay in flight)
         if(y + 1 < y1) {
 #pragma unroll
             for(int i = 0; i < MEM_F_NC; i++) {
-                if(mv(va[i])) { s[i] += (double)va[i]; c[i]++; }
-                if(mv(vs[i])) { s[i] -= (double)vs[i]; c[i]--; }
+                if(dev_valid(va[i])) { s[i] += (double)va[i]; c[i]++; }
+                if(dev_valid(vs[i])) { s[i] -= (double)vs[i]; c[i]--; }
             }
             if(y + 2 < y1) {
 #pragma unroll
@@ -177,7 +169,7 @@ __global__ __launch_bounds__(256) void k_mem_minmax_cols(const float* __restrict
     const long r = t / N, j = t - r * N;
     const long y = ya + r, lo = max(0L, y - hw), hi = min((long)Y - 1, y + hw);
     float m = NAN;
-    for(long k = lo; k <= hi; k++) { const float v = in[k * N + j]; if(mv(v) && (!mv(m) || (is_max ? v > m : v < m))) m = v; }
+    for(long k = lo; k <= hi; k++) { const float v = in[k * N + j]; if(dev_valid(v) && (!dev_valid(m) || (is_max ? v > m : v < m))) m = v; }
     tmp[t] = m;
 }
 __global__ __launch_bounds__(256) void k_mem_minmax_rows(const float* __restrict__ tmp, long rows, int X, int E, int hw, int is_max, float* __restrict__ out) {
@@ -189,7 +181,7 @@ __global__ __launch_bounds__(256) void k_mem_minmax_rows(const float* __restrict
     const long lo = max(0L, x - hw), hi = min((long)X - 1, x + hw);
     const float* row = tmp + r * N + e;
     float m = NAN;
-    for(long k = lo; k <= hi; k++) { const float v = row[k * E]; if(mv(v) && (!mv(m) || (is_max ? v > m : v < m))) m = v; }
+    for(long k = lo; k <= hi; k++) { const float v = row[k * E]; if(dev_valid(v) && (!dev_valid(m) || (is_max ? v > m : v < m))) m = v; }
     out[t] = m;
 }
 // calc_gradient.cpp:26-74 (MinMax) for one (cell, member): the reference's walk in row-major order, strict > / <, validity of base and value
@@ -208,17 +200,16 @@ __global__ __launch_bounds__(256) void k_mem_gradient_minmax(const float* __rest
         for(long xx = xlo; xx <= xhi; ++xx) {
             const long n = yy * nX + xx;
             const float b = base[base_e ? n * E + e : n];
-            if(!mv(b) || !mv(values[n * E + e])) continue;
-            if(!mv(cmax) || b > cmax) { cmax = b; imax = n; }
-            if(!mv(cmin) || b < cmin) { cmin = b; imin = n; }
+            if(!dev_valid(b) || !dev_valid(values[n * E + e])) continue;
+            if(!dev_valid(cmax) || b > cmax) { cmax = b; imax = n; }
+            if(!dev_valid(cmin) || b < cmin) { cmin = b; imin = n; }
             count++;
         }
     float r = default_gradient;
-    if(!(count < num_min || !mv(cmax) || !mv(cmin) || fabsf(cmax - cmin) <= min_range)) r = (values[imax * E + e] - values[imin * E + e]) / (cmax - cmin);
+    if(!(count < num_min || !dev_valid(cmax) || !dev_valid(cmin) || fabsf(cmax - cmin) <= min_range)) r = (values[imax * E + e] - values[imin * E + e]) / (cmax - cmin);
     out[t] = r;
 }
 
-inline unsigned blocks(long n) { return (unsigned)((n + 255) / 256); }
 
 // The fused form takes this call (the halo fits its strip); GPP_MEMBERS_TWO_PASS forces the two-pass form (tests, A/B timings)
 bool fused_form(int hw, int E) { return (long)hw * E <= MEM_F_MAXH && !path_env("GPP_MEMBERS_TWO_PASS"); }
@@ -255,15 +246,12 @@ void box_band(MemBuffers& w, const Source& s, int src, bool fused, int Y, int X,
         int SH = 64;   // rows a workgroup marches down: shorter where the launch would not fill the chip (its first window costs 2 hw + 1 rows)
         while(SH > 16 && strips * ((rows + SH - 1) / SH) < 1024) SH >>= 1;
         if(const char* v = path_env("GPP_MEMBERS_SEG_ROWS")) SH = std::max(1, atoi(v));   // (tests: the long segments of a large cube on a small one; A/B timings)
-        hipLaunchKernelGGL(fused_kernel(src), dim3((unsigned)(strips * ((rows + SH - 1) / SH))), dim3(256), 0, stream(), s, Y, N, hw, statistic, ya, yb, SH, d_out);
-        GPP_HIP(hipGetLastError());
+        launch(fused_kernel(src), (unsigned)(strips * ((rows + SH - 1) / SH)), 256, 0, s, Y, N, hw, statistic, ya, yb, SH, d_out);
         return;
     }
-    hipLaunchKernelGGL(cols_kernel(src), dim3(blocks(nstrip * N)), dim3(256), 0, stream(), s, Y, N, hw, ya, yb, w.cs.p, w.cc.p);
-    GPP_HIP(hipGetLastError());
+    launch(cols_kernel(src), blocks_of(nstrip * N), 256, 0, s, Y, N, hw, ya, yb, w.cs.p, w.cc.p);
     const long nseg = ((long)X + MEM_SEG - 1) / MEM_SEG;
-    hipLaunchKernelGGL(k_mem_rows, dim3(blocks(rows * nseg * s.E)), dim3(256), 0, stream(), (const double*)w.cs.p, (const int*)w.cc.p, rows, X, s.E, hw, statistic, d_out);
-    GPP_HIP(hipGetLastError());
+    launch(k_mem_rows, blocks_of(rows * nseg * s.E), 256, 0, (const double*)w.cs.p, (const int*)w.cc.p, rows, X, s.E, hw, statistic, d_out);
 }
 
 void members_neighbourhood(const float* d_in, int Y, int X, int E, int hw, int statistic, float* d_out) {
@@ -282,9 +270,8 @@ void members_neighbourhood(const float* d_in, int Y, int X, int E, int hw, int s
         const long n = (long)(yb - ya) * N;
         float* o = d_out + (long)ya * N;
         if(minmax) {
-            hipLaunchKernelGGL(k_mem_minmax_cols, dim3(blocks(n)), dim3(256), 0, stream(), d_in, Y, N, hw, statistic == GPP_MAX, ya, yb, w.f.p);
-            hipLaunchKernelGGL(k_mem_minmax_rows, dim3(blocks(n)), dim3(256), 0, stream(), (const float*)w.f.p, (long)(yb - ya), X, E, hw, statistic == GPP_MAX, o);
-            GPP_HIP(hipGetLastError());
+            launch(k_mem_minmax_cols, blocks_of(n), 256, 0, d_in, Y, N, hw, statistic == GPP_MAX, ya, yb, w.f.p);
+            launch(k_mem_minmax_rows, blocks_of(n), 256, 0, (const float*)w.f.p, (long)(yb - ya), X, E, hw, statistic == GPP_MAX, o);
         }
         else if(moments) {   // neighbourhood.cpp:205-233: the float means of the values and of their float squares, then k_std_finish
             float *mean = w.f.p, *mean2 = w.f.p + bn;
@@ -300,9 +287,7 @@ void members_gradient(const float* d_base, int base_e, const float* d_values, in
                       float default_gradient, float* d_out) {
     const long N = (long)X * E;
     if(type == GPP_GRADIENT_MINMAX) {
-        hipLaunchKernelGGL(k_mem_gradient_minmax, dim3(blocks((long)Y * N)), dim3(256), 0, stream(), d_base, base_e, d_values, Y, X, E, hw, num_min, min_range,
-                           default_gradient, d_out);
-        GPP_HIP(hipGetLastError());
+        launch(k_mem_gradient_minmax, blocks_of((long)Y * N), 256, 0, d_base, base_e, d_values, Y, X, E, hw, num_min, min_range, default_gradient, d_out);
         return;
     }
     // calc_gradient.cpp:79-124: box means of the four moment fields, the box sum of the mask, k_gradient_regression
@@ -344,9 +329,7 @@ extern "C" int gpp_neighbourhood_members(const float* input, int ny, int nx, int
     in.bind(input, n, mem);
     o.bind(out, n, mem);
     members_neighbourhood(in.d, ny, nx, ne, halfwidth, statistic, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -369,8 +352,6 @@ extern "C" int gpp_calc_gradient_members(const float* base, int base_members, co
     v.bind(values, n, mem);
     o.bind(out, n, mem);
     members_gradient(b.d, base_members == ne ? 1 : 0, v.d, ny, nx, ne, gradient_type, halfwidth, num_min, min_range, default_gradient, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }

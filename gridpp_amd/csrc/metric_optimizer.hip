@@ -88,11 +88,9 @@ struct MoRun {
 };
 static_assert(sizeof(MoRun) == 32, "eight words");
 
-__device__ __forceinline__ bool mo_valid(float v) { return !isnan(v) && !isinf(v); }   // util.cpp:16-18
-
 __device__ __forceinline__ MoRun mo_empty() { return MoRun{0, 0, 0, 0, 0, 0, 0, 0u}; }
 __device__ __forceinline__ MoRun mo_single(float u, float s) {
-    return MoRun{u, s, u, s, s, u, 0, mo_valid(s) ? (MO_HAS | MO_BEST | MO_LOFIRST) : MO_HAS};
+    return MoRun{u, s, u, s, s, u, 0, dev_valid(s) ? (MO_HAS | MO_BEST | MO_LOFIRST) : MO_HAS};
 }
 // L lies below R
 __device__ __forceinline__ MoRun mo_combine(const MoRun& L, const MoRun& R) {
@@ -326,8 +324,7 @@ void mo_solve(const float* ref, const float* fcst, long long n, const float* thr
     key.get((size_t)n);
     skey.get((size_t)n);
     sref.get((size_t)n);
-    hipLaunchKernelGGL(k_mo_keys, dim3((unsigned)std::min<long long>((n + 255) / 256, 8192)), dim3(256), 0, stream(), f.d, n, key.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_mo_keys, grid_capped(blocks_of(n), 8192), 256, 0, f.d, n, key.p);
     size_t sb = 0;
     GPP_HIP(rocprim::radix_sort_pairs((void*)nullptr, sb, key.p, skey.p, r.d, sref.p, (size_t)n, 0u, 32u, stream()));
     Staged<char> tmp;
@@ -347,15 +344,11 @@ void mo_solve(const float* ref, const float* fcst, long long n, const float* thr
     for(int t0 = 0; t0 < T; t0 += TB) {
         const int tb = std::min(TB, T - t0);
         const dim3 grid((unsigned)nblocks, (unsigned)((tb + MO_G - 1) / MO_G));
-        hipLaunchKernelGGL(k_mo_totals, grid, dim3(MO_THREADS), 0, stream(), (const float*)sref.p, n, tile, (const float*)dthr.p + t0, tb, nblocks, tot.p);
-        GPP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_mo_scan, dim3(2 * tb), dim3(MO_THREADS), 0, stream(), (const unsigned*)tot.p, nblocks, base.p, total.p);
-        GPP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_mo_sweep, grid, dim3(MO_THREADS), 0, stream(), (const unsigned*)skey.p, (const float*)sref.p, n, tile,
-                           (const float*)dthr.p + t0, tb, nblocks, (const u64*)base.p, (const u64*)total.p, metric, runs.p);
-        GPP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_mo_finish, dim3(tb), dim3(64), 0, stream(), (const MoRun*)runs.p, nblocks, dout.p + t0);
-        GPP_HIP(hipGetLastError());
+        launch(k_mo_totals, grid, MO_THREADS, 0, (const float*)sref.p, n, tile, (const float*)dthr.p + t0, tb, nblocks, tot.p);
+        launch(k_mo_scan, 2 * tb, MO_THREADS, 0, (const unsigned*)tot.p, nblocks, base.p, total.p);
+        launch(k_mo_sweep, grid, MO_THREADS, 0, (const unsigned*)skey.p, (const float*)sref.p, n, tile, (const float*)dthr.p + t0, tb, nblocks, (const u64*)base.p,
+               (const u64*)total.p, metric, runs.p);
+        launch(k_mo_finish, tb, 64, 0, (const MoRun*)runs.p, nblocks, dout.p + t0);
     }
     GPP_HIP(hipMemcpyAsync(x, dout.p, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));   // the one synchronisation of the call; the workspaces go back to the pool here

@@ -21,6 +21,7 @@
 #include <mutex>
 #include <atomic>
 #include "common.h"
+#include "march_geom.h"
 #include <algorithm>
 #include <utility>
 #include <rocprim/rocprim.hpp>
@@ -46,12 +47,12 @@ __device__ __forceinline__ float row_mean_sum_count_v4(const float* row, int E, 
 #pragma unroll 5
     for(int i = 0; i < n4; i++) {
         const float4 q = r4[i];
-        if(nv(q.x)) { total += q.x; count++; }
-        if(nv(q.y)) { total += q.y; count++; }
-        if(nv(q.z)) { total += q.z; count++; }
-        if(nv(q.w)) { total += q.w; count++; }
+        if(dev_valid(q.x)) { total += q.x; count++; }
+        if(dev_valid(q.y)) { total += q.y; count++; }
+        if(dev_valid(q.z)) { total += q.z; count++; }
+        if(dev_valid(q.w)) { total += q.w; count++; }
     }
-    for(int i = n4 * 4; i < E; i++) { const float v = row[i]; if(nv(v)) { total += v; count++; } }
+    for(int i = n4 * 4; i < E; i++) { const float v = row[i]; if(dev_valid(v)) { total += v; count++; } }
     if(statistic == GPP_COUNT) return (float)count;
     if(count == 0) return NAN;
     return (statistic == GPP_MEAN) ? total / (float)count : total;
@@ -102,7 +103,7 @@ __device__ __forceinline__ void member_row_work(const float* row, const int E, c
                     const float vv[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                     for(int j = 0; j < 4; j++) {
-                        const bool ok = nv(vv[j]);
+                        const bool ok = dev_valid(vv[j]);
                         const float v = ok ? vv[j] : NAN;   // NaN compares false against every threshold
                         cnt += ok ? 1 : 0;
 #pragma unroll
@@ -113,7 +114,7 @@ __device__ __forceinline__ void member_row_work(const float* row, const int E, c
             else {
 #pragma unroll 4
                 for(int e = 0; e < E; e++) {
-                    const bool ok = nv(row[e]);
+                    const bool ok = dev_valid(row[e]);
                     const float v = ok ? row[e] : NAN;
                     cnt += ok ? 1 : 0;
 #pragma unroll
@@ -258,7 +259,7 @@ __global__ __launch_bounds__(QF_NB) void k_qf_lut(const float* __restrict__ thr,
     if(j == 0) {
         int flag = 0, U = 0, ident = 1;
         float scale = 1.0f, off = 0.0f;
-        for(int t = 0; t < T; t++) if(!nv(st[t]) || fabsf(st[t]) > 1e37f) flag = 1;
+        for(int t = 0; t < T; t++) if(!dev_valid(st[t]) || fabsf(st[t]) > 1e37f) flag = 1;
         if(!flag) {   // distinct values, ascending (T <= 16: insertion)
             for(int t = 0; t < T; t++) {
                 const float v = st[t];
@@ -271,13 +272,13 @@ __global__ __launch_bounds__(QF_NB) void k_qf_lut(const float* __restrict__ thr,
             // lowest threshold -> bucket 1.5, highest -> bucket 253.5
             const float lo = u[0], hi = u[U - 1];
             scale = (hi > lo) ? 252.0f / (hi - lo) : 1.0f;
-            if(!nv(scale) || scale <= 0) scale = 1.0f;
+            if(!dev_valid(scale) || scale <= 0) scale = 1.0f;
             off = (hi > lo ? 1.5f : 127.5f) - lo * scale;
             for(int k = 0; k < U; k++) {
                 ub[k] = (int)(qf_bucket_into(u[k], scale, off, 0, 0) & 0xffu);
                 if(ub[k] < 1 || ub[k] > 254 || (k > 0 && ub[k] == ub[k - 1])) flag = 1;
             }
-            if(!nv(off)) flag = 1;
+            if(!dev_valid(off)) flag = 1;
         }
         s_scale = scale; s_off = off;
         L->scale = scale; L->off = off; L->ident = ident;
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(256) void k_box_rows(const float* __restrict__ in, 
         int x = x0 - hwc + i;
         const bool inrow = x >= 0 && x < X;
         const float v = inrow ? row[x] : 0.0f;
-        bad |= (inrow && !nv(v)) ? 1 : 0;
+        bad |= (inrow && !dev_valid(v)) ? 1 : 0;
         lds[i] = inrow ? v : NAN;
     }
     const int any_bad = __syncthreads_or(bad);   // (also the barrier after the tile load)
@@ -479,7 +480,7 @@ __global__ __launch_bounds__(256) void k_box_rows(const float* __restrict__ in, 
     double s = 0; int c = 0;
     if(any_bad) {   // some value of this tile is missing: validity per tap
         if(threadIdx.x == 0) atomicOr(&plane_has_invalid[blockIdx.z], 1);
-        if(x < X) for(int k = 0; k <= 2 * hwc; k++) { float v = lds[threadIdx.x + k]; if(nv(v)) { s += (double)v; c++; } }
+        if(x < X) for(int k = 0; k <= 2 * hwc; k++) { float v = lds[threadIdx.x + k]; if(dev_valid(v)) { s += (double)v; c++; } }
     }
     else {          // all valid (the common case): two instructions per tap, the count is the clipped window width
         for(int i = threadIdx.x; i < 256 + 2 * hwc; i += 256) { const int xx = x0 - hwc + i; if(!(xx >= 0 && xx < X)) lds[i] = 0.0f; }
@@ -513,7 +514,7 @@ __global__ __launch_bounds__(256) void k_box_rows4(const float* __restrict__ in,
         const int x = x0 - hwc + i;
         const bool inrow = x >= 0 && x < X;
         const float v = inrow ? row[x] : 0.0f;
-        bad |= (inrow && !nv(v)) ? 1 : 0;
+        bad |= (inrow && !dev_valid(v)) ? 1 : 0;
         lds[pad4(i)] = inrow ? v : NAN;
     }
     const int any_bad = __syncthreads_or(bad);
@@ -524,7 +525,7 @@ __global__ __launch_bounds__(256) void k_box_rows4(const float* __restrict__ in,
 #pragma unroll
         for(int j = 0; j < 4; ++j) {
             double s = 0; int c = 0;
-            if(x0 + base + j < X) for(int k = 0; k <= 2 * hwc; k++) { const float v = lds[pad4(base + j + k)]; if(nv(v)) { s += (double)v; c++; } }
+            if(x0 + base + j < X) for(int k = 0; k <= 2 * hwc; k++) { const float v = lds[pad4(base + j + k)]; if(dev_valid(v)) { s += (double)v; c++; } }
             s4[j] = s; c4[j] = c;
         }
     }
@@ -561,12 +562,12 @@ __global__ __launch_bounds__(256) void k_box_rows_wide(const float* __restrict__
     if(xa >= xb) return;
     double s = 0; int c = 0, bad = 0;
     const int lo = max(xa - hw, 0), hi = (int)min((long)X - 1, (long)xa + hw);
-    for(int k = lo; k <= hi; ++k) { const float v = row[k]; if(nv(v)) { s += (double)v; c++; } else bad = 1; }
+    for(int k = lo; k <= hi; ++k) { const float v = row[k]; if(dev_valid(v)) { s += (double)v; c++; } else bad = 1; }
     for(int x = xa; x < xb; ++x) {
         if(x > xa) {
             const long in_k = (long)x + hw; const int out_k = x - hw - 1;
-            if(in_k < X) { const float v = row[in_k]; if(nv(v)) { s += (double)v; c++; } else bad = 1; }
-            if(out_k >= 0) { const float v = row[out_k]; if(nv(v)) { s -= (double)v; c--; } }
+            if(in_k < X) { const float v = row[in_k]; if(dev_valid(v)) { s += (double)v; c++; } else bad = 1; }
+            if(out_k >= 0) { const float v = row[out_k]; if(dev_valid(v)) { s -= (double)v; c--; } }
         }
         rs[plane + (long)y * X + x] = s;
         rc[plane + (long)y * X + x] = c;
@@ -604,7 +605,7 @@ __global__ __launch_bounds__(256) void k_box_cols(const double* __restrict__ rs,
         float o = NAN;
         if(statistic == GPP_COUNT) o = (float)c;
         else if(c > 0) o = (statistic == GPP_MEAN) ? (float)(s / (double)c) : (float)s;
-        if(qf_reps > 0 && nv(o)) {   // quantile_fast epilogue (neighbourhood.cpp:378-389 / 494-506): E-fold float sum / E, clamp
+        if(qf_reps > 0 && dev_valid(o)) {   // quantile_fast epilogue (neighbourhood.cpp:378-389 / 494-506): E-fold float sum / E, clamp
             float yv = o;
             if(qf_reps > 1) { float sum = 0; for(int e = 0; e < qf_reps; e++) sum += o; yv = sum / (float)qf_reps; }
             o = yv > 1 ? 1.0f : (yv < 0 ? 0.0f : yv);
@@ -620,13 +621,8 @@ __global__ __launch_bounds__(256) void k_box_cols(const double* __restrict__ rs,
 // written once; the two-kernel form writes and re-reads a plane of doubles and one of counts in between (config 4 Mean: 0.09 + 0.05 ms for the
 // two passes, this kernel: see DESIGN 11.5).  (A first version without the march -- tiles of 32 x 64 outputs, each loading its halo rows again --
 // took 0.22 ms: 60 KB of LDS per workgroup leave two of them on a CU, and a workgroup that loads, sums and stores once is mostly latency.)
-// a workgroup barrier that orders LDS accesses only (__syncthreads also waits for every global load and store of the wave: here that would be a
-// wait for the next chunk's values in the middle of the current chunk)
-__device__ __forceinline__ void bm_lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
+// The barriers of the marching kernels are lds_barrier(): __syncthreads also waits for every global load and store of the wave, which here would be a wait for
+// the next chunk's values in the middle of the current chunk.
 #define BM_W 64
 #define BM_C 32
 #define BM_RING 64
@@ -685,7 +681,7 @@ __global__ __launch_bounds__(256) void k_box_march(const float* __restrict__ in,
     };
     fetch(0);
     if(tid < 2) bflag[tid] = 0;
-    bm_lds_barrier();
+    lds_barrier();
     int ynext = ya;                                                 // first output row not yet written
     // The outputs of a chunk wait in registers and are stored one chunk later, in front of the next fetch: stores and loads complete in the order
     // they were issued, so the wait for a chunk's values would otherwise be a wait for the stores issued behind its fetch as well (measured: 0.080 ms
@@ -720,11 +716,11 @@ __global__ __launch_bounds__(256) void k_box_march(const float* __restrict__ in,
             for(int j = 0; j < NCc; j++) {
                 const int c = (tid & 31) + 32 * j;
                 tin[r * P + c] = v[i][j];                           // (c < 96 <= P)
-                bad |= nv(v[i][j]) ? 0 : 1;                         // (outside the field: 0)
+                bad |= dev_valid(v[i][j]) ? 0 : 1;                         // (outside the field: 0)
             }
         }
         if(bad) bflag[k & 1] = 1;
-        bm_lds_barrier();                                           // the chunk is in LDS, and the previous chunk's outputs are finished
+        lds_barrier();                                              // the chunk is in LDS, and the previous chunk's outputs are finished
         const bool counted = bflag[k & 1] != 0;
         if(tid == 0) bflag[(k + 1) & 1] = 0;                        // (read by everybody one chunk ago, before the barrier below; written again behind it)
         hist = (hist << 1) | (counted ? 1u : 0u);
@@ -752,7 +748,7 @@ __global__ __launch_bounds__(256) void k_box_march(const float* __restrict__ in,
                 const int y = yl0 + k * BM_C + r;
                 const bool rowok = y >= 0 && y < Y;
                 unsigned char* const rc = rcnt + slot * BM_W + 8 * sg;
-                auto ok = [&](const int q) { const int c = 8 * sg + q; return rowok && c >= clo && c < chi && nv(t[q]); };
+                auto ok = [&](const int q) { const int c = 8 * sg + q; return rowok && c >= clo && c < chi && dev_valid(t[q]); };
                 double s = 0.0; int n = 0;
                 for(int q = 0; q <= 2 * hw; q++) if(ok(q)) { s += (double)t[q]; n++; }
                 rs[0] = s; rc[0] = (unsigned char)n;
@@ -764,7 +760,7 @@ __global__ __launch_bounds__(256) void k_box_march(const float* __restrict__ in,
                 }
             }
         }
-        bm_lds_barrier();                                           // the ring holds the rows up to ytop; the chunk's LDS rows are free again
+        lds_barrier();                                              // the ring holds the rows up to ytop; the chunk's LDS rows are free again
         const int ytop = yl0 + (k + 1) * BM_C - 1;
         const int ylim = min(yb, ytop - hw + 1);                    // outputs [ynext, ylim) have their 2 hw + 1 rows in the ring (at most BM_C of them)
         {
@@ -826,7 +822,7 @@ __global__ __launch_bounds__(256) void k_box_march(const float* __restrict__ in,
                         }
                         else o = (float)s;
                     }
-                    if(qf_reps > 0 && nv(o)) {   // quantile_fast epilogue (neighbourhood.cpp:378-389 / 494-506): E-fold float sum / E, clamp
+                    if(qf_reps > 0 && dev_valid(o)) {   // quantile_fast epilogue (neighbourhood.cpp:378-389 / 494-506): E-fold float sum / E, clamp
                         float yv = o;
                         if(qf_reps > 1) { float sum = 0; for(int e = 0; e < qf_reps; e++) sum += o; yv = sum / (float)qf_reps; }
                         o = yv > 1 ? 1.0f : (yv < 0 ? 0.0f : yv);
@@ -907,7 +903,7 @@ __global__ __launch_bounds__(256) void k_minmax_march(const float* __restrict__ 
 #pragma unroll
             for(int j = 0; j < NCc; j++) {
                 const float t = row[xo[j]];
-                v[i][j] = (rowok && colok[j] && nv(t)) ? t : ident;
+                v[i][j] = (rowok && colok[j] && dev_valid(t)) ? t : ident;
             }
         }
     };
@@ -933,7 +929,7 @@ __global__ __launch_bounds__(256) void k_minmax_march(const float* __restrict__ 
         for(int i = 0; i < NR; i++)
 #pragma unroll
             for(int j = 0; j < NCc; j++) tin[((tid >> 5) + 8 * i) * P + (tid & 31) + 32 * j] = v[i][j];
-        bm_lds_barrier();                                           // the chunk is in LDS, and the previous chunk's outputs are finished
+        lds_barrier();                                              // the chunk is in LDS, and the previous chunk's outputs are finished
         flush();
         if(k + 1 < nchunk) fetch(k + 1);
         {
@@ -950,7 +946,7 @@ __global__ __launch_bounds__(256) void k_minmax_march(const float* __restrict__ 
                 for(int j = 0; j < 8; j++) rs[j] = o[j];
             }
         }
-        bm_lds_barrier();
+        lds_barrier();
         const int ytop = yl0 + (k + 1) * BM_C - 1;
         const int ylim = min(yb, ytop - hw + 1);
         {
@@ -979,11 +975,11 @@ __global__ __launch_bounds__(256) void k_minmax_pass(const float* __restrict__ i
     float m = NAN;
     if(dir == 0) {
         const int a = max(0, x - hw), b = (int)min((long)X - 1, (long)x + hw);
-        for(int k = a; k <= b; k++) { float v = in[(long)y * X + k]; if(nv(v) && (!nv(m) || (is_max ? v > m : v < m))) m = v; }
+        for(int k = a; k <= b; k++) { float v = in[(long)y * X + k]; if(dev_valid(v) && (!dev_valid(m) || (is_max ? v > m : v < m))) m = v; }
     }
     else {
         const int a = max(0, y - hw), b = (int)min((long)Y - 1, (long)y + hw);
-        for(int k = a; k <= b; k++) { float v = in[(long)k * X + x]; if(nv(v) && (!nv(m) || (is_max ? v > m : v < m))) m = v; }
+        for(int k = a; k <= b; k++) { float v = in[(long)k * X + x]; if(dev_valid(v) && (!dev_valid(m) || (is_max ? v > m : v < m))) m = v; }
     }
     out[(long)y * X + x] = m;
 }
@@ -1017,7 +1013,7 @@ __device__ float wave_kth(const Window& w, int n, int k, int lane) {
     while(lo < hi) {
         unsigned mid = lo + ((hi - lo) >> 1);
         int c = 0;
-        for(int i = lane; i < n; i += 64) { float v = w.at(i); if(nv(v) && f2ord(v) <= mid) c++; }
+        for(int i = lane; i < n; i += 64) { float v = w.at(i); if(dev_valid(v) && f2ord(v) <= mid) c++; }
         c = wave_sum_i(c);
         if(c >= k + 1) hi = mid; else lo = mid + 1;
     }
@@ -1039,8 +1035,8 @@ __global__ __launch_bounds__(256) void k_brute(const float* __restrict__ in, int
             const bool sv = (statistic == GPP_STD || statistic == GPP_VARIANCE);
             for(int i = 0; i < n; i++) {
                 float v = w.at(i);
-                if(!nv(v)) continue;
-                if(sv) { if(!nv(K)) K = v; float d = v - K; total += d; total2 += d * d; }
+                if(!dev_valid(v)) continue;
+                if(sv) { if(!dev_valid(K)) K = v; float d = v - K; total += d; total2 += d * d; }
                 else total += v;
                 count++;
             }
@@ -1054,7 +1050,7 @@ __global__ __launch_bounds__(256) void k_brute(const float* __restrict__ in, int
     }
     else {
         int N = 0;
-        for(int i = lane; i < n; i += 64) if(nv(w.at(i))) N++;
+        for(int i = lane; i < n; i += 64) if(dev_valid(w.at(i))) N++;
         N = wave_sum_i(N);
         if(statistic == GPP_RANDOMCHOICE) {   // util.cpp:74-95 uses rand(); any valid element is a correct draw
             if(N > 0) {
@@ -1064,7 +1060,7 @@ __global__ __launch_bounds__(256) void k_brute(const float* __restrict__ in, int
         }
         else {
             float qq = (statistic == GPP_MIN) ? 0.0f : (statistic == GPP_MEDIAN) ? 0.5f : (statistic == GPP_MAX) ? 1.0f : q;
-            if(N > 0 && nv(qq)) {
+            if(N > 0 && dev_valid(qq)) {
                 if(qq == 0) value = wave_kth(w, n, 0, lane);
                 else if(qq == 1) value = wave_kth(w, n, N - 1, lane);
                 else {
@@ -1088,7 +1084,7 @@ __global__ void k_qf_yarray(float* __restrict__ planes, long n, int reps) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= n) return;
     float s = planes[i];
-    if(!nv(s)) { planes[i] = NAN; return; }
+    if(!dev_valid(s)) { planes[i] = NAN; return; }
     float yv;
     if(reps <= 1) yv = s;   // 2-D form (:378-384): sum = s, count = 1
     else { float sum = 0; for(int e = 0; e < reps; e++) sum += s; yv = sum / (float)reps; }
@@ -1100,7 +1096,7 @@ __device__ __forceinline__ float qf_interp_column(const float* __restrict__ ya, 
     const float y0a = ya[c], yLa = ya[(long)(T - 1) * C + c];
     if(x == 1 && y0a == 1) return thr[0];
     if(x == 0 && yLa == 0) return thr[T - 1];
-    if(!nv(x)) return NAN;                         // interpolate(): util.cpp:378-379
+    if(!dev_valid(x)) return NAN;                         // interpolate(): util.cpp:378-379
     if(x > yLa) return thr[T - 1];                 // util.cpp:386-389
     if(x < y0a) return thr[0];
     int i0 = -1, i1 = -1;                          // get_lower_index / get_upper_index (util.cpp:339-376)
@@ -1121,7 +1117,7 @@ __global__ void k_qf_interp(const float* __restrict__ ya, long C, int T, const f
     long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if(c >= C) return;
     bool missing = false;
-    for(int t = 0; t < T; t++) if(!nv(ya[(long)t * C + c])) missing = true;
+    for(int t = 0; t < T; t++) if(!dev_valid(ya[(long)t * C + c])) missing = true;
     out[c] = missing ? NAN : qf_interp_column(ya, C, c, T, thr, qfield ? q[c] : q[0]);
 }
 // The unfused finish of the many-level forms.  k_qf_interp_multi: the same column for nq scalar levels, out [C][nq].
@@ -1130,7 +1126,7 @@ __global__ void k_qf_interp_multi(const float* __restrict__ ya, long C, int T, c
     long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if(c >= C) return;
     bool missing = false;
-    for(int t = 0; t < T; t++) if(!nv(ya[(long)t * C + c])) missing = true;
+    for(int t = 0; t < T; t++) if(!dev_valid(ya[(long)t * C + c])) missing = true;
     for(int j = 0; j < nq; j++) out[c * nq + j] = missing ? NAN : qf_interp_column(ya, C, c, T, thr, levels[j]);
 }
 __global__ void k_qf_cdf_copy(const float* __restrict__ ya, long C, int T, float* __restrict__ out) {
@@ -1179,8 +1175,7 @@ extern "C" int gpp_debug_poison_nbh_workspace(int byte, int keep_padding) {
     if(keep_padding && w.pad.ptr && w.pad.ptr == (const void*)w.planes.p && w.pad.gen == w.planes.gen) {
         const QfGeom g = qf_geom(w.pad.y, w.pad.x);
         const long C = (long)g.Y * g.X;
-        hipLaunchKernelGGL(k_poison_plane_cells, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), reinterpret_cast<unsigned char*>(w.planes.p), g, w.pad.t + 1, byte);
-        GPP_HIP(hipGetLastError());
+        launch(k_poison_plane_cells, blocks_of(C), 256, 0, reinterpret_cast<unsigned char*>(w.planes.p), g, w.pad.t + 1, byte);
     }
     else { w.planes.poison(byte); w.pad = QfPadKey(); }
     GPP_HIP(hipStreamSynchronize(stream()));
@@ -1199,8 +1194,7 @@ void member_pass_launch(const float* d_in, long C, int E, int statistic, const f
     std::call_once(attr_once, [] { GPP_HIP(hipFuncSetAttribute((const void*)k_member_pass<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ((16 * MEMBER_EC + 63) / 64) * 1024)); });
     const int waves_per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / std::max<size_t>(lds, 1)));
     const long grid = std::min<long>(tiles, (long)256 * waves_per_cu);
-    hipLaunchKernelGGL((k_member_pass<MODE>), dim3((unsigned)grid), dim3(64), lds, stream(), d_in, C, E, statistic, d_thr, T, d_out, dma ? 1 : 0, g);
-    GPP_HIP(hipGetLastError());
+    launch(k_member_pass<MODE>, (unsigned)grid, 64, lds, d_in, C, E, statistic, d_thr, T, d_out, dma ? 1 : 0, g);
 }
 void member_pass(const float* d_in, long C, int E, int mode, int statistic, const float* d_thr, int T, float* d_out, const QfGeom& g = QfGeom()) {
     if(mode == 0) member_pass_launch<0>(d_in, C, E, statistic, d_thr, T, d_out, g);
@@ -1214,8 +1208,7 @@ void qf_count_launch_nl(const float* d_in, long C, int E, const float* d_thr, in
     int waves_per_cu = (int)std::max<size_t>(1, std::min<size_t>(24, (160 * 1024) / lds));
     if(path_env("GPP_QF_WAVES")) waves_per_cu = std::max(1, std::min(waves_per_cu, atoi(path_env("GPP_QF_WAVES"))));   // (A/B: fewer, longer streams)
     const long grid = std::max<long>(1, std::min<long>((C / 64 + 3) / 4, (long)256 * waves_per_cu));
-    hipLaunchKernelGGL((k_qf_count<NL>), dim3((unsigned)grid), dim3(64), lds, stream(), d_in, C, E, d_thr, T, lut, cnt8, g, Uexp);
-    GPP_HIP(hipGetLastError());
+    launch(k_qf_count<NL>, (unsigned)grid, 64, lds, d_in, C, E, d_thr, T, lut, cnt8, g, Uexp);
 }
 template <int... I> auto qf_count_form(std::integer_sequence<int, I...>, int U) { static constexpr decltype(&qf_count_launch_nl<3>) forms[] = {qf_count_launch_nl<I + 3>...}; return forms[U - 1]; }
 void qf_count_launch(const float* d_in, long C, int E, const float* d_thr, int T, const QfLut* lut, int U, unsigned char* cnt8, const QfGeom& g, const int Uexp) {
@@ -1232,11 +1225,8 @@ struct MarchGeom {
         if((!box && statistic != GPP_MIN && statistic != GPP_MAX) || hw > (box ? BM_MAXHW : BM_MM_MAXHW) || nplanes > 65535 || path_env("GPP_BOX_TWO_PASS")) return;
         W = box || hw <= BM_MAXHW ? BM_W : BM_W / 2; strips = (X + W - 1) / W;
         const long fill = path_env("GPP_BM_FILL") ? std::max(1, atoi(path_env("GPP_BM_FILL"))) : box ? 768 : 1280;   // (A/B: workgroups the launch aims for)
-        const long want = std::max<long>(1, fill / std::max<long>(1, (long)strips * nplanes));
-        const int even = (int)std::min<long>(want, (Y + BM_C - 1) / BM_C);
-        SH = ((Y + even - 1) / even + BM_C - 1) / BM_C * BM_C;
-        while((Y + SH - 1) / SH > 65535) SH += BM_C;   // gridDim.y is a 16-bit quantity
-        segs = (Y + SH - 1) / SH; ok = true;
+        const MarchSegments sg = march_segments(Y, BM_C, std::max<long>(1, fill / std::max<long>(1, (long)strips * nplanes)));
+        SH = sg.SH; segs = sg.segs; ok = true;
     }
     dim3 grid(int nseg, int nplanes = 1) const { return dim3(strips, nseg < 0 ? segs : nseg, nplanes); }   // nseg < 0: every segment; else a band of them (from seg0)
 };
@@ -1254,8 +1244,7 @@ void box_stat(const float* d_in, int Y, int X, int nplanes, int hw, int statisti
     const MarchGeom mg(Y, X, hw, statistic, nplanes);
     if(mg.ok) {   // both passes in one kernel (k_box_march)
         const BoxMarch kernel = box_march(std::make_integer_sequence<int, BM_MAXHW + 1>(), hw);
-        hipLaunchKernelGGL(kernel, mg.grid(nseg, nplanes), dim3(256), bm_lds_bytes(hw), stream(), d_in, Y, X, statistic, d_out, qf_reps, mg.SH, seg0);
-        GPP_HIP(hipGetLastError());
+        launch(kernel, mg.grid(nseg, nplanes), 256, bm_lds_bytes(hw), d_in, Y, X, statistic, d_out, qf_reps, mg.SH, seg0);
         return;
     }
     long n = (long)Y * X * nplanes;
@@ -1271,25 +1260,21 @@ void box_stat(const float* d_in, int Y, int X, int nplanes, int hw, int statisti
     for(int ybase = 0; ybase < Y; ybase += 65535) {   // gridDim.y is a 16-bit quantity
         const int ny = std::min(65535, Y - ybase);
         if(wide)
-            hipLaunchKernelGGL(k_box_rows_wide, dim3(1, ny, nplanes), dim3(256), 0, stream(), d_in, Y, X, hw, rs, rc, flags, ybase);
+            launch(k_box_rows_wide, dim3(1, ny, nplanes), 256, 0, d_in, Y, X, hw, rs, rc, flags, ybase);
         else if(hwc <= 1024 && hwc > 0 && !path_env("GPP_BOX_ROWS_DIRECT")) {
             const int ntap = ROWS4_TILE + 2 * hwc;
-            hipLaunchKernelGGL(k_box_rows4, dim3((X + ROWS4_TILE - 1) / ROWS4_TILE, ny, nplanes), dim3(256), (size_t)(ntap + (ntap >> 2) + 4) * sizeof(float), stream(),
-                               d_in, Y, X, hw, rs, rc, flags, ybase);
+            launch(k_box_rows4, dim3((X + ROWS4_TILE - 1) / ROWS4_TILE, ny, nplanes), 256, (size_t)(ntap + (ntap >> 2) + 4) * sizeof(float), d_in, Y, X, hw, rs, rc, flags, ybase);
         }
         else
-            hipLaunchKernelGGL(k_box_rows, dim3((X + 255) / 256, ny, nplanes), dim3(256), (256 + 2 * hwc) * sizeof(float), stream(), d_in, Y, X, hw, rs, rc, flags, ybase);
-        GPP_HIP(hipGetLastError());
+            launch(k_box_rows, dim3(blocks_of(X), ny, nplanes), 256, (256 + 2 * hwc) * sizeof(float), d_in, Y, X, hw, rs, rc, flags, ybase);
     }
-    hipLaunchKernelGGL(k_box_cols, dim3((X + 255) / 256, (Y + COL_STRIP - 1) / COL_STRIP, nplanes), dim3(256), 0, stream(), rs, rc, Y, X, hw, statistic, d_out, qf_reps, flags);
-    GPP_HIP(hipGetLastError());
+    launch(k_box_cols, dim3(blocks_of(X), (Y + COL_STRIP - 1) / COL_STRIP, nplanes), 256, 0, rs, rc, Y, X, hw, statistic, d_out, qf_reps, flags);
 }
 void brute(const float* d_in, int Y, int X, int E, int hw, int statistic, float q, float* d_out) {
     long C = (long)Y * X;
     static std::atomic<unsigned> seed_state{12345u};
     const unsigned seed = seed_state.fetch_add(1013904223u) * 1664525u + 1013904223u;
-    hipLaunchKernelGGL(k_brute, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, stream(), d_in, Y, X, E, hw, statistic, q, seed, d_out);
-    GPP_HIP(hipGetLastError());
+    launch(k_brute, (unsigned)((C + 3) / 4), 256, 0, d_in, Y, X, E, hw, statistic, q, seed, d_out);
 }
 // neighbourhood(vec2, hw, stat) on a device-resident plane (neighbourhood.cpp:28-242)
 void neighbourhood2d(const float* d_in, int Y, int X, int hw, int statistic, float* d_out, int seg0 = 0, int nseg = -1) {
@@ -1298,16 +1283,14 @@ void neighbourhood2d(const float* d_in, int Y, int X, int hw, int statistic, flo
     const MarchGeom mg(Y, X, hw, statistic);   // (of Min and Max: !ok for every other statistic)
     if(mg.ok) {   // both passes in one kernel (k_minmax_march)
         const MinMaxForm& f = minmax_march(std::make_integer_sequence<int, BM_MM_MAXHW + 1>(), hw);
-        hipLaunchKernelGGL(statistic == GPP_MAX ? f.max : f.min, mg.grid(nseg), dim3(256), f.lds, stream(), d_in, Y, X, d_out, mg.SH, seg0);
-        GPP_HIP(hipGetLastError());
+        launch(statistic == GPP_MAX ? f.max : f.min, mg.grid(nseg), 256, f.lds, d_in, Y, X, d_out, mg.SH, seg0);
     }
     else if(statistic == GPP_MIN || statistic == GPP_MAX) {
         float* t = g_nb.tmp.get(C);
         for(int dir = 1; dir >= 0; --dir)
             for(int ybase = 0; ybase < Y; ybase += 4 * 65535) {
                 const dim3 grid((X + 63) / 64, (std::min(4 * 65535, Y - ybase) + 3) / 4);
-                hipLaunchKernelGGL(k_minmax_pass, grid, dim3(256), 0, stream(), dir ? d_in : (const float*)t, Y, X, hw, statistic == GPP_MAX, dir, dir ? t : d_out, ybase);
-                GPP_HIP(hipGetLastError());
+                launch(k_minmax_pass, grid, 256, 0, dir ? d_in : (const float*)t, Y, X, hw, statistic == GPP_MAX, dir, dir ? t : d_out, ybase);
             }
     }
     else if(statistic == GPP_STD || statistic == GPP_VARIANCE) {
@@ -1315,10 +1298,9 @@ void neighbourhood2d(const float* d_in, int Y, int X, int hw, int statistic, flo
         float* sq = g_nb.tmp2.get(2 * C);
         float* mean2 = sq + C;
         box_stat(d_in, Y, X, 1, hw, GPP_MEAN, mean);
-        hipLaunchKernelGGL(k_square, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), d_in, C, sq);
+        launch(k_square, blocks_of(C), 256, 0, d_in, C, sq);
         box_stat(sq, Y, X, 1, hw, GPP_MEAN, mean2);
-        hipLaunchKernelGGL(k_std_finish, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)mean, (const float*)mean2, C, statistic == GPP_STD, d_out);
-        GPP_HIP(hipGetLastError());
+        launch(k_std_finish, blocks_of(C), 256, 0, (const float*)mean, (const float*)mean2, C, statistic == GPP_STD, d_out);
     }
     else brute(d_in, Y, X, 1, hw, statistic, 0.0f, d_out);   // Median, RandomChoice (:236-238)
 }
@@ -1333,7 +1315,7 @@ void check_stat(int s) {
 struct Fields {
     InField in; OutField o;
     void bind(const float* src, size_t nin, float* dst, size_t nout, int mem) { in.bind(src, nin, mem); o.bind(dst, nout, mem); }
-    int done() { o.finish(); GPP_HIP(hipStreamSynchronize(stream())); return GPP_OK; }
+    int done() { return finish_call(o); }
 };
 
 // One gpp_neighbourhood call on the host, a local of the entry point below.  The banded host path (round 6): a large 2-D plane in host memory (numpy in, numpy out: 64 MB up,
@@ -1379,8 +1361,7 @@ struct NbhCall : Fields {
         if(!(mem & GPP_HOST_F64)) GPP_HIP(hipMemcpyAsync(d_in + off, input + off, cnt * sizeof(float), hipMemcpyHostToDevice, s));
         else {
             GPP_HIP(hipMemcpyAsync(wide.p + off, reinterpret_cast<const double*>(input) + off, cnt * sizeof(double), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_stage_f64, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, (const double*)(wide.p + off), cnt, d_in + off);
-            GPP_HIP(hipGetLastError());
+            launch_on(s, k_stage_f64, blocks_of(cnt), 256, 0, (const double*)(wide.p + off), cnt, d_in + off);
         }
         up = need;
     }
@@ -1477,8 +1458,7 @@ struct QfCall : Fields {
         if(fused) rowflag = ws.plane_flags.get(ny + 2);
         if(ranked) {
             lut = reinterpret_cast<QfLut*>(ws.qf.get((sizeof(QfLut) + 3) / 4));
-            hipLaunchKernelGGL(k_qf_lut, dim3(1), dim3(QF_NB), 0, stream(), th.d, nt, lut, rowflag, fused ? ny + 2 : 0);
-            GPP_HIP(hipGetLastError());
+            launch(k_qf_lut, 1, QF_NB, 0, th.d, nt, lut, rowflag, fused ? ny + 2 : 0);
             if(!spec) GPP_HIP(hipMemcpyAsync(lut_head, lut, sizeof(lut_head), hipMemcpyDeviceToHost, stream()));
         }
         else if(fused) GPP_HIP(hipMemsetAsync(rowflag, 0, sizeof(int) * (ny + 2), stream()));
@@ -1534,10 +1514,9 @@ struct QfCall : Fields {
         member_pass(in.d, C, ne, 1, 0, th.d, nt, planes);                 // fractions per threshold (:453-472)
         // stats[t] = neighbourhood(temp, hw, Mean) (:473) with the yarray epilogue (:494-506) fused into the column pass
         box_stat(planes, ny, nx, nt, halfwidth, GPP_MEAN, stats, is3d ? ne : 1);
-        if(!multi) hipLaunchKernelGGL(k_qf_interp, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
-        else if(multi == QF_LEVELS) hipLaunchKernelGGL(k_qf_interp_multi, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, th.d, qf.d, nq, o.d);
-        else hipLaunchKernelGGL(k_qf_cdf_copy, dim3((unsigned)((C * nt + 255) / 256)), dim3(256), 0, stream(), (const float*)stats, C, nt, o.d);
-        GPP_HIP(hipGetLastError());
+        if(!multi) launch(k_qf_interp, blocks_of(C), 256, 0, (const float*)stats, C, nt, th.d, qf.d, nq == 1 ? 0 : 1, o.d);
+        else if(multi == QF_LEVELS) launch(k_qf_interp_multi, blocks_of(C), 256, 0, (const float*)stats, C, nt, th.d, qf.d, nq, o.d);
+        else launch(k_qf_cdf_copy, blocks_of(C * nt), 256, 0, (const float*)stats, C, nt, o.d);
     }
     int run() {   // the rounds of a call whose arguments are checked and whose device is there
         bind_fields();
@@ -1555,8 +1534,7 @@ struct QfCall : Fields {
 // k_std_finish over any number of elements, for members.hip: the per-member Std / Variance of a cube ends in the kernel of the 2-D call itself
 namespace gpp {
 void std_finish_launch(const float* mean, const float* mean2, long n, int is_std, float* out) {
-    hipLaunchKernelGGL(k_std_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), mean, mean2, n, is_std, out);
-    GPP_HIP(hipGetLastError());
+    launch(k_std_finish, blocks_of(n), 256, 0, mean, mean2, n, is_std, out);
 }
 }   // namespace gpp
 
@@ -1645,8 +1623,7 @@ extern "C" int gpp_calc_statistic(const float* array, long rows, int len, int st
     f.bind(array, (size_t)rows * len, out, rows, mem);
     if(statistic == GPP_MEDIAN) rows_quantile(f.in.d, rows, len, nullptr, 0, f.o.d);
     else if(len <= MEMBER_EC && len > 0) member_pass(f.in.d, rows, len, 0, statistic, nullptr, 0, f.o.d);
-    else hipLaunchKernelGGL(k_rows_statistic, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), f.in.d, rows, len, statistic, f.o.d);
-    GPP_HIP(hipGetLastError());
+    else launch(k_rows_statistic, blocks_of(rows), 256, 0, f.in.d, rows, len, statistic, f.o.d);
     return f.done();
     GPP_CATCH
 }
@@ -1674,7 +1651,7 @@ __global__ void k_count_equal(const float* __restrict__ v, long n, float x, unsi
     unsigned long long m = __ballot(eq);
     if((threadIdx.x & 63) == 0 && m) atomicAdd(cnt, (unsigned long long)__popcll(m));
 }
-struct IsValidF { __device__ bool operator()(const float& v) const { return !isnan(v) && !isinf(v); } };
+struct IsValidF { __device__ bool operator()(const float& v) const { return dev_valid(v); } };
 
 // gridpp::calc_even_quantiles (util.cpp:261-338) on the valid values of `values`; the global sort and the
 // unique pass run on the device (rocPRIM radix sort / select / unique), the index picks on the host.
@@ -1727,7 +1704,7 @@ extern "C" int gpp_calc_even_quantiles(const float* values, long n, int num, int
     else {
         const float lowest = fetch(uniq.p, 0), highest = fetch(uniq.p, nu - 1);
         GPP_HIP(hipMemsetAsync(dcnt.p, 0, sizeof(unsigned long long), stream()));
-        hipLaunchKernelGGL(k_count_equal, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream(), (const float*)sorted.p, (long)size, lowest, dcnt.p);
+        launch(k_count_equal, blocks_of(size), 256, 0, (const float*)sorted.p, (long)size, lowest, dcnt.p);
         unsigned long long cl = 0;
         GPP_HIP(hipMemcpyAsync(&cl, dcnt.p, sizeof(cl), hipMemcpyDeviceToHost, stream()));
         GPP_HIP(hipStreamSynchronize(stream()));

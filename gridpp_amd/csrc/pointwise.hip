@@ -117,12 +117,9 @@ struct PointwiseWorkspace {
 thread_local PointwiseWorkspace g_pw;
 
 template <class Op, int VEC, bool IN64>
-void launch(const Op& op, const Inputs<Op::NIN>& in, long long nvec, long long first, float* out, unsigned long long* status) {
+void launch_vec(const Op& op, const Inputs<Op::NIN>& in, long long nvec, long long first, float* out, unsigned long long* status) {
     if(nvec <= 0) return;
-    const long long want = (nvec + GPP_POINTWISE_BLOCK - 1) / GPP_POINTWISE_BLOCK;
-    const unsigned blocks = (unsigned)(want < GPP_POINTWISE_MAX_BLOCKS ? want : GPP_POINTWISE_MAX_BLOCKS);
-    hipLaunchKernelGGL((k_pointwise<Op, Op::NIN, VEC, IN64>), dim3(blocks), dim3(GPP_POINTWISE_BLOCK), 0, stream(), op, in, nvec, first, out, status);
-    GPP_HIP(hipGetLastError());
+    launch(k_pointwise<Op, Op::NIN, VEC, IN64>, grid_capped(blocks_of(nvec, GPP_POINTWISE_BLOCK), GPP_POINTWISE_MAX_BLOCKS), GPP_POINTWISE_BLOCK, 0, op, in, nvec, first, out, status);
 }
 
 // the wide launch over the first 4 * (n / 4) values where every pointer is 16-byte aligned, one value per lane for the rest
@@ -131,11 +128,11 @@ void launch_both(const Op& op, const Inputs<Op::NIN>& in, long long n, float* ou
     uintptr_t bits = (uintptr_t)out;
     for(int a = 0; a < Op::NIN; a++) bits |= (uintptr_t)in.p[a];
     const long long n4 = (bits & 15) == 0 ? n / 4 : 0;
-    launch<Op, 4, IN64>(op, in, n4, 0, out, status);
+    launch_vec<Op, 4, IN64>(op, in, n4, 0, out, status);
     Inputs<Op::NIN> tail;
     for(int a = 0; a < Op::NIN; a++)
         tail.p[a] = IN64 ? (const void*)(static_cast<const double*>(in.p[a]) + 4 * n4) : (const void*)(static_cast<const float*>(in.p[a]) + 4 * n4);
-    launch<Op, 1, IN64>(op, tail, n - 4 * n4, 4 * n4, out + 4 * n4, status);
+    launch_vec<Op, 1, IN64>(op, tail, n - 4 * n4, 4 * n4, out + 4 * n4, status);
 }
 
 const char* slp_message(int code) {   // pressure.cpp:32-38

@@ -32,16 +32,6 @@ namespace {
 #define QB_SH 64        // output rows per workgroup (plus 2 HW + 1 rows of run-in)
 #endif
 
-// a workgroup barrier that orders LDS accesses only (the threads of a workgroup share nothing else; __syncthreads also waits for the global
-// stores of the interpolation stage)
-__device__ __forceinline__ void qb_lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-__device__ __forceinline__ bool qb_nv(float v) { return !isnan(v) && !isinf(v); }
-
 // 8 * byte I of the dword array w (I is a constant after unrolling): one instruction, the byte offset of a table entry
 __device__ __forceinline__ unsigned qb_byte_x8(const unsigned (&w)[QB_NDW], const int i) {
     unsigned a;
@@ -83,12 +73,12 @@ __device__ __forceinline__ void qb_windows(Val val, Acc acc) {
 
 __device__ float qb_interp(const float* __restrict__ ya, const int stride, const int T, const float* __restrict__ thr, const float x) {
     bool missing = false;
-    for(int t = 0; t < T; t++) if(!qb_nv(ya[t * stride])) missing = true;
+    for(int t = 0; t < T; t++) if(!dev_valid(ya[t * stride])) missing = true;
     if(missing) return NAN;
     const float y0a = ya[0], yLa = ya[(T - 1) * stride];
     if(x == 1 && y0a == 1) return thr[0];                     // neighbourhood.cpp:508-513
     if(x == 0 && yLa == 0) return thr[T - 1];
-    if(!qb_nv(x)) return NAN;                                  // interpolate(): util.cpp:378-379
+    if(!dev_valid(x)) return NAN;                                  // interpolate(): util.cpp:378-379
     if(x > yLa) return thr[T - 1];                             // util.cpp:386-389
     if(x < y0a) return thr[0];
     int i0 = -1, i1 = -1;                                      // get_lower_index / get_upper_index (util.cpp:339-376)
@@ -133,7 +123,7 @@ __device__ float qb_interp_lazy(float* __restrict__ ya, const int stride, const 
     unsigned done = 0, amb = 0;          // bit t: ya[t] holds F(o_t) / o_t is not clearly on one side of x
     for(int t = 0; t < T; t++) {
         const float v = ya[t * stride];
-        if(!qb_nv(v)) missing = true;
+        if(!dev_valid(v)) missing = true;
         if(v == 0.0f || v == 1.0f || reps <= 1) done |= 1u << t;
         else if(!(v * 1.000012f < x) && !(v * 0.999988f > x)) amb |= 1u << t;   // (a NaN quantile lands here too)
     }
@@ -160,7 +150,7 @@ __device__ float qb_interp_lazy(float* __restrict__ ya, const int stride, const 
     const float y0a = ya[0], yLa = ya[(T - 1) * stride];
     if(x == 1 && y0a == 1) return thr[0];                     // neighbourhood.cpp:508-513
     if(x == 0 && yLa == 0) return thr[T - 1];
-    if(!qb_nv(x)) return NAN;                                  // interpolate(): util.cpp:378-379
+    if(!dev_valid(x)) return NAN;                                  // interpolate(): util.cpp:378-379
     if(x > yLa) return thr[T - 1];                             // util.cpp:386-389
     if(x < y0a) return thr[0];
     int i0 = -1, i1 = -1;                                      // get_lower_index / get_upper_index (util.cpp:339-376)
@@ -341,7 +331,7 @@ __device__ __forceinline__ void qb_march(const unsigned char* __restrict__ cnt8,
             }
             if constexpr (LAZY) {
 #pragma unroll
-            for(int j = 0; j < QB_SEG; j++) yab[p * QB_SW + s * QB_SEG + j] = qb_nv(o[j]) ? o[j] : NAN;   // the means: F where interpolate() looks, qb_interp_lazy
+            for(int j = 0; j < QB_SEG; j++) yab[p * QB_SW + s * QB_SEG + j] = dev_valid(o[j]) ? o[j] : NAN;   // the means: F where interpolate() looks, qb_interp_lazy
             (void)acc;
             }
             else {
@@ -379,11 +369,11 @@ __device__ __forceinline__ void qb_march(const unsigned char* __restrict__ cnt8,
                 // rounding boundary, the double product is within 2^-52 of it)
                 float yv = reps > 1 ? (float)((double)acc[j] * rreps) : o[j];
                 yv = yv > 1 ? 1.0f : (yv < 0 ? 0.0f : yv);
-                yab[MODE == 1 ? (s * QB_SEG + j) * T + p : p * QB_SW + s * QB_SEG + j] = qb_nv(o[j]) ? yv : NAN;
+                yab[MODE == 1 ? (s * QB_SEG + j) * T + p : p * QB_SW + s * QB_SEG + j] = dev_valid(o[j]) ? yv : NAN;
             }
             }
         }
-        qb_lds_barrier();
+        lds_barrier();   // (the threads of a workgroup share nothing but LDS; __syncthreads would also wait for the global stores of the interpolation stage)
         if constexpr (MODE == 1) {
             // the step's run of the result: ncols cells x T (cdf) or x qstride (levels) floats, contiguous in `out`; lane i writes float i
             const int ncols = min(QB_SW, X - xs);
@@ -448,17 +438,16 @@ void launch_hw(const unsigned char* cnt8, const QfGeom& g, int reps, int T, cons
     const int SH = std::max(1, (g.Y + segs - 1) / segs);
     const dim3 grid(strips, (g.Y + SH - 1) / SH);
     if(!multi) {
-        hipLaunchKernelGGL((k_qf_box<HW, false>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
-        hipLaunchKernelGGL((k_qf_box<HW, true>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
+        launch_on(st, k_qf_box<HW, false>, grid, threads, lds, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
+        launch_on(st, k_qf_box<HW, true>, grid, threads, lds, cnt8, g, reps, T, d_thr, d_q, qfield, d_out, SH);
     }
     else {
         for(int q0 = 0; q0 < std::max(nq, 1); q0 += QB_MAXQ) {
             const int n = std::min(QB_MAXQ, nq - q0);   // (0: the cdf)
-            hipLaunchKernelGGL((k_qf_box_multi<HW, false>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q + q0, n, nq, d_out + q0, SH);
-            hipLaunchKernelGGL((k_qf_box_multi<HW, true>), grid, dim3(threads), lds, st, cnt8, g, reps, T, d_thr, d_q + q0, n, nq, d_out + q0, SH);
+            launch_on(st, k_qf_box_multi<HW, false>, grid, threads, lds, cnt8, g, reps, T, d_thr, d_q + q0, n, nq, d_out + q0, SH);
+            launch_on(st, k_qf_box_multi<HW, true>, grid, threads, lds, cnt8, g, reps, T, d_thr, d_q + q0, n, nq, d_out + q0, SH);
         }
     }
-    GPP_HIP(hipGetLastError());
 }
 void launch_any(const unsigned char* cnt8, const QfGeom& g, int reps, int hw, int T, const float* d_thr, const float* d_q, int qfield, float* d_out, hipStream_t st,
                 const bool multi, const int nq) {

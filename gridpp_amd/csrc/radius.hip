@@ -78,14 +78,14 @@ __global__ __launch_bounds__(256) void k_radius_statistic(IxView ix, const float
     visit_radius(ix, qx[q], qy[q], qz[q], radius, true, [&](int, int orig, float) {
         ++c;
         const float v = values[orig];
-        if(!nv(v)) return;
+        if(!dev_valid(v)) return;
         if(spread) {
-            if(!nv(K)) K = v;
+            if(!dev_valid(K)) K = v;
             const float d = v - K;
             total += d; total2 += d * d;
         }
         else if(lo || hi) {
-            if(!nv(m)) m = v;
+            if(!dev_valid(m)) m = v;
             else if(lo ? v < m : v > m) m = v;
         }
         else total += v;
@@ -149,14 +149,14 @@ __global__ __launch_bounds__(256) void k_radius_statistic_wave(IxView ix, const 
                     const int b = __ffsll((long long)mask) - 1;
                     mask &= mask - 1;
                     const float vb = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), b));
-                    if(!nv(vb)) continue;
+                    if(!dev_valid(vb)) continue;
                     if(spread) {
-                        if(!nv(K)) K = vb;
+                        if(!dev_valid(K)) K = vb;
                         const float d = vb - K;
                         total += d; total2 += d * d;
                     }
                     else if(lo || hi) {
-                        if(!nv(m)) m = vb;
+                        if(!dev_valid(m)) m = vb;
                         else if(lo ? vb < m : vb > m) m = vb;
                     }
                     else total += vb;
@@ -217,13 +217,9 @@ extern "C" int gpp_count(gpp_points* from, gpp_points* to, float radius, float* 
     else {
         to->to_device();
         gpp_obs_index* ix = gpp_build_obs_index(from);
-        hipLaunchKernelGGL(k_radius_count, dim3((nq + 255) / 256), dim3(256), 0, stream(), view_of(ix), to->d_x.p, to->d_y.p, to->d_z.p, nq,
-                           radius, 1, (int*)nullptr, o.d);
+        launch(k_radius_count, blocks_of(nq), 256, 0, view_of(ix), to->d_x.p, to->d_y.p, to->d_z.p, nq, radius, 1, (int*)nullptr, o.d);
     }
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -257,19 +253,12 @@ extern "C" int gpp_gridding(gpp_points* to, gpp_points* from, const float* value
                              statistic == GPP_VARIANCE || statistic == GPP_MIN || statistic == GPP_MAX;
         if(streams && !path_env("GPP_GRIDDING_CSR")) {
             if(path_env("GPP_GRIDDING_THREAD"))
-                hipLaunchKernelGGL(k_radius_statistic, dim3((nq + 255) / 256), dim3(256), 0, stream(), iv, to->d_x.p, to->d_y.p, to->d_z.p, nq, radius,
-                                   v.d, min_num, statistic, o.d);
+                launch(k_radius_statistic, blocks_of(nq), 256, 0, iv, to->d_x.p, to->d_y.p, to->d_z.p, nq, radius, v.d, min_num, statistic, o.d);
             else
-                hipLaunchKernelGGL(k_radius_statistic_wave, dim3((nq + 3) / 4), dim3(256), 0, stream(), iv, to->d_x.p, to->d_y.p, to->d_z.p, nq, radius,
-                                   v.d, min_num, statistic, o.d);
-            GPP_HIP(hipGetLastError());
-            o.finish();
-            GPP_HIP(hipStreamSynchronize(stream()));
-            return GPP_OK;
+                launch(k_radius_statistic_wave, (nq + 3) / 4, 256, 0, iv, to->d_x.p, to->d_y.p, to->d_z.p, nq, radius, v.d, min_num, statistic, o.d);
+            return finish_call(o);
         }
-        hipLaunchKernelGGL(k_radius_count, dim3((nq + 255) / 256), dim3(256), 0, stream(), iv, to->d_x.p, to->d_y.p, to->d_z.p, nq, radius, 1,
-                           cnt.p, (float*)nullptr);
-        GPP_HIP(hipGetLastError());
+        launch(k_radius_count, blocks_of(nq), 256, 0, iv, to->d_x.p, to->d_y.p, to->d_z.p, nq, radius, 1, cnt.p, (float*)nullptr);
         const long long total = scan_counts(cnt.p, nq, wide, offset);
         for(auto ch : chunks_of(offset, nq, total)) {
             const int q0 = ch.first, n = ch.second - ch.first;
@@ -280,19 +269,12 @@ extern "C" int gpp_gridding(gpp_points* to, gpp_points* from, const float* value
             }
             else end = total;
             val.get((size_t)std::max<long long>(end - base, 1));
-            hipLaunchKernelGGL(k_radius_fill, dim3((n + 255) / 256), dim3(256), 0, stream(), iv, to->d_x.p, to->d_y.p, to->d_z.p, q0, n, radius, 1,
-                               offset.p, base, (int*)nullptr, (float*)nullptr, v.d, val.p);
-            hipLaunchKernelGGL(k_segment_statistic, dim3((n + 255) / 256), dim3(256), 0, stream(), val.p, offset.p, base, cnt.p, q0, n, min_num,
-                               statistic, 0, o.d);
-            GPP_HIP(hipGetLastError());
+            launch(k_radius_fill, blocks_of(n), 256, 0, iv, to->d_x.p, to->d_y.p, to->d_z.p, q0, n, radius, 1, offset.p, base, (int*)nullptr, (float*)nullptr, v.d, val.p);
+            launch(k_segment_statistic, blocks_of(n), 256, 0, val.p, offset.p, base, cnt.p, q0, n, min_num, statistic, 0, o.d);
         }
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        return finish_call(o);
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -309,7 +291,7 @@ void gpp_gridding_nearest_device(gpp_points* to, gpp_points* from, const float* 
     DevBuf<int> target, starget, order, iota, cnt;
     target.get(S); starget.get(S); order.get(S); iota.get(S); cnt.get(no);
     gpp_nearest_device(to, from->d_x.p, from->d_y.p, from->d_z.p, S, 1, target.p);   // gridding.cpp:85-90
-    hipLaunchKernelGGL(k_iota, dim3((S + 255) / 256), dim3(256), 0, stream(), iota.p, S);
+    launch(k_iota, blocks_of(S), 256, 0, iota.p, S);
     // stable sort by target keeps the input order inside every location (the reference push_backs in input order)
     int bits = 1;
     while((1ll << bits) < no) bits++;
@@ -319,15 +301,13 @@ void gpp_gridding_nearest_device(gpp_points* to, gpp_points* from, const float* 
     tmp.get(sb);
     GPP_HIP(rocprim::radix_sort_pairs((void*)tmp.p, sb, target.p, starget.p, iota.p, order.p, (size_t)S, 0u, (unsigned)bits, stream()));
     GPP_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * no, stream()));
-    hipLaunchKernelGGL(k_histogram, dim3((S + 255) / 256), dim3(256), 0, stream(), target.p, S, cnt.p);
+    launch(k_histogram, blocks_of(S), 256, 0, target.p, S, cnt.p);
     DevBuf<long long> wide, offset;
     scan_counts(cnt.p, no, wide, offset);
     DevBuf<float> val;
     val.get(S);
-    hipLaunchKernelGGL(k_gather_sorted, dim3((S + 255) / 256), dim3(256), 0, stream(), d_values, order.p, S, val.p);
-    hipLaunchKernelGGL(k_segment_statistic, dim3((no + 255) / 256), dim3(256), 0, stream(), val.p, offset.p, 0ll, cnt.p, 0, no, min_num, statistic,
-                       1, d_out);
-    GPP_HIP(hipGetLastError());
+    launch(k_gather_sorted, blocks_of(S), 256, 0, d_values, order.p, S, val.p);
+    launch(k_segment_statistic, blocks_of(no), 256, 0, val.p, offset.p, 0ll, cnt.p, 0, no, min_num, statistic, 1, d_out);
     GPP_HIP(hipStreamSynchronize(stream()));   // the workspaces above are freed on return
 }
 
@@ -349,9 +329,7 @@ extern "C" int gpp_gridding_nearest(gpp_points* to, gpp_points* from, const floa
         v.bind(values, S, mem);
     }
     gpp_gridding_nearest_device(to, from, v.d, min_num, statistic, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -380,9 +358,7 @@ extern "C" int gpp_points_get_neighbours_batch(gpp_points* p, const float* qlats
     const IxView iv = view_of(ix);
     DevBuf<int> cnt;
     cnt.get(nq);
-    hipLaunchKernelGGL(k_radius_count, dim3((nq + 255) / 256), dim3(256), 0, stream(), iv, dx.p, dy.p, dz.p, nq, radius, include_match, cnt.p,
-                       (float*)nullptr);
-    GPP_HIP(hipGetLastError());
+    launch(k_radius_count, blocks_of(nq), 256, 0, iv, dx.p, dy.p, dz.p, nq, radius, include_match, cnt.p, (float*)nullptr);
     DevBuf<long long> wide, offset;
     const long long tot = scan_counts(cnt.p, nq, wide, offset);
     *total = tot;
@@ -394,9 +370,7 @@ extern "C" int gpp_points_get_neighbours_batch(gpp_points* p, const float* qlats
     DevBuf<float> ddist;
     didx.get((size_t)tot);
     ddist.get((size_t)tot);
-    hipLaunchKernelGGL(k_radius_fill, dim3((nq + 255) / 256), dim3(256), 0, stream(), iv, dx.p, dy.p, dz.p, 0, nq, radius, include_match, offset.p,
-                       0ll, didx.p, ddist.p, (const float*)nullptr, (float*)nullptr);
-    GPP_HIP(hipGetLastError());
+    launch(k_radius_fill, blocks_of(nq), 256, 0, iv, dx.p, dy.p, dz.p, 0, nq, radius, include_match, offset.p, 0ll, didx.p, ddist.p, (const float*)nullptr, (float*)nullptr);
     std::vector<int> hi((size_t)tot);
     std::vector<float> hd((size_t)tot);
     GPP_HIP(hipMemcpyAsync(hi.data(), didx.p, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, stream()));
@@ -466,8 +440,7 @@ extern "C" int gpp_points_get_closest_neighbours(gpp_points* p, float lat, float
     DevBuf<unsigned> key, skey;
     DevBuf<int> idx, sidx;
     key.get(n); skey.get(n); idx.get(n); sidx.get(n);
-    hipLaunchKernelGGL(k_dist2_keys, dim3((n + 255) / 256), dim3(256), 0, stream(), p->d_x.p, p->d_y.p, p->d_z.p, n, qx, qy, qz, include_match, key.p, idx.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_dist2_keys, blocks_of(n), 256, 0, p->d_x.p, p->d_y.p, p->d_z.p, n, qx, qy, qz, include_match, key.p, idx.p);
     size_t sb = 0;
     GPP_HIP(rocprim::radix_sort_pairs((void*)nullptr, sb, key.p, skey.p, idx.p, sidx.p, (size_t)n, 0u, 32u, stream()));
     DevBuf<char> tmp;
@@ -580,15 +553,11 @@ extern "C" int gpp_distance(gpp_points* from, gpp_points* to, int num, int query
         skey.get((size_t)slab * k); sidx.get((size_t)slab * k);
         for(int q0 = 0; q0 < nq; q0 += slab) {
             const int m = std::min(slab, nq - q0);
-            hipLaunchKernelGGL(k_knn_max_distance, dim3((m + 255) / 256), dim3(256), 0, stream(), view_of(ix), from->d_lat.p, from->d_lon.p, from->n,
-                               to->d_x.p + q0, to->d_y.p + q0, to->d_z.p + q0, to->d_lat.p + q0, to->d_lon.p + q0, m, num, from->type, query_first,
-                               skey.p, sidx.p, o.d + q0);
+            launch(k_knn_max_distance, blocks_of(m), 256, 0, view_of(ix), from->d_lat.p, from->d_lon.p, from->n, to->d_x.p + q0, to->d_y.p + q0, to->d_z.p + q0, to->d_lat.p + q0,
+                   to->d_lon.p + q0, m, num, from->type, query_first, skey.p, sidx.p, o.d + q0);
         }
     }
-    GPP_HIP(hipGetLastError());
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -661,25 +630,18 @@ extern "C" int gpp_staticcorr_points(gpp_points* points, gpp_points* knots, cons
     const IxView iv = view_of(ix);
     DevBuf<int> cnt;
     cnt.get(nY);
-    hipLaunchKernelGGL(k_staticcorr_candidates, dim3((nY + 255) / 256), dim3(256), 0, stream(), iv, d, points->d_x.p, points->d_y.p, points->d_z.p,
-                       points->d_elev.p, points->d_laf.p, nY, cnt.p, (const long long*)nullptr, (unsigned long long*)nullptr);
-    GPP_HIP(hipGetLastError());
+    launch(k_staticcorr_candidates, blocks_of(nY), 256, 0, iv, d, points->d_x.p, points->d_y.p, points->d_z.p, points->d_elev.p, points->d_laf.p, nY, cnt.p,
+           (const long long*)nullptr, (unsigned long long*)nullptr);
     DevBuf<long long> wide, offset;
     const long long tot = scan_counts(cnt.p, nY, wide, offset);
     if(tot > 0) {
         DevBuf<unsigned long long> keys;
         keys.get((size_t)tot);
-        hipLaunchKernelGGL(k_staticcorr_candidates, dim3((nY + 255) / 256), dim3(256), 0, stream(), iv, d, points->d_x.p, points->d_y.p, points->d_z.p,
-                           points->d_elev.p, points->d_laf.p, nY, cnt.p, offset.p, keys.p);
-        hipLaunchKernelGGL(k_staticcorr_write, dim3((nY + 255) / 256), dim3(256), 0, stream(), keys.p, offset.p, cnt.p, nY, nS, max_points, o.d);
-        GPP_HIP(hipGetLastError());
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        launch(k_staticcorr_candidates, blocks_of(nY), 256, 0, iv, d, points->d_x.p, points->d_y.p, points->d_z.p, points->d_elev.p, points->d_laf.p, nY, cnt.p, offset.p, keys.p);
+        launch(k_staticcorr_write, blocks_of(nY), 256, 0, keys.p, offset.p, cnt.p, nY, nS, max_points, o.d);
+        return finish_call(o);
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -757,9 +719,7 @@ extern "C" int gpp_smart(gpp_points* igrid, gpp_points* ogrid, const float* valu
     o.bind(out, nq, mem);
     if(igrid->n == 0 || num <= 0) {   // no candidate / nothing kept: count == 0 (smart.cpp:59-61)
         fill_f32(o.d, (size_t)nq, NAN);
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        return finish_call(o);
     }
     if(!values) invalid("values is NULL");
     InField v;
@@ -769,9 +729,8 @@ extern "C" int gpp_smart(gpp_points* igrid, gpp_points* ogrid, const float* valu
     const IxView iv = view_of(ix);
     DevBuf<int> cnt;
     cnt.get(nq);
-    hipLaunchKernelGGL(k_smart_candidates, dim3((nq + 255) / 256), dim3(256), 0, stream(), iv, d, ogrid->d_x.p, ogrid->d_y.p, ogrid->d_z.p,
-                       ogrid->d_elev.p, ogrid->d_laf.p, 0, nq, cnt.p, (const long long*)nullptr, 0ll, (unsigned long long*)nullptr);
-    GPP_HIP(hipGetLastError());
+    launch(k_smart_candidates, blocks_of(nq), 256, 0, iv, d, ogrid->d_x.p, ogrid->d_y.p, ogrid->d_z.p, ogrid->d_elev.p, ogrid->d_laf.p, 0, nq, cnt.p, (const long long*)nullptr,
+           0ll, (unsigned long long*)nullptr);
     DevBuf<long long> wide, offset;
     const long long total = scan_counts(cnt.p, nq, wide, offset);
     DevBuf<unsigned long long> keys;
@@ -783,14 +742,10 @@ extern "C" int gpp_smart(gpp_points* igrid, gpp_points* ogrid, const float* valu
             GPP_HIP(hipMemcpy(&end, offset.p + ch.second, sizeof(long long), hipMemcpyDeviceToHost));
         }
         keys.get((size_t)std::max<long long>(end - base, 1));
-        hipLaunchKernelGGL(k_smart_candidates, dim3((n + 255) / 256), dim3(256), 0, stream(), iv, d, ogrid->d_x.p, ogrid->d_y.p, ogrid->d_z.p,
-                           ogrid->d_elev.p, ogrid->d_laf.p, q0, n, cnt.p, (const long long*)offset.p, base, keys.p);
-        hipLaunchKernelGGL(k_smart_mean, dim3((n + 255) / 256), dim3(256), 0, stream(), (const unsigned long long*)keys.p,
-                           (const long long*)offset.p, base, (const int*)cnt.p, q0, n, num, v.d, o.d);
-        GPP_HIP(hipGetLastError());
+        launch(k_smart_candidates, blocks_of(n), 256, 0, iv, d, ogrid->d_x.p, ogrid->d_y.p, ogrid->d_z.p, ogrid->d_elev.p, ogrid->d_laf.p, q0, n, cnt.p, (const long long*)offset.p,
+               base, keys.p);
+        launch(k_smart_mean, blocks_of(n), 256, 0, (const unsigned long long*)keys.p, (const long long*)offset.p, base, (const int*)cnt.p, q0, n, num, v.d, o.d);
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }

@@ -66,7 +66,7 @@ long long scan_counts(const int* cnt, int nq, DevBuf<long long>& wide, DevBuf<lo
     wide.get((size_t)nq + 1);
     offset.get((size_t)nq + 1);
     GPP_HIP(hipMemsetAsync(wide.p + nq, 0, sizeof(long long), stream()));
-    hipLaunchKernelGGL(k_widen, dim3((nq + 255) / 256), dim3(256), 0, stream(), cnt, nq, wide.p);
+    launch(k_widen, blocks_of(nq), 256, 0, cnt, nq, wide.p);
     size_t sb = 0;
     GPP_HIP(rocprim::exclusive_scan((void*)nullptr, sb, wide.p, offset.p, 0LL, (size_t)(nq + 1), rocprim::plus<long long>(), stream()));
     DevBuf<char> tmp;

@@ -5,14 +5,12 @@
 
 #pragma clang fp contract(off)
 
-__device__ __forceinline__ bool nv(float v) { return !isnan(v) && !isinf(v); }
-
 // src/api/util.cpp:19-110 on one row held in LDS (stride 1), sequential like the reference
 static __device__ float row_statistic(const float* row, int n, int statistic) {
     float value = NAN;
     if(statistic == GPP_MEAN || statistic == GPP_SUM || statistic == GPP_COUNT) {
         float total = 0; int count = 0;
-        for(int i = 0; i < n; i++) { float v = row[i]; if(nv(v)) { total += v; count++; } }
+        for(int i = 0; i < n; i++) { float v = row[i]; if(dev_valid(v)) { total += v; count++; } }
         if(statistic == GPP_COUNT) value = (float)count;
         else if(count > 0) value = (statistic == GPP_MEAN) ? total / (float)count : total;
     }
@@ -20,8 +18,8 @@ static __device__ float row_statistic(const float* row, int n, int statistic) {
         float total = 0, total2 = 0, K = NAN; int count = 0;
         for(int i = 0; i < n; i++) {
             float v = row[i];
-            if(nv(v)) {
-                if(!nv(K)) K = v;
+            if(dev_valid(v)) {
+                if(!dev_valid(K)) K = v;
                 float d = v - K;
                 total += d; total2 += d * d; count++;
             }
@@ -37,8 +35,8 @@ static __device__ float row_statistic(const float* row, int n, int statistic) {
         float m = NAN;
         for(int i = 0; i < n; i++) {
             float v = row[i];
-            if(!nv(v)) continue;
-            if(!nv(m)) m = v;
+            if(!dev_valid(v)) continue;
+            if(!dev_valid(m)) m = v;
             else if(statistic == GPP_MIN ? v < m : v > m) m = v;
         }
         value = m;
@@ -69,15 +67,15 @@ static __device__ float row_kth(const float* row, int n, int k) {
     while(lo < hi) {
         unsigned mid = lo + ((hi - lo) >> 1);
         int c = 0;
-        for(int i = 0; i < n; i++) { float v = row[i]; if(nv(v) && f2ord(v) <= mid) c++; }
+        for(int i = 0; i < n; i++) { float v = row[i]; if(dev_valid(v) && f2ord(v) <= mid) c++; }
         if(c >= k + 1) hi = mid; else lo = mid + 1;
     }
     return ord2f(lo);
 }
 static __device__ float row_quantile(const float* row, int n, float q) {   // util.cpp:111-178 (q already validated)
-    if(!nv(q)) return NAN;
+    if(!dev_valid(q)) return NAN;
     int N = 0;
-    for(int i = 0; i < n; i++) if(nv(row[i])) N++;
+    for(int i = 0; i < n; i++) if(dev_valid(row[i])) N++;
     if(N == 0) return NAN;
     if(q == 0) return row_statistic(row, n, GPP_MIN);
     if(q == 1) return row_statistic(row, n, GPP_MAX);

@@ -37,7 +37,7 @@ static int rq_min_levels(int len) {
 
 // one level out of a sorted row of keys with N valid ones; mn / mx: the positional Min / Max (read only for q == 0 / q == 1)
 __device__ __forceinline__ float rq_pick(const unsigned* sorted, int N, float q, float mn, float mx) {
-    if(!nv(q) || N == 0) return NAN;
+    if(!dev_valid(q) || N == 0) return NAN;
     if(q == 0) return mn;
     if(q == 1) return mx;
     int lo, up;
@@ -256,7 +256,6 @@ RqPath rq_choose(int len, int nq) {
     }
     return RQ_LOOP;
 }
-unsigned rq_magic(int d) { return (unsigned)((1ull << 32) / (unsigned)d + 1); }   // (unused for d == 1, where it does not fit)
 }   // namespace
 
 void rows_quantiles(const float* d_in, long rows, int len, const float* h_levels, int nq, float* d_out) {
@@ -273,16 +272,11 @@ void rows_quantiles(const float* d_in, long rows, int len, const float* h_levels
         // many waves fit a CU, and a guess one too high leaves 256 workgroups to run their share of the tiles alone at the end
         const long grid = std::min<long>((rows + 63) / 64, 1L << 20);
         const int vec_ok = (reinterpret_cast<size_t>(d_in) & 15) == 0;
-        hipLaunchKernelGGL(k_rowsq_tile, dim3((unsigned)grid), dim3(64), lds, stream(), d_in, rows, len, rq_magic(len), vec_ok, lv.p, nq, qc,
-                           rq_magic(qc), rq_magic(tail), ends, d_out);
+        launch(k_rowsq_tile, (unsigned)grid, 64, lds, d_in, rows, len, magic_div(len), vec_ok, lv.p, nq, qc, magic_div(qc), magic_div(tail), ends, d_out);
         break;
     }
     case RQ_BLOCK: {
-        int P = 2;
-        while(P < len) P <<= 1;
-        const size_t lds = (size_t)len * sizeof(unsigned);
-        hipLaunchKernelGGL(k_rowsq_block, dim3((unsigned)std::min<long>(rows, 1L << 20)), dim3(256), lds, stream(), d_in, rows, len, P, lv.p, nq, ends,
-                           d_out);
+        launch(k_rowsq_block, grid_capped(rows, (size_t)1 << 20), 256, (size_t)len * sizeof(unsigned), d_in, rows, len, pow2_at_least(len), lv.p, nq, ends, d_out);
         break;
     }
     default:
@@ -291,10 +285,9 @@ void rows_quantiles(const float* d_in, long rows, int len, const float* h_levels
         float* d_col = col.get((size_t)rows);
         for(int j = 0; j < nq; j++) {
             rows_quantile(d_in, rows, len, lv.p + j, 0, d_col);
-            hipLaunchKernelGGL(k_rowsq_scatter, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), d_col, rows, nq, j, d_out);
+            launch(k_rowsq_scatter, blocks_of(rows), 256, 0, d_col, rows, nq, j, d_out);
         }
     }
-    GPP_HIP(hipGetLastError());
 }
 
 }   // namespace gpp
@@ -314,8 +307,6 @@ extern "C" int gpp_calc_quantiles(const float* array, long rows, int len, const 
     in.bind(array, (size_t)rows * len, mem);
     o.bind(out, (size_t)rows * nq, mem);
     rows_quantiles(in.d, rows, len, quantiles, nq, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(64) void k_crps_tile(const float* __restrict__ in, 
                 s1 += fabs(x - y);
                 s2 += (double)(2 * r - N + 1) * x;
             });
-            out[row0 + lane] = N == 0 || !nv(yf) ? NAN : (float)(s1 / (double)N - s2 / ((double)N * (double)N));
+            out[row0 + lane] = N == 0 || !dev_valid(yf) ? NAN : (float)(s1 / (double)N - s2 / ((double)N * (double)N));
         }
     }
 }
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(256) void k_crps_block(const float* __restrict__ in
         __syncthreads();
         if(tid == 0) {
             const double t1 = ((red[0] + red[2]) + red[4]) + red[6], t2 = ((red[1] + red[3]) + red[5]) + red[7];
-            out[r] = N == 0 || !nv(yf) ? NAN : (float)(t1 / (double)N - t2 / ((double)N * (double)N));
+            out[r] = N == 0 || !dev_valid(yf) ? NAN : (float)(t1 / (double)N - t2 / ((double)N * (double)N));
         }
     }
 }
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256) void k_crps_long(const unsigned* __restrict__ 
         __syncthreads();
         if(tid == 0) {
             const double t1 = ((red[0] + red[2]) + red[4]) + red[6], t2 = ((red[1] + red[3]) + red[5]) + red[7];
-            out[r] = N == 0 || !nv(yf) ? NAN : (float)(t1 / (double)N - t2 / ((double)N * (double)N));
+            out[r] = N == 0 || !dev_valid(yf) ? NAN : (float)(t1 / (double)N - t2 / ((double)N * (double)N));
         }
     }
 }
@@ -400,13 +400,7 @@ RrPath rr_choose(int len) {
     }
     return tile_ok ? RR_TILE : block_ok ? RR_BLOCK : RR_LONG;
 }
-unsigned rr_magic(int d) { return (unsigned)((1ull << 32) / (unsigned)d + 1); }   // (unused for d == 1, where it does not fit)
-unsigned rr_grid(long n) { return (unsigned)std::min<long>(n, 1L << 20); }
-int rr_pow2(int len) {
-    int P = 2;
-    while(P < len) P <<= 1;
-    return P;
-}
+constexpr size_t RR_MAXGRID = (size_t)1 << 20;   // the tile and block kernels stride over their grid beyond it
 // the keys of a tile and `bytes` areas of bytes (rr_bpitch, restated for the host).  At len = 160 that is 41 216 + 10 496 bytes per area of
 // bytes: with two of them 62 208, within the 64 KB a kernel gets unasked
 size_t rr_tile_lds(int len, int bytes) { return (size_t)64 * (len | 1) * sizeof(unsigned) + (size_t)bytes * 64 * 4 * (((len + 3) >> 2) | 1); }
@@ -418,8 +412,7 @@ struct SegBegin {   // the bounds of the equal segments of the long path
 // (canonical key, position) of n = rows * len values at d_in, sorted row by row into skeys / spos
 void rr_long_sort(const float* d_in, long rows, int len, unsigned* keys, int* pos, unsigned* skeys, int* spos) {
     const long n = rows * len;
-    hipLaunchKernelGGL(k_rank_long_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), d_in, n, len, keys, pos);
-    GPP_HIP(hipGetLastError());
+    launch(k_rank_long_keys, blocks_of(n), 256, 0, d_in, n, len, keys, pos);
     auto begin = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(0u), SegBegin{(unsigned)len});
     size_t sb = 0;
     GPP_HIP(rocprim::segmented_radix_sort_pairs((void*)nullptr, sb, keys, skeys, pos, spos, (unsigned)n, (unsigned)rows, begin, begin + 1, 0u, 32u, stream()));
@@ -443,15 +436,15 @@ void rows_ranks(const float* d_in, long rows, int len, int* d_ranks, float* d_so
     case RR_TILE: {
         const size_t lds = rr_tile_lds(len, (d_ranks != nullptr) + (d_sorted != nullptr));
         const int vec_ok = (reinterpret_cast<size_t>(d_in) & 15) == 0;
-        hipLaunchKernelGGL(k_rank_tile, dim3(rr_grid((rows + 63) / 64)), dim3(64), lds, stream(), d_in, rows, len, rr_magic(len), vec_ok, d_ranks, d_sorted);
+        launch(k_rank_tile, grid_capped((rows + 63) / 64, RR_MAXGRID), 64, lds, d_in, rows, len, magic_div(len), vec_ok, d_ranks, d_sorted);
         break;
     }
     case RR_BLOCK:
         if(d_ranks)
-            hipLaunchKernelGGL(k_rank_block<0>, dim3(rr_grid(rows)), dim3(256), (size_t)len * sizeof(rr_u64), stream(), d_in, (const float*)nullptr, rows, len,
-                               rr_pow2(len), d_ranks, d_sorted);
+            launch(k_rank_block<0>, grid_capped(rows, RR_MAXGRID), 256, (size_t)len * sizeof(rr_u64), d_in, (const float*)nullptr, rows, len, pow2_at_least(len), d_ranks,
+                   d_sorted);
         else   // the sorted rows alone: 32-bit keys
-            hipLaunchKernelGGL(k_sort_block, dim3(rr_grid(rows)), dim3(256), (size_t)len * sizeof(unsigned), stream(), d_in, rows, len, rr_pow2(len), d_sorted);
+            launch(k_sort_block, grid_capped(rows, RR_MAXGRID), 256, (size_t)len * sizeof(unsigned), d_in, rows, len, pow2_at_least(len), d_sorted);
         break;
     default: {
         LongWs ws;
@@ -460,12 +453,11 @@ void rows_ranks(const float* d_in, long rows, int len, int* d_ranks, float* d_so
         for(long r0 = 0; r0 < rows; r0 += step) {
             const long nr = std::min(step, rows - r0), n = nr * len;
             rr_long_sort(d_in + r0 * len, nr, len, ws.keys.p, ws.pos.p, ws.skeys.p, ws.spos.p);
-            hipLaunchKernelGGL(k_rank_long_emit<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), d_in + r0 * len, (const float*)nullptr,
-                               ws.skeys.p, ws.spos.p, n, len, d_ranks ? d_ranks + r0 * len : nullptr, d_sorted ? d_sorted + r0 * len : nullptr);
+            launch(k_rank_long_emit<0>, blocks_of(n), 256, 0, d_in + r0 * len, (const float*)nullptr, ws.skeys.p, ws.spos.p, n, len, d_ranks ? d_ranks + r0 * len : nullptr,
+                   d_sorted ? d_sorted + r0 * len : nullptr);
         }
     }
     }
-    GPP_HIP(hipGetLastError());
 }
 
 // d_out[r][i] = sorted(d_values row r)[rank of d_templ[r][i]], NaN where the template's value is invalid or its rank reaches past the valid values
@@ -475,8 +467,7 @@ void rows_reorder(const float* d_values, const float* d_templ, long rows, int le
     if(path == RR_TILE) {
         const size_t lds = rr_tile_lds(len, 2);
         const int vec_ok = ((reinterpret_cast<size_t>(d_values) | reinterpret_cast<size_t>(d_templ)) & 15) == 0;
-        hipLaunchKernelGGL(k_reorder_tile, dim3(rr_grid((rows + 63) / 64)), dim3(64), lds, stream(), d_values, d_templ, rows, len, rr_magic(len), vec_ok, d_out);
-        GPP_HIP(hipGetLastError());
+        launch(k_reorder_tile, grid_capped((rows + 63) / 64, RR_MAXGRID), 64, lds, d_values, d_templ, rows, len, magic_div(len), vec_ok, d_out);
         return;
     }
     // block and long: the sorted `values` rows go through a scratch array in HBM, a bounded number of rows at a time
@@ -489,21 +480,18 @@ void rows_reorder(const float* d_values, const float* d_templ, long rows, int le
         const long nr = std::min(step, rows - r0), n = nr * len;
         const float *v = d_values + r0 * len, *t = d_templ + r0 * len;
         if(path == RR_BLOCK) {
-            const int P = rr_pow2(len);
+            const int P = pow2_at_least(len);
             const size_t lds = (size_t)len * sizeof(rr_u64);
-            hipLaunchKernelGGL(k_sort_block, dim3(rr_grid(nr)), dim3(256), (size_t)len * sizeof(unsigned), stream(), v, nr, len, P, sorted.p);
-            hipLaunchKernelGGL(k_rank_block<1>, dim3(rr_grid(nr)), dim3(256), lds, stream(), t, (const float*)sorted.p, nr, len, P, (int*)nullptr,
-                               d_out + r0 * len);
+            launch(k_sort_block, grid_capped(nr, RR_MAXGRID), 256, (size_t)len * sizeof(unsigned), v, nr, len, P, sorted.p);
+            launch(k_rank_block<1>, grid_capped(nr, RR_MAXGRID), 256, lds, t, (const float*)sorted.p, nr, len, P, (int*)nullptr, d_out + r0 * len);
         }
         else {
-            const dim3 grid((unsigned)((n + 255) / 256));
+            const dim3 grid(blocks_of(n));
             rr_long_sort(v, nr, len, ws.keys.p, ws.pos.p, ws.skeys.p, ws.spos.p);
-            hipLaunchKernelGGL(k_rank_long_emit<0>, grid, dim3(256), 0, stream(), v, (const float*)nullptr, ws.skeys.p, ws.spos.p, n, len, (int*)nullptr, sorted.p);
+            launch(k_rank_long_emit<0>, grid, 256, 0, v, (const float*)nullptr, ws.skeys.p, ws.spos.p, n, len, (int*)nullptr, sorted.p);
             rr_long_sort(t, nr, len, ws.keys.p, ws.pos.p, ws.skeys.p, ws.spos.p);
-            hipLaunchKernelGGL(k_rank_long_emit<1>, grid, dim3(256), 0, stream(), t, (const float*)sorted.p, ws.skeys.p, ws.spos.p, n, len, (int*)nullptr,
-                               d_out + r0 * len);
+            launch(k_rank_long_emit<1>, grid, 256, 0, t, (const float*)sorted.p, ws.skeys.p, ws.spos.p, n, len, (int*)nullptr, d_out + r0 * len);
         }
-        GPP_HIP(hipGetLastError());
     }
 }
 
@@ -511,19 +499,18 @@ void rows_reorder(const float* d_values, const float* d_templ, long rows, int le
 void rows_crps(const float* d_ens, const float* d_ref, long rows, int len, float* d_out) {
     if(rows <= 0) return;
     if(len <= 0) {   // no member at all: NaN
-        hipLaunchKernelGGL(k_crps_long, dim3(rr_grid(rows)), dim3(256), 0, stream(), (const unsigned*)nullptr, d_ref, rows, 0, d_out);
-        GPP_HIP(hipGetLastError());
+        launch(k_crps_long, grid_capped(rows, RR_MAXGRID), 256, 0, (const unsigned*)nullptr, d_ref, rows, 0, d_out);
         return;
     }
     switch(rr_choose(len)) {
     case RR_TILE: {
         const size_t lds = rr_tile_lds(len, 0);
         const int vec_ok = (reinterpret_cast<size_t>(d_ens) & 15) == 0;
-        hipLaunchKernelGGL(k_crps_tile, dim3(rr_grid((rows + 63) / 64)), dim3(64), lds, stream(), d_ens, d_ref, rows, len, rr_magic(len), vec_ok, d_out);
+        launch(k_crps_tile, grid_capped((rows + 63) / 64, RR_MAXGRID), 64, lds, d_ens, d_ref, rows, len, magic_div(len), vec_ok, d_out);
         break;
     }
     case RR_BLOCK:
-        hipLaunchKernelGGL(k_crps_block, dim3(rr_grid(rows)), dim3(256), (size_t)len * sizeof(unsigned), stream(), d_ens, d_ref, rows, len, rr_pow2(len), d_out);
+        launch(k_crps_block, grid_capped(rows, RR_MAXGRID), 256, (size_t)len * sizeof(unsigned), d_ens, d_ref, rows, len, pow2_at_least(len), d_out);
         break;
     default: {
         LongWs ws;
@@ -532,11 +519,10 @@ void rows_crps(const float* d_ens, const float* d_ref, long rows, int len, float
         for(long r0 = 0; r0 < rows; r0 += step) {
             const long nr = std::min(step, rows - r0);
             rr_long_sort(d_ens + r0 * len, nr, len, ws.keys.p, ws.pos.p, ws.skeys.p, ws.spos.p);
-            hipLaunchKernelGGL(k_crps_long, dim3(rr_grid(nr)), dim3(256), 0, stream(), (const unsigned*)ws.skeys.p, d_ref + r0, nr, len, d_out + r0);
+            launch(k_crps_long, grid_capped(nr, RR_MAXGRID), 256, 0, (const unsigned*)ws.skeys.p, d_ref + r0, nr, len, d_out + r0);
         }
     }
     }
-    GPP_HIP(hipGetLastError());
 }
 
 }   // namespace gpp
@@ -557,10 +543,7 @@ extern "C" int gpp_calc_ranks(const float* array, long rows, int len, int* ranks
     r.bind(ranks, n, mem);
     s.bind(sorted, n, mem);
     rows_ranks(in.d, rows, len, r.d, s.d);
-    r.finish();
-    s.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(r, s);
     GPP_CATCH
 }
 
@@ -578,9 +561,7 @@ extern "C" int gpp_reorder_by_ranks(const float* values, const float* templ, lon
     t.bind(templ, n, mem);
     o.bind(out, n, mem);
     rows_reorder(v.d, t.d, rows, len, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 
@@ -597,8 +578,6 @@ extern "C" int gpp_calc_crps(const float* ensemble, const float* ref, long rows,
     y.bind(ref, (size_t)rows, mem);
     o.bind(out, (size_t)rows, mem);
     rows_crps(e.d, y.d, rows, len, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }

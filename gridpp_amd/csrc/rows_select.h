@@ -27,7 +27,7 @@ void rows_quantiles(const float* d_in, long rows, int len, const float* h_levels
 #define RS_TILE_MAXLEN 160        // (MEMBER_EC of neighbourhood.hip: rows up to this length are selected out of LDS)
 #define RS_INV 0xFFFFFFFFu        // key of an invalid value: no finite float maps to it
 
-__device__ __forceinline__ unsigned rs_key(float v) { return nv(v) ? f2ord(v) : RS_INV; }
+__device__ __forceinline__ unsigned rs_key(float v) { return dev_valid(v) ? f2ord(v) : RS_INV; }
 __device__ __forceinline__ void rs_indices(float q, int N, int& lo, int& up) {   // util.cpp:152-157
     const float pos = q * (float)(N - 1);
     lo = (int)floorf(pos); up = (int)ceilf(pos);

@@ -46,7 +46,7 @@ __device__ __forceinline__ float rs_lane_select(const unsigned* row, const int l
         const unsigned k = row[i];
         if(k != RS_INV) { N++; kmin = min(kmin, k); kmax = max(kmax, k); }
     }
-    if(!nv(q) || N == 0) return NAN;
+    if(!dev_valid(q) || N == 0) return NAN;
     if(q == 0 || q == 1) {   // row_statistic's Min / Max: the first valid value, replaced on a strict compare only
         float m = NAN; bool have = false;
         for(int i = 0; i < len; i++) {
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_rows_block(const float* __restrict__ in
         const float qq = rs_level(q, qfield, r);
         __syncthreads();
         float res;   // (every branch below is taken by the whole workgroup: qq, N and the keys are the same for all threads)
-        if(!nv(qq) || N == 0) res = NAN;
+        if(!dev_valid(qq) || N == 0) res = NAN;
         else if(qq == 0 || qq == 1) {
             const bool is_min = qq == 0;
             if(tid == 0) s64 = is_min ? ~0ull : 0ull;
@@ -309,7 +309,7 @@ __global__ void k_split_plan(long rows, const float* __restrict__ q, int qfield,
     const float qq = rs_level(q, qfield, r);
     const int N = (int)st.N;
     st.q = qq;
-    if(!nv(qq) || N == 0) { out[r] = NAN; return; }   // (mode stays 0)
+    if(!dev_valid(qq) || N == 0) { out[r] = NAN; return; }   // (mode stays 0)
     if(qq == 0 || qq == 1) { st.mode = qq == 0 ? 2 : 3; st.packed = qq == 0 ? ~0ull : 0ull; return; }
     int lo, up;
     rs_indices(qq, N, lo, up);
@@ -414,15 +414,15 @@ void rs_split(const float* d_in, long rows, int len, const float* d_q, int q_per
     // workgroups per row: enough to fill the chip eight times over, at least 4096 elements each
     const long want = std::max<long>(1, 2048 / rows), most = std::max<long>(1, ((long)len + 4095) / 4096);
     const dim3 grid((unsigned)std::min(want, most), (unsigned)rows), rowgrid((unsigned)((rows + 63) / 64));
-    hipLaunchKernelGGL(k_split_init, dim3((unsigned)rows), dim3(256), 0, stream(), S);
-    hipLaunchKernelGGL(k_split_count, grid, dim3(256), 0, stream(), d_in, len, S);
-    hipLaunchKernelGGL(k_split_plan, rowgrid, dim3(64), 0, stream(), rows, d_q, q_per_row, S, d_out);
+    launch(k_split_init, (unsigned)rows, 256, 0, S);
+    launch(k_split_count, grid, 256, 0, d_in, len, S);
+    launch(k_split_plan, rowgrid, 64, 0, rows, d_q, q_per_row, S, d_out);
     for(int pass = 0; pass < 4; pass++) {
-        hipLaunchKernelGGL(k_split_hist, grid, dim3(256), 0, stream(), d_in, len, S, pass);
-        hipLaunchKernelGGL(k_split_pick, dim3((unsigned)rows), dim3(64), 0, stream(), S, pass);
+        launch(k_split_hist, grid, 256, 0, d_in, len, S, pass);
+        launch(k_split_pick, (unsigned)rows, 64, 0, S, pass);
     }
-    hipLaunchKernelGGL(k_split_final, grid, dim3(256), 0, stream(), d_in, len, S);
-    hipLaunchKernelGGL(k_split_finish, rowgrid, dim3(64), 0, stream(), d_in, rows, len, S, d_out);
+    launch(k_split_final, grid, 256, 0, d_in, len, S);
+    launch(k_split_finish, rowgrid, 64, 0, d_in, rows, len, S, d_out);
 }
 }   // namespace
 
@@ -433,21 +433,19 @@ void rows_quantile(const float* d_in, long rows, int len, const float* d_q, int 
         const size_t lds = (size_t)64 * (len | 1) * sizeof(unsigned);
         const long waves_per_cu = std::max<long>(1, std::min<long>(16, (160 * 1024) / (long)lds));
         const long grid = std::min<long>((rows + 63) / 64, 256 * waves_per_cu);
-        const unsigned magic = (unsigned)((1ull << 32) / (unsigned)len + 1);   // (unused for len == 1, where it does not fit)
         const int vec_ok = (reinterpret_cast<size_t>(d_in) & 15) == 0;
-        hipLaunchKernelGGL(k_rows_tile, dim3((unsigned)grid), dim3(64), lds, stream(), d_in, rows, len, magic, vec_ok, d_q, q_per_row, d_out);
+        launch(k_rows_tile, (unsigned)grid, 64, lds, d_in, rows, len, magic_div(len), vec_ok, d_q, q_per_row, d_out);
         break;
     }
     case RS_BLOCK:
-        hipLaunchKernelGGL(k_rows_block, dim3((unsigned)std::min<long>(rows, 256 * 8)), dim3(256), 0, stream(), d_in, rows, len, d_q, q_per_row, d_out);
+        launch(k_rows_block, (unsigned)std::min<long>(rows, 256 * 8), 256, 0, d_in, rows, len, d_q, q_per_row, d_out);
         break;
     case RS_SPLIT:
         rs_split(d_in, rows, len, d_q, q_per_row, d_out);
         break;
     default:
-        hipLaunchKernelGGL(k_rows_lane, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream(), d_in, rows, len, d_q, q_per_row, d_out);
+        launch(k_rows_lane, blocks_of(rows), 256, 0, d_in, rows, len, d_q, q_per_row, d_out);
     }
-    GPP_HIP(hipGetLastError());
 }
 
 bool quantile_out_of_range(const float* d_q, long nq) {
@@ -456,8 +454,7 @@ bool quantile_out_of_range(const float* d_q, long nq) {
     int* d_flag = flag.get(1);
     int h = 0;
     GPP_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), stream()));
-    hipLaunchKernelGGL(k_quantile_range, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream(), d_q, nq, d_flag);
-    GPP_HIP(hipGetLastError());
+    launch(k_quantile_range, blocks_of(nq), 256, 0, d_q, nq, d_flag);
     GPP_HIP(hipMemcpyAsync(&h, d_flag, sizeof(int), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));
     return h != 0;

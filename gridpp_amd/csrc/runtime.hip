@@ -361,8 +361,7 @@ static void upload_as_float(DevBuf<float>& dst, const double* src, int n) {
     DevBuf<double> tmp;
     tmp.upload(src, n);
     dst.get(n);
-    hipLaunchKernelGGL(k_cast_f64, dim3((n + 255) / 256), dim3(256), 0, stream(), tmp.p, n, dst.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_cast_f64, blocks_of(n), 256, 0, tmp.p, n, dst.p);
     GPP_HIP(hipStreamSynchronize(stream()));   // tmp dies here
 }
 // lats / lons: the caller's arrays (they become the persistent d_lat / d_lon of the set)
@@ -376,8 +375,7 @@ static bool convert_all_device(gpp_points* p, const T* lats, const T* lons) {
     p->d_x.get(n); p->d_y.get(n); p->d_z.get(n);
     d_flag.get(cap); d_cnt.get(2);
     GPP_HIP(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(int), stream()));
-    hipLaunchKernelGGL(k_convert, dim3((n + 255) / 256), dim3(256), 0, stream(), p->d_lat.p, p->d_lon.p, n, p->type, p->d_x.p, p->d_y.p, p->d_z.p, d_flag.p, cap, d_cnt.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_convert, blocks_of(n), 256, 0, p->d_lat.p, p->d_lon.p, n, p->type, p->d_x.p, p->d_y.p, p->d_z.p, d_flag.p, cap, d_cnt.p);
     int cnt[2] = {0, 0};
     GPP_HIP(hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));
@@ -394,8 +392,7 @@ static bool convert_all_device(gpp_points* p, const T* lats, const T* lons) {
         DevBuf<float> d_v;
         DevBuf<int> d_i;
         d_v.upload(v.data(), v.size()); d_i.upload(idx.data(), idx.size());
-        hipLaunchKernelGGL(k_patch, dim3((cnt[0] + 255) / 256), dim3(256), 0, stream(), d_i.p, d_v.p, cnt[0], p->d_x.p, p->d_y.p, p->d_z.p);
-        GPP_HIP(hipGetLastError());
+        launch(k_patch, blocks_of(cnt[0]), 256, 0, d_i.p, d_v.p, cnt[0], p->d_x.p, p->d_y.p, p->d_z.p);
         GPP_HIP(hipStreamSynchronize(stream()));
     }
     return true;
@@ -460,8 +457,7 @@ __global__ void k_fill_f32(float* out, size_t n, float v) {
 }
 void gpp::fill_f32(float* d, size_t n, float v) {
     if(n == 0) return;
-    hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), d, n, v);
-    GPP_HIP(hipGetLastError());
+    launch(k_fill_f32, blocks_of(n), 256, 0, d, n, v);
 }
 template <class T>
 static gpp_points* make_points(const T* lats, const T* lons, const T* elevs, const T* lafs, int n, int ny, int nx, int type) {
@@ -499,7 +495,6 @@ static gpp_points* make_points(const T* lats, const T* lons, const T* elevs, con
         else fill_f32(p->d_elev.get(n), n, NAN);
         if(lafs) upload_as_float(p->d_laf, lafs, n);
         else fill_f32(p->d_laf.get(n), n, NAN);
-        GPP_HIP(hipGetLastError());
         GPP_HIP(hipStreamSynchronize(stream()));   // the caller's arrays may go away after this call
         p->on_device = true;
         return p.release();
@@ -679,16 +674,13 @@ void gpp_nearest_device(gpp_points* p, const float* d_qx, const float* d_qy, con
     if(nq == 0) return;
     if(p->n > 2048 && !path_env("GPP_NN_BRUTE")) {
         gpp_obs_index* ix = gpp_build_obs_index(p);
-        hipLaunchKernelGGL(k_nearest_binned, dim3((nq + 255) / 256), dim3(256), 0, stream(), ix->d_sgeo.p, ix->d_smeta.p, ix->d_bin_start.p,
-                           ix->axis_a, ix->axis_b, ix->nbx, ix->nby, ix->amin, ix->bmin, ix->inv_s, d_qx, d_qy, d_qz, nq, include_match, d_out);
-        GPP_HIP(hipGetLastError());
+        launch(k_nearest_binned, blocks_of(nq), 256, 0, ix->d_sgeo.p, ix->d_smeta.p, ix->d_bin_start.p, ix->axis_a, ix->axis_b, ix->nbx, ix->nby, ix->amin, ix->bmin, ix->inv_s,
+               d_qx, d_qy, d_qz, nq, include_match, d_out);
         return;
     }
     int waves_per_block = 4;
     int blocks = (nq + waves_per_block - 1) / waves_per_block;
-    hipLaunchKernelGGL(k_nearest_bruteforce, dim3(blocks), dim3(256), 0, stream(), p->d_x.p, p->d_y.p, p->d_z.p, p->n,
-                       d_qx, d_qy, d_qz, nq, include_match, d_out);
-    GPP_HIP(hipGetLastError());
+    launch(k_nearest_bruteforce, blocks, 256, 0, p->d_x.p, p->d_y.p, p->d_z.p, p->n, d_qx, d_qy, d_qz, nq, include_match, d_out);
 }
 
 extern "C" int gpp_points_nearest_neighbour(gpp_points* p, const float* qlats, const float* qlons, int nq, int include_match, int* indices) {
@@ -744,16 +736,11 @@ extern "C" int gpp_nearest_levels(gpp_points* from, gpp_points* to, const float*
         DevBuf<int> idx;
         idx.get(nq);
         gpp_nearest_device(from, to->d_x.p, to->d_y.p, to->d_z.p, nq, 1, idx.p);
-        if(nt == 1) hipLaunchKernelGGL(k_gather, dim3((nq + 255) / 256), dim3(256), 0, stream(), v.d, idx.p, nq, o.d);
-        else hipLaunchKernelGGL(k_gather_levels, dim3((nq + 255) / 256), dim3(256), 0, stream(), v.d, idx.p, nq, (size_t)from->n, nt, o.d);
-        GPP_HIP(hipGetLastError());
-        o.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));   // staged buffers die with this scope
-        return GPP_OK;
+        if(nt == 1) launch(k_gather, blocks_of(nq), 256, 0, v.d, idx.p, nq, o.d);
+        else launch(k_gather_levels, blocks_of(nq), 256, 0, v.d, idx.p, nq, (size_t)from->n, nt, o.d);
+        return finish_call(o);   // staged buffers die with this scope
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(o);
     GPP_CATCH
 }
 

@@ -29,6 +29,7 @@
 // 65536: hw <= 127.  GPP_SCORE_FUSED_MAXHW = 16 is set by the ring (SC_C + 2 hw <= SC_RING), far inside that bound; a window of 65535 or
 // more counted cells can therefore only occur on the general path, whose counters are 32 bits wide (a field has fewer than 2^31 cells).
 #include "common.h"
+#include "march_geom.h"
 #include "score.h"
 #include <algorithm>
 #include <cstdint>
@@ -56,8 +57,6 @@ static_assert(SC_C + 2 * SC_MAXHW <= SC_RING && (SC_RING & (SC_RING - 1)) == 0, 
 static_assert((2 * SC_MAXHW + 1) * (2 * SC_MAXHW + 1) < 65536, "16-bit lanes hold the counts of a window");
 static_assert(SC_C * SC_WT % SC_THREADS == 0 && SC_THREADS == 8 * SC_C && SC_THREADS == 4 * SC_W && SC_W == 64 && SC_C == 32, "thread layout");
 static_assert((SC_P / 4) % 2 == 1 && SC_P % 4 == 0 && SC_RP % 2 == 1, "odd pitches");
-
-__device__ __forceinline__ bool dev_valid(float v) { return !isnan(v) && !isinf(v); }   // util.cpp:16-18
 
 __global__ __launch_bounds__(256) void k_score_classify(const float* __restrict__ ref_grid, const float* __restrict__ fcst, size_t n, float threshold,
                                                         unsigned char* __restrict__ cat) {
@@ -216,8 +215,6 @@ __global__ __launch_bounds__(256) void k_score_counts(const float* __restrict__ 
     }
 }
 
-unsigned grid_for(size_t items) { return (unsigned)std::min<size_t>(std::max<size_t>(items, 1), (size_t)1 << 22); }
-
 void check_metric(int metric) {
     if(!gpp_score_metric_known(metric)) invalid("Unknown metric");   // metric_optimizer.cpp:241-243
 }
@@ -248,9 +245,7 @@ extern "C" int gpp_calc_score(const float* ref, const float* fcst, long long n, 
         DevBuf<unsigned long long> counts;
         counts.get(4);
         GPP_HIP(hipMemsetAsync(counts.p, 0, 4 * sizeof(unsigned long long), stream()));
-        const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 8192);
-        hipLaunchKernelGGL(k_score_counts, dim3(blocks), dim3(256), 0, stream(), r.d, f.d, n, threshold, fthreshold, counts.p);
-        GPP_HIP(hipGetLastError());
+        launch(k_score_counts, grid_capped(blocks_of(n), 8192), 256, 0, r.d, f.d, n, threshold, fthreshold, counts.p);
         GPP_HIP(hipMemcpyAsync(h, counts.p, sizeof(h), hipMemcpyDeviceToHost, stream()));
         GPP_HIP(hipStreamSynchronize(stream()));
     }
@@ -284,31 +279,21 @@ extern "C" int gpp_neighbourhood_score(gpp_points* grid, gpp_points* points, con
     gpp_gridding_nearest_device(grid, points, r.d, 1, GPP_MEAN, o.d);
     Staged<unsigned char> cat;
     cat.get(C);
-    hipLaunchKernelGGL(k_score_classify, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream(), (const float*)o.d, f.d, C, threshold, cat.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_score_classify, blocks_of(C), 256, 0, (const float*)o.d, f.d, C, threshold, cat.p);
     if(half_width <= SC_MAXHW && !path_env("GPP_SCORE_GENERAL")) {
         const int strips = (X + SC_W - 1) / SC_W;
         const long fill = path_env("GPP_SCORE_FILL") ? std::max(1, atoi(path_env("GPP_SCORE_FILL"))) : 1024;   // (tests: workgroups the launch aims for)
-        const int segs = (int)std::max(1L, std::min((fill + strips - 1) / strips, (long)(Y + SC_C - 1) / SC_C));   // about a thousand workgroups where the field has them
-        int SH = ((Y + segs - 1) / segs + SC_C - 1) / SC_C * SC_C;
-        while((Y + SH - 1) / SH > 65535) SH += SC_C;
-        hipLaunchKernelGGL(k_score_march, dim3(strips, (Y + SH - 1) / SH), dim3(SC_THREADS), 0, stream(), (const unsigned char*)cat.p, Y, X, half_width,
-                           metric, SH, o.d);
-        GPP_HIP(hipGetLastError());
+        const MarchSegments sg = march_segments(Y, SC_C, std::max(1L, (fill + strips - 1) / strips));   // about a thousand workgroups where the field has them
+        launch(k_score_march, dim3(strips, sg.segs), SC_THREADS, 0, (const unsigned char*)cat.p, Y, X, half_width, metric, sg.SH, o.d);
     }
     else {
         const int hw = std::min(half_width, std::max(Y, X));   // a window that covers the field either way
         Staged<uint4> rows;
         rows.get(C);
-        hipLaunchKernelGGL(k_score_rows, dim3(grid_for(((size_t)Y * ((X + SC_RUN - 1) / SC_RUN) + 255) / 256)), dim3(256), 0, stream(),
-                           (const unsigned char*)cat.p, Y, X, hw, rows.p);
-        GPP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_score_cols, dim3(grid_for(((size_t)X * ((Y + SC_RUN - 1) / SC_RUN) + 255) / 256)), dim3(256), 0, stream(),
-                           (const uint4*)rows.p, Y, X, hw, metric, o.d);
-        GPP_HIP(hipGetLastError());
+        const size_t cap = (size_t)1 << 22;   // (the two kernels stride over their grid; the field has cells here, so neither grid is empty)
+        launch(k_score_rows, grid_capped(blocks_of((size_t)Y * ((X + SC_RUN - 1) / SC_RUN)), cap), 256, 0, (const unsigned char*)cat.p, Y, X, hw, rows.p);
+        launch(k_score_cols, grid_capped(blocks_of((size_t)X * ((Y + SC_RUN - 1) / SC_RUN)), cap), 256, 0, (const uint4*)rows.p, Y, X, hw, metric, o.d);
     }
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));   // the workspaces go back to the pool here
-    return GPP_OK;
+    return finish_call(o);   // (the workspaces go back to the pool here)
     GPP_CATCH
 }

@@ -36,9 +36,7 @@ void corr_launch(const gpp_structure* s, const float p1[7], const float* x, cons
     const gpp_structure t = gpp_structure_at(s, p1[5], p1[6]);
     const DevStructure d = gpp_resolve_structure(&t);
     const long long blocks = std::min((n + CORR_BLOCK - 1) / CORR_BLOCK, CORR_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_structure_corr_many, dim3((unsigned)blocks), dim3(CORR_BLOCK), 0, stream(), d, make_float4(p1[0], p1[1], p1[2], p1[3]),
-                       p1[4], x, y, z, elev, laf, stride, n, background, d_out);
-    GPP_HIP(hipGetLastError());
+    launch(k_structure_corr_many, (unsigned)blocks, CORR_BLOCK, 0, d, make_float4(p1[0], p1[1], p1[2], p1[3]), p1[4], x, y, z, elev, laf, stride, n, background, d_out);
 }
 
 }   // namespace
@@ -56,9 +54,7 @@ extern "C" int gpp_structure_corr_many(const gpp_structure* s, const float p1[7]
     in.bind(p2, (size_t)n * 7, GPP_MEM_HOST);
     out.bind(rho, (size_t)n, GPP_MEM_HOST);
     corr_launch(s, p1, in.d, in.d + 1, in.d + 2, in.d + 3, in.d + 4, 7, n, background, out.d);
-    out.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    return finish_call(out);
     GPP_CATCH
 }
 
@@ -74,8 +70,6 @@ extern "C" int gpp_structure_corr_points(const gpp_structure* s, const float p1[
     OutField out;
     out.bind(rho, (size_t)to->n, mem);
     corr_launch(s, p1, to->d_x.p, to->d_y.p, to->d_z.p, to->d_elev.p, to->d_laf.p, 1, to->n, background, out.d);
-    out.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));   // (a device result is read by the caller's own stream next)
-    return GPP_OK;
+    return finish_call(out);   // (a device result is read by the caller's own stream next)
     GPP_CATCH
 }

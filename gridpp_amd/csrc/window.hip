@@ -169,7 +169,7 @@ __global__ __launch_bounds__(WIN_ROWS) void k_window_scan(const float* __restric
 #pragma unroll
                 for(int c = 0; c < WIN_COLS; c++) {
                     const int x = in0 + c;
-                    const bool counts = x >= 0 && x < T && nv(v[c]);
+                    const bool counts = x >= 0 && x < T && dev_valid(v[c]);
                     P = counts ? P + v[c] : P;
                     N += counts ? 1 : 0;
                     if(PLANES) { stage[c] = P; reinterpret_cast<int*>(ring_p)[c] = N; }
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void k_window_from_planes(const float* __restr
 __device__ __forceinline__ float gather_output(const float* seg, int n, bool outside, long long cell, int statistic, int keep_missing,
                                                int missing_edges) {
     int valid = 0;
-    for(int i = 0; i < n; i++) valid += nv(seg[i]) ? 1 : 0;
+    for(int i = 0; i < n; i++) valid += dev_valid(seg[i]) ? 1 : 0;
     if(keep_missing && valid < n) return NAN;     // :144-145
     if(missing_edges && outside) return NAN;      // :146-147
     if(statistic == GPP_MEDIAN) return row_quantile(seg, n, 0.5f);
@@ -230,7 +230,7 @@ __device__ __forceinline__ float gather_output(const float* seg, int n, bool out
         unsigned h = (unsigned)cell * 2654435761u ^ (unsigned)(cell >> 32); h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
         int pick = (int)(h % (unsigned)valid);
         for(int i = 0; i < n; i++)
-            if(nv(seg[i]) && pick-- == 0) return seg[i];
+            if(dev_valid(seg[i]) && pick-- == 0) return seg[i];
         return NAN;
     }
     return row_statistic(seg, n, statistic);
@@ -283,36 +283,31 @@ __global__ __launch_bounds__(256) void k_window_gather_rows(const float* __restr
 }
 
 // every kernel here loops with a grid stride: 2^22 workgroups of at most 256 threads keep a launch below 2^32 threads, whatever Y and T
-unsigned grid_for(long long items) { return (unsigned)std::min<long long>(std::max<long long>(items, 1), 1LL << 22); }
+constexpr size_t WIN_MAXGRID = (size_t)1 << 22;
 
 template <int VEC>
-void launch(const float* in, long long Y, int T, int back, int ahead, int statistic, int keep, int edges, float* out) {
+void window_launch(const float* in, long long Y, int T, int back, int ahead, int statistic, int keep, int edges, float* out) {
     const bool scan = statistic == GPP_MEAN || statistic == GPP_SUM || statistic == GPP_COUNT;
     const int lead = (ahead + 3) & ~3;
     const bool fused = back + lead <= WIN_SPAN && !path_env("GPP_WINDOW_GENERAL");
-    const unsigned tiles = grid_for((Y + WIN_ROWS - 1) / WIN_ROWS);
+    const unsigned tiles = grid_capped(std::max<size_t>(blocks_of(Y, WIN_ROWS), 1), WIN_MAXGRID);
     const long long total = Y * T;
-    const unsigned flat = grid_for((total + 255) / 256);
+    const unsigned flat = grid_capped(std::max<size_t>(blocks_of(total), 1), WIN_MAXGRID);
     if(scan && fused)
-        hipLaunchKernelGGL((k_window_scan<VEC, false>), dim3(tiles), dim3(WIN_ROWS), 0, stream(), in, Y, T, back, ahead, lead, statistic, keep, edges, out,
-                           (int*)nullptr);
+        launch(k_window_scan<VEC, false>, tiles, WIN_ROWS, 0, in, Y, T, back, ahead, lead, statistic, keep, edges, out, (int*)nullptr);
     else if(scan) {
         Staged<float> P;   // the pool of common.h: gpp_release_workspaces() gives the planes back
         Staged<int> N;
         P.get((size_t)total);
         N.get((size_t)total);
-        hipLaunchKernelGGL((k_window_scan<VEC, true>), dim3(tiles), dim3(WIN_ROWS), 0, stream(), in, Y, T, 0, 0, 0, statistic, keep, edges, P.p, N.p);
-        GPP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_window_from_planes, dim3(flat), dim3(256), 0, stream(), (const float*)P.p, (const int*)N.p, total, T, back, ahead, statistic,
-                           keep, edges, out);
-        GPP_HIP(hipGetLastError());
+        launch(k_window_scan<VEC, true>, tiles, WIN_ROWS, 0, in, Y, T, 0, 0, 0, statistic, keep, edges, P.p, N.p);
+        launch(k_window_from_planes, flat, 256, 0, (const float*)P.p, (const int*)N.p, total, T, back, ahead, statistic, keep, edges, out);
         GPP_HIP(hipStreamSynchronize(stream()));   // the planes go back to the pool here
     }
     else if(fused)
-        hipLaunchKernelGGL((k_window_gather<VEC>), dim3(tiles), dim3(GATHER_THREADS), 0, stream(), in, Y, T, back, ahead, statistic, keep, edges, out);
+        launch(k_window_gather<VEC>, tiles, GATHER_THREADS, 0, in, Y, T, back, ahead, statistic, keep, edges, out);
     else
-        hipLaunchKernelGGL(k_window_gather_rows, dim3(flat), dim3(256), 0, stream(), in, total, T, back, ahead, statistic, keep, edges, out);
-    GPP_HIP(hipGetLastError());
+        launch(k_window_gather_rows, flat, 256, 0, in, total, T, back, ahead, statistic, keep, edges, out);
 }
 
 }   // namespace
@@ -339,10 +334,8 @@ extern "C" int gpp_window(const float* array, long long ny, int nx, int length, 
     a.bind(array, total, mem);
     o.bind(out, total, mem);
     const bool wide = T % 4 == 0 && (((uintptr_t)a.d | (uintptr_t)o.d) & 15) == 0;
-    if(wide) launch<4>(a.d, ny, T, back, ahead, statistic, keep_missing != 0, missing_edges != 0, o.d);
-    else launch<1>(a.d, ny, T, back, ahead, statistic, keep_missing != 0, missing_edges != 0, o.d);
-    o.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    if(wide) window_launch<4>(a.d, ny, T, back, ahead, statistic, keep_missing != 0, missing_edges != 0, o.d);
+    else window_launch<1>(a.d, ny, T, back, ahead, statistic, keep_missing != 0, missing_edges != 0, o.d);
+    return finish_call(o);
     GPP_CATCH
 }
