@@ -1797,6 +1797,7 @@ struct OiCall {
         gpp_bind_field(a.s.st, st, bgrid, points, ws.cell_idx, ws.obs_idx);
         a.allow_extrap = allow_extrapolation ? 1 : 0;
         a.debug = timing_env("GPP_OI_DEBUG") ? atoi(timing_env("GPP_OI_DEBUG")) : 0;
+        a.no_bulk_cert = path_env("GPP_OI_NO_BULK_CERT") ? 1 : 0;   // (A/B, tests: every item of k_oi_union runs the uncertified bulk loop)
         a.tile0 = 0; a.tile_n = a.ntiles;
     }
     // which solver and which kernels
@@ -2230,8 +2231,12 @@ struct OiCall {
         GPP_HIP(hipEventElapsedTime(&g_stats.kernel_ms, ws.e0, ws.e1));
         g_stats.union_kernel_ms = 0;
         if(ran_union || (ran_sp && !sp_failed)) GPP_HIP(hipEventElapsedTime(&g_stats.union_kernel_ms, ws.e0, ws.eu));
-        g_stats.cells_updated = 0; g_stats.solves = 0;
-        for(int k = 0; k < GPP_NSLOT; k++) { g_stats.cells_updated += (long long)counters[80 + 2 * k]; g_stats.solves += (long long)counters[81 + 2 * k]; }
+        g_stats.cells_updated = 0; g_stats.solves = 0; g_stats.bulk_certified = 0;
+        // (the factorisation counter carries two sums: low word the factorisations, high word the items whose bulk disc was certified -- oi_union.h)
+        for(int k = 0; k < GPP_NSLOT; k++) {
+            g_stats.cells_updated += (long long)counters[80 + 2 * k];
+            g_stats.solves += (long long)(counters[81 + 2 * k] & 0xffffffffull); g_stats.bulk_certified += (long long)(counters[81 + 2 * k] >> 32);
+        }
         if(timing_env("GPP_SCAN_STATS")) fprintf(stderr, "[gpp] scan: %llu candidates iterated, %llu survivor-branch executions, %d tiles\n", counters[2], counters[3], a.ntiles);
 #ifdef GPP_UNION_PROFILE
         { const char* nm[24] = {"cell loads", "bbox+init", "phase-1 loads", "rings", "phase 2", "classify", "union records", "P build", "eliminate", "export", "per-lane",
@@ -2330,9 +2335,12 @@ static int complete_pending(PendingOi& pc) {
         pc.stats.fallback_tiles = pc.n_remembered; pc.stats.fallback_subtiles = left;
         GPP_HIP(hipEventElapsedTime(&pc.stats.kernel_ms, sl.e0, sl.e1));
         pc.stats.union_kernel_ms = pc.stats.kernel_ms;   // (the first pass is what stream A ran between the two timestamps; the list passes ran beside the call before)
-        pc.stats.cells_updated = 0; pc.stats.solves = 0;
+        pc.stats.cells_updated = 0; pc.stats.solves = 0; pc.stats.bulk_certified = 0;
         const unsigned long long* const c = sl.h + 8;
-        for(int k = 0; k < GPP_NSLOT; k++) { pc.stats.cells_updated += (long long)c[80 + 2 * k]; pc.stats.solves += (long long)c[81 + 2 * k]; }
+        for(int k = 0; k < GPP_NSLOT; k++) {
+            pc.stats.cells_updated += (long long)c[80 + 2 * k];
+            pc.stats.solves += (long long)(c[81 + 2 * k] & 0xffffffffull); pc.stats.bulk_certified += (long long)(c[81 + 2 * k] >> 32);
+        }
         pc.done = true; pc.rc = GPP_OK;
         return GPP_OK;
     }

@@ -49,6 +49,7 @@ struct OiArgs {
     int level;               // k_oi_union<., true>: 1 or 2 (see there)
     const int* parent_count; // level 2: length of the level-1 input list (how many tiles were split)
     int debug;               // GPP_OI_DEBUG: bit0 = skip the solve (timing experiments only)
+    int no_bulk_cert;        // GPP_OI_NO_BULK_CERT: no item's bulk disc is certified (see `cert` in union_item; A/B and the tests)
     int pair_solo;           // k_oi_union_pair: never merge (A/B: what the two-wave workgroups cost by themselves)
     // k_oi -> k_oi_big: cells with more usable observations than the 62-row register tile holds
     int* big_list;           // cell indices
@@ -293,6 +294,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                                        // the slots back from LDS to learn it (live_mask, the classification)
     unsigned long long alloc = 0ull;   // allocated slots (wave-uniform)
     bool fb = false;                   // wave-uniform: this tile goes to k_oi
+    bool cert = false;                 // wave-uniform: the bulk disc of this item is certified (round 10: behind the bisection)
     constexpr unsigned long long FULL = U_WCAP >= 64 ? ~0ull : ((1ull << (U_WCAP & 63)) - 1ull);
     // an empty (never used / evicted / not wanted by this cell) entry is +inf; all slot loops are static so that the
     // slot LDS reads issue back to back (ds_read2st64) instead of one latency per slot
@@ -485,6 +487,27 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             for(int q = 0; q < EV; ++q) rho[q] = ok[q] ? rho[q] : 0.0f;
         };
 
+        // The bulk disc of a CERTIFIED item (round 10; see `cert` behind the bisection): every test of eval_n has the same answer for every
+        // bulk candidate -- ok is `active`, no candidate is near R, rho is a normal number -- so only the arithmetic the value needs is left.
+        // The same helpers in the same order: every rho keeps its bits.
+        auto eval_cert_n = [&](const float4& rec, const int (&cc)[EV], float (&rho)[EV]) {
+            float dist[EV];
+#pragma unroll
+            for(int q = 0; q < EV; ++q) {
+                const float ox = readlane_f(rec.x, cc[q]), oy = readlane_f(rec.y, cc[q]), oz = readlane_f(rec.z, cc[q]);
+                const float dx = ox - gx, dy = oy - gy, dz = oz - gz;
+                float d2 = dx * dx + dy * dy;
+                d2 = d2 + dz * dz;
+                dist[q] = d_sqrt_cr(d2);
+            }
+#pragma unroll
+            for(int q = 0; q < EV; ++q) rho[q] = 1.0f;
+            if(hh) {
+#pragma unroll
+                for(int q = 0; q < EV; ++q) rho[q] = d_barnes_rho_flat(dist[q], rh);
+            }
+        };
+
         // the candidates `mask` of one chunk of 64 records (lane c holds record c: rec, met, sorted position posv)
         auto run_chunk = [&](const float4 rec, const float2 met, const int posv, unsigned long long mask) {
             while(mask != 0ull && !fb) {
@@ -614,6 +637,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 auto end_bulk = [&]() {   // worst kept entry of every cell after the bulk rings
                     bulk = false;
                     alloc = nb >= 64 ? ~0ull : ((1ull << nb) - 1ull);
+                    if(cert) { cnt = active ? nb : 0; mine = active ? alloc : 0ull; }   // (certified: every active cell took every bulk slot)
                     float r0;
                     int s0;
                     bool multi;
@@ -649,7 +673,35 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                         }
                     }
                 }
-                UPROF(16);  // bisection
+                // Round 10, the certificate of the bulk disc: when NO bulk record can be farther from ANY active cell of the item than the
+                // smallest near_r of those cells and than 12 h, then for every active lane and every bulk candidate dist <= near_r < R (so
+                // d2 <= thr2_R -- thr2 is still thr2_R: no cell holds max_points entries yet --, and the strictly-inside box passes: see
+                // eval), and v = dist / h <= 12, rho >= exp(-72): a normal, positive float32.  `ok` and `rho > 0` are then `active`, decided
+                // here once and not per candidate.  Only without elevation / land-fraction factors (their product can underflow).
+                // The bound, per record that may be in the disc (pd <= tlo): projected separation <= sqrt(pd) + rad (every active cell
+                // lies within rad of the centre), third axis <= the record's distance to the far end of the cells' interval on that axis;
+                // chord^2 <= the sum of the squares.  Each step padded by 1 % -- five orders above float32 rounding; a conservative miss
+                // only costs time.  Every test reads !(... <= ...) -> not certified: a NaN anywhere fails the certificate.
+                if constexpr(PLAIN && EV > 1 && !SP && !PAIR) {
+                    if(!hvu && !hwu && !a.no_bulk_cert) {
+                        const int ax3 = 3 - sa.axis_a - sa.axis_b;
+                        const float pc = ax3 == 0 ? gx : (ax3 == 1 ? gy : gz);
+#define third(rec) (ax3 == 0 ? (rec).x : (ax3 == 1 ? (rec).y : (rec).z))   // (no lambda over the records: one that was not inlined put them on the stack)
+                        const float cmin_t = wave_min(active ? pc : INFINITY), cmax_t = wave_max(active ? pc : -INFINITY);
+                        float lim = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wave_min(active ? near_r : INFINITY))));
+                        if(hh) lim = fminf(lim, 12.0f * fabsf(st.h));
+                        lim *= 0.99f;
+                        const float lim2c = lim * lim;
+                        auto far = [&](const float rc, const float pd) __attribute__((always_inline)) {   // rc: the record's third coordinate
+                            const float p = d_sqrt_raw(pd) * 1.01f + rad, t = fmaxf(fabsf(rc - cmin_t), fabsf(rc - cmax_t));
+                            return pd <= tlo && !((p * p + t * t) * 1.01f <= lim2c);
+                        };
+                        // (wave_min drops a NaN: the second ballot sees the near_r of every active lane itself)
+                        cert = lim > 0.0f && wave_ballot(far(third(rec0), pd0) || far(third(rec1), pd1) || far(third(rec2), pd2)) == 0ull && wave_ballot(active && !(lim <= near_r)) == 0ull;
+                    }
+                }
+#undef third
+                UPROF(16);  // bisection, certificate
                 for(int ring = -1; ring < NR && !fb; ++ring) {   // ring -1: the bulk disc
                     const float hi = d_sqrt_raw(tlo) + (float)(ring + 1) * sa.ring_dr;
                     const float hi2 = ring < 0 ? tlo : ((ring == NR - 1) ? INFINITY : hi * hi);
@@ -673,6 +725,27 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                                 L.worig[slot] = __float_as_int(met.y);
                             }
                             if constexpr(PLAIN && EV > 1) {
+                                if(cert) {   // (ownership and count are written once, in end_bulk)
+                                    for(unsigned long long mm = mk; mm != 0ull;) {
+                                        int cc[EV], n = 0;
+#pragma unroll
+                                        for(int q = 0; q < EV; ++q) {
+                                            cc[q] = mm != 0ull ? __builtin_ctzll(mm) : cc[0];
+                                            n += mm != 0ull ? 1 : 0;
+                                            mm &= mm - 1ull;
+                                        }
+                                        float rho[EV];
+                                        eval_cert_n(rec, cc, rho);
+#pragma unroll
+                                        for(int q = 0; q < EV; ++q) {
+                                            if(q < n) {
+                                                L.rho[nb][lane] = active ? rho[q] : INFINITY;
+                                                nb++;
+                                            }
+                                        }
+                                    }
+                                }
+                                else
                                 for(unsigned long long mm = mk; mm != 0ull;) {
                                     int cc[EV], n = 0;
 #pragma unroll
@@ -1590,7 +1663,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         if(lane == 0 && a.counters) {
             unsigned long long* cs = a.counters + 80 + 2 * (blockIdx.x % GPP_NSLOT);
             atomicAdd(&cs[0], (unsigned long long)__popcll(upd));
-            if(solver) atomicAdd(&cs[1], 1ull);
+            if(solver) atomicAdd(&cs[1], 1ull + (cert ? 1ull << 32 : 0ull));   // (high word: certified items -- the host splits the sum)
         }
     }
 #ifdef GPP_UNION_PROFILE

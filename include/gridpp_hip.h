@@ -718,6 +718,8 @@ typedef struct gpp_oi_stats {
     float union_kernel_ms;    /* of which k_oi_union, first pass (one factorisation per tile); 0 when that kernel was not used */
     long long fallback_subtiles; /* work items (4 cells, or whole tiles) k_oi_union's list passes left to k_oi */
     long long big_cells;      /* grid points with more than 62 usable observations (done by k_oi_big) */
+    long long bulk_certified; /* of `solves`: work items of k_oi_union whose bulk disc was certified (every per-candidate test decided once per item);
+                               * 0 under GPP_OI_NO_BULK_CERT, with elevation / land-fraction factors, and on k_oi_union_pair / k_oi_union_sp */
 } gpp_oi_stats;
 int gpp_oi_last_stats(gpp_oi_stats* stats);
 /* diagnostics: the two coordinate axes (0 = x, 1 = y, 2 = z; the two of largest extent) on which the observation index of `points` is binned --
