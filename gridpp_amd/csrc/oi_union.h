@@ -190,6 +190,9 @@ struct PairLds {
 #ifndef GPP_UNION_COLS
 #define GPP_UNION_COLS 0
 #endif
+#ifndef GPP_UNION_SPLIT
+#define GPP_UNION_SPLIT 1   // 32-column row form: every row of the shared factorisation in two lanes, 18 register slots each (see the row load of union_item)
+#endif
 template <int NC, bool COLS>
 __device__ __forceinline__ int union_solve_doubles(const int c, const int nE) {
     if constexpr(COLS) return c * (c + nE + 1) - c * (c - 1) / 2 + c + nE * nE + nE;   // packed columns (rows of U), 1/diag, Schur complement, d'
@@ -1013,6 +1016,8 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         // issues (VALU 78 % busy), and the column forms issue more of them (496 instead of 378 multiply-adds in the sweep, a per-lane LDS read per
         // extra and column).  The row form stays the product.
         constexpr bool COLS = NC == 32 && GPP_UNION_COLS != 0;
+        // rows split over two lanes (see the row load): the 32-column row form only -- 48 or 64 columns do not fit twice into 64 lanes
+        constexpr bool SPLIT = NC == 32 && !PAIR && !SP && !COLS && GPP_UNION_SPLIT != 0;
         const int FAC = c * (u + 1) - c * (c - 1) / 2;
         const int oL = 0, oI = (COLS || SP) ? FAC : c * (c + 1) / 2, oZ = oI + c, oB = oZ + c, bs = c | 1, oS = (COLS || SP) ? oI + c : oB + nE * bs, oD = oS + nE * nE;
         double* const sv = LS.f.solve;
@@ -1268,7 +1273,35 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         UPROF(7);   // P build
-        double row[NC];
+        // SPLIT (round 11): a row lives in TWO lanes.  Lower half -- columns 0 .. 17 -- of row i in lane i (i < u <= 40), of the obs - background
+        // row in lane 63, as before; upper half -- columns 18 .. 31 -- of rows 18 .. 39 in lanes 40 .. 61 and of the obs - background row in lane
+        // 62 (rows below 18 have no entry there that anybody reads).  Every lane holds 18 slots: slot k of a lower lane is column k, slots 4 .. 17
+        // of an upper lane are columns 18 .. 31 (slots 0 .. 3 of an upper lane are nobody's).  The elimination issues one multiply-add per
+        // occupied slot instead of one per matrix column; every entry takes the multiply-adds it took, operands and order unchanged.
+        constexpr int HS = SPLIT ? 18 : NC, HO = NC - HS, HL = U_MAXU - HS;   // slots of a lane; columns an upper slot is shifted by; upper lane - its row
+        static_assert(!SPLIT || (2 * U_MAXU - HS + 2 == 64 && HO % 2 == 0 && 2 * HS >= NC + 4), "rows and their upper halves fill the wave; pairs of multipliers stay 16-byte aligned");
+        const bool up = SPLIT && lane >= U_MAXU && lane < 63;                  // this lane holds an upper half
+        const int orow = up ? (lane == 62 ? 63 : lane - HL) : lane;           // its row (63: obs - background)
+        const int cofs = up ? HO : 0;                                         // column of its slot 0
+        double row[HS];
+        if constexpr(SPLIT) {
+            const float rdiag = __shfl(o1.w, orow);                           // lR of the row (its observation's record sits in the lower lane)
+            const int rk = orow < u ? orow - cofs : -1;                       // slot of the row's diagonal entry (lower triangle only: all the factorisation reads)
+            const int dk = lane >= 62 ? u - cofs : 0;                         // slots of the obs - background row that are columns of the union
+            const float* const cb = colbuf + cofs * U_MAXU + (orow < u ? orow : 0);
+            const double* const cd = colL + cofs;
+#pragma unroll
+            for(int k = 0; k < HS; ++k) {
+                double v = 0.0;
+                if(k <= rk) {
+                    v = (double)cb[k * U_MAXU];
+                    if(k == rk) v += (double)rdiag;                                                        // lP + lR
+                }
+                if(k < dk) v = cd[k];
+                row[k] = v;
+            }
+        }
+        else {
 #pragma unroll
         for(int p = 0; p < NC; ++p) {
             double v = 0.0;
@@ -1280,6 +1313,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 if(lane == 63) v = colL[p];
             }
             row[p] = v;
+        }
         }
         // columns 32..u-1 do not fit the 32-column register tile: their entries (rows >= 32 and the obs - background row) wait
         // in LDS and are reduced after the elimination
@@ -1375,6 +1409,69 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         }
         else {
         // right-looking Cholesky over the core columns; the trailing rows/columns end as B, the Schur complement, L_C^-1 d, d'
+        if constexpr(SPLIT) {
+        typedef double d2v __attribute__((ext_vector_type(2)));
+        static_assert((U_SOLVE - 64) % 2 == 0, "colL and its pairs are 16-byte aligned");
+        const double* const cm = colL + cofs;       // the multiplier of slot k: column k resp. HO + k of the factor's current column
+        double* const cw = colL + lane;             // first 18 steps: the lower lanes publish their entries (rows 0 .. 39, and 63); what an upper lane writes, at 40 .. 62, nobody reads
+        double* const cr = colL + orow;             // the entry of this lane's row
+#pragma unroll
+        for(int j = 0; j < NC; ++j) {
+            if(j < c) {
+                if(j < HS) {
+                    // the pivot and the column's entries are the lower lanes'; an upper lane takes its row's entry back from LDS, behind the same
+                    // write the multipliers wait for (the lower lanes read their own back: no select between two sources)
+                    const double ajj = readlane_d(row[j], j);
+                    if(!(ajj > 0.0)) bad = true;
+                    const double rs = rsqrt_nr(ajj);
+                    if(lane == 0) sv[oI + j] = rs;
+                    *cw = row[j] * rs;
+                    const double cj = *cr;
+                    if(!up) row[j] = cj;
+                    // slots j + 1 .. 17 are columns both halves still update; slots 4 .. j are final columns of a lower lane and columns 18 + of an
+                    // upper one: masked, never multiplied by zero.  (Slots 1 .. 3 of an upper lane hold nothing: the first three steps need no mask.)
+                    constexpr int K4 = 4;
+                    const int k0 = j + 1 < K4 ? j + 1 : K4;
+                    double mv[HS];
+                    const int pe = (k0 + 1) & ~1;
+                    if(pe != k0) mv[k0] = cm[k0];
+#pragma unroll
+                    for(int k = pe; k < HS; k += 2) {
+                        const d2v v = reinterpret_cast<const d2v*>(cm)[k >> 1];
+                        mv[k] = v.x; mv[k + 1] = v.y;
+                    }
+#pragma unroll
+                    for(int k = j + 1; k < HS; ++k) row[k] = __builtin_fma(-cj, mv[k], row[k]);
+                    if(up) {
+#pragma unroll
+                        for(int k = K4; k <= j; ++k) row[k] = __builtin_fma(-cj, mv[k], row[k]);
+                    }
+                }
+                else {
+                    // columns 18 .. : pivot, entries and updates are the upper lanes'
+                    const int s = j - HO;
+                    const double ajj = readlane_d(row[s], j + HL);
+                    if(!(ajj > 0.0)) bad = true;
+                    const double rs = rsqrt_nr(ajj);
+                    if(lane == 0) sv[oI + j] = rs;
+                    if(up) {
+                        const double cj = row[s] * rs;
+                        row[s] = cj;
+                        *cr = cj;
+                        const int pe = (s + 2) & ~1;
+                        if(pe != s + 1) row[s + 1] = __builtin_fma(-cj, cm[s + 1], row[s + 1]);
+#pragma unroll
+                        for(int k = pe; k < HS; k += 2) {
+                            const d2v v = reinterpret_cast<const d2v*>(cm)[k >> 1];
+                            row[k] = __builtin_fma(-cj, v.x, row[k]);
+                            row[k + 1] = __builtin_fma(-cj, v.y, row[k + 1]);
+                        }
+                    }
+                }
+            }
+        }
+        }
+        else {
 #pragma unroll
         for(int j = 0; j < NC; ++j) {
             if(j < c) {
@@ -1405,6 +1502,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 }
             }
         }
+        }
         UPROF(8);   // row load + elimination
         // export: L_C rows packed, B rows (stride bs), L_C^-1 d, Schur complement, d'
         // (the export and the finish compare against copies of c and u the optimiser cannot see through, like st.h above: it otherwise keeps
@@ -1413,7 +1511,29 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         int ce = c, ue = u;
         asm("" : "+s"(ce), "+s"(ue));
         const int ea = lane - c;   // extras row index of this lane
-        {   // one masked store per column: every lane has a last column and two bases (columns below c / from c on); written
+        const int eo = orow - c;   // SPLIT: extras row index of this lane's row
+        if constexpr(SPLIT) {   // one masked store per slot; last column, the two bases and the column where they change shifted by the half's first column
+            int maxp = -1, baseLo = 0, baseHi = 0;
+            if(orow < c) { maxp = orow; baseLo = oL + orow * (orow + 1) / 2; baseHi = baseLo; }
+            else if(orow < u) { maxp = u - 1; baseLo = oB + eo * bs; baseHi = oS + eo * nE - c; }
+            else if(orow == 63) { maxp = u - 1; baseLo = oZ; baseHi = oD - c; }
+            const int maxk = maxp - cofs, ck = ce - cofs;
+            baseLo += cofs; baseHi += cofs;
+#pragma unroll
+            for(int k = 0; k < HS; ++k) {
+                const int bse = (k < ck) ? baseLo : baseHi;
+                if(k <= maxk && (k >= 2 * HS - NC || !up)) sv[bse + k] = row[k];     // (slots 0 .. 3 of an upper lane are nobody's)
+            }
+            // The upper triangle of the Schur complement is never used, but the padded reads of the per-cell finish touch it (times z = 0) and
+            // an extras row below 18 has no lane that holds its columns 18 .. : zeros where the unsplit rows left finite leftovers
+            if(ce < HS && ue > HS) {
+                if(lane >= c && lane < HS) {
+#pragma nounroll
+                    for(int p = HS; p < min(ue, NC); ++p) sv[oS + ea * nE + (p - c)] = 0.0;
+                }
+            }
+        }
+        else {   // one masked store per column: every lane has a last column and two bases (columns below c / from c on); written
             // with nested ifs this loop compiled to ~60 mostly scalar instructions and a dozen branches per column
             int maxp = -1, baseLo = 0, baseHi = 0;
             if(lane < c) { maxp = lane; baseLo = oL + lane * (lane + 1) / 2; baseHi = baseLo; }
@@ -1438,6 +1558,41 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                     const bool mine = (lane >= p && lane < u) || lane == 63;
                     double acc = mine ? L.late[b][lidx] : 0.0;
                     const double* const bp = sv + oB + (p - c) * bs;
+                    if constexpr(SPLIT) {
+                        // ONE chain in the order k = 0 .. c - 1: the lower lane runs the columns below 18 and hands the sum to its upper lane, which
+                        // runs the rest and stores (two partial sums added would round differently).  Every lane runs both parts on its own
+                        // slots; what the other half computes there is dropped.
+                        auto part = [&](const int k, const int sl) {   // columns k .. k + 3 in slots sl .. sl + 3, grouped as below
+                            if(k + 3 < ce) {
+                                const double b0 = bp[k], b1 = bp[k + 1], b2 = bp[k + 2], b3 = bp[k + 3];
+                                acc = __builtin_fma(-row[sl], b0, acc);
+                                acc = __builtin_fma(-row[sl + 1], b1, acc);
+                                acc = __builtin_fma(-row[sl + 2], b2, acc);
+                                acc = __builtin_fma(-row[sl + 3], b3, acc);
+                            }
+                            else if(k < ce) {
+                                acc = __builtin_fma(-row[sl], bp[k], acc);
+                                if(k + 1 < ce) acc = __builtin_fma(-row[sl + 1], bp[k + 1], acc);
+                                if(k + 2 < ce) acc = __builtin_fma(-row[sl + 2], bp[k + 2], acc);
+                            }
+                        };
+#pragma unroll
+                        for(int k = 0; k + 3 < HS; k += 4) part(k, k);
+#pragma unroll
+                        for(int k = HS & ~3; k < HS; ++k) if(k < ce) acc = __builtin_fma(-row[k], bp[k], acc);
+                        // (a late column means u > 32, i.e. c >= 33 - U_MAXE = 21 core columns: the chain always goes on in the upper half)
+                        static_assert(NC + 1 - U_MAXE > HS, "the chain of a late column ends in the upper half");
+                        acc = __hiloint2double(__shfl(__double2hiint(acc), orow), __shfl(__double2loint(acc), orow));
+#pragma unroll
+                        for(int k = HS; k < ((HS + 3) & ~3); ++k) if(k < ce) acc = __builtin_fma(-row[k - HO], bp[k], acc);
+#pragma unroll
+                        for(int k = (HS + 3) & ~3; k < NC; k += 4) part(k, k - HO);
+                        if(up) {
+                            if(orow >= p && orow < u) sv[oS + eo * nE + (p - c)] = acc;
+                            else if(orow == 63) sv[oD + (p - c)] = acc;
+                        }
+                    }
+                    else {
                     // (round 9: four columns behind one test while whole groups lie below c, the reads of a group issued together; the
                     //  group that holds column c - 1 one by one -- the registers behind it hold the Schur complement, not zeros, so nothing
                     //  may be read past the row here as the per-cell finish does)
@@ -1458,6 +1613,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                     }
                     if(lane >= p && lane < u) sv[oS + ea * nE + (p - c)] = acc;
                     else if(lane == 63) sv[oD + (p - c)] = acc;
+                    }
                 }
             }
         }
