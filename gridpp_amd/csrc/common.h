@@ -1,6 +1,7 @@
 // Shared host-side definitions of libgridpp_hip.so (not part of the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cmath>
 #include <mutex>
 #include <cstdarg>
@@ -84,7 +85,15 @@ inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes
     launch_on(stream(), kernel, grid, block, lds_bytes, static_cast<A&&>(args)...);
 }
 inline size_t blocks_of(size_t n, size_t per = 256) { return (n + per - 1) / per; }                     // the flat grid of n items
-inline unsigned grid_capped(size_t items, size_t cap) { return (unsigned)(items < cap ? items : cap); }   // the grid of a kernel that strides over it beyond `cap`
+// The grid of a kernel that strides over it beyond `cap`.  GPP_GRID_CAP=n (a path override, n >= 1) caps every such grid at n workgroups as well, so that
+// a small shape sends each workgroup through the loop several times (tests/test_gpu_grid_stride.py).  The launch path takes no lock for it:
+// gpp_set_path_override keeps the value in g_grid_cap (0: not set) and this reads it relaxed.
+extern std::atomic<unsigned> g_grid_cap;   // runtime.hip
+inline unsigned grid_capped(size_t items, size_t cap) {
+    const size_t n = g_grid_cap.load(std::memory_order_relaxed);
+    if(n && n < cap) cap = n;
+    return (unsigned)(items < cap ? items : cap);
+}
 inline unsigned magic_div(int d) { return (unsigned)((1ull << 32) / (unsigned)d + 1); }                   // x / d == umulhi(x, magic_div(d)) for the small x of a tile (not for d == 1, where it does not fit)
 inline int pow2_at_least(int len) { int p = 2; while(p < len) p <<= 1; return p; }                        // the padded length of a bitonic network: a power of two >= len, at least 2
 

@@ -195,10 +195,8 @@ int compute_units() {
 template <bool LDS, int VEC>
 void launch_shared(const float* in, long long nvec, const float* cx, const float* cy, int nc, int pb, int pa, int sorted, int interp, float* out) {
     if(nvec <= 0) return;
-    const long long want = (nvec + SHARED_BLOCK - 1) / SHARED_BLOCK;
     // a staged curve is loaded once per workgroup: two resident workgroups per compute unit walk the values with a grid stride
-    const long long cap = (long long)compute_units() * 2;
-    const unsigned blocks = (unsigned)std::min(want, cap);
+    const unsigned blocks = grid_capped(blocks_of(nvec, SHARED_BLOCK), (size_t)compute_units() * 2);
     const size_t lds = LDS ? (size_t)2 * nc * sizeof(float) : 0;
     launch(k_curve_shared<LDS, VEC>, blocks, SHARED_BLOCK, lds, in, nvec, cx, cy, nc, pb, pa, sorted, interp, out);
 }

@@ -1193,8 +1193,7 @@ void member_pass_launch(const float* d_in, long C, int E, int statistic, const f
     static std::once_flag attr_once;
     std::call_once(attr_once, [] { GPP_HIP(hipFuncSetAttribute((const void*)k_member_pass<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ((16 * MEMBER_EC + 63) / 64) * 1024)); });
     const int waves_per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / std::max<size_t>(lds, 1)));
-    const long grid = std::min<long>(tiles, (long)256 * waves_per_cu);
-    launch(k_member_pass<MODE>, (unsigned)grid, 64, lds, d_in, C, E, statistic, d_thr, T, d_out, dma ? 1 : 0, g);
+    launch(k_member_pass<MODE>, grid_capped(tiles, (size_t)256 * waves_per_cu), 64, lds, d_in, C, E, statistic, d_thr, T, d_out, dma ? 1 : 0, g);
 }
 void member_pass(const float* d_in, long C, int E, int mode, int statistic, const float* d_thr, int T, float* d_out, const QfGeom& g = QfGeom()) {
     if(mode == 0) member_pass_launch<0>(d_in, C, E, statistic, d_thr, T, d_out, g);
@@ -1207,8 +1206,7 @@ void qf_count_launch_nl(const float* d_in, long C, int E, const float* d_thr, in
     const size_t lds = (size_t)(2 * QF_NB + std::max(16 * E, NL * 64)) * sizeof(unsigned) + (size_t)(T + 1) * 256;
     int waves_per_cu = (int)std::max<size_t>(1, std::min<size_t>(24, (160 * 1024) / lds));
     if(path_env("GPP_QF_WAVES")) waves_per_cu = std::max(1, std::min(waves_per_cu, atoi(path_env("GPP_QF_WAVES"))));   // (A/B: fewer, longer streams)
-    const long grid = std::max<long>(1, std::min<long>((C / 64 + 3) / 4, (long)256 * waves_per_cu));
-    launch(k_qf_count<NL>, (unsigned)grid, 64, lds, d_in, C, E, d_thr, T, lut, cnt8, g, Uexp);
+    launch(k_qf_count<NL>, grid_capped(std::max<long>(1, (C / 64 + 3) / 4), (size_t)256 * waves_per_cu), 64, lds, d_in, C, E, d_thr, T, lut, cnt8, g, Uexp);
 }
 template <int... I> auto qf_count_form(std::integer_sequence<int, I...>, int U) { static constexpr decltype(&qf_count_launch_nl<3>) forms[] = {qf_count_launch_nl<I + 3>...}; return forms[U - 1]; }
 void qf_count_launch(const float* d_in, long C, int E, const float* d_thr, int T, const QfLut* lut, int U, unsigned char* cnt8, const QfGeom& g, const int Uexp) {

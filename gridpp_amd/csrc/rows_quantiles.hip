@@ -270,9 +270,8 @@ void rows_quantiles(const float* d_in, long rows, int len, const float* h_levels
         const size_t lds = ((size_t)64 * (len | 1) + (size_t)64 * (qc | 1)) * sizeof(unsigned);
         // One workgroup per tile (grid-stride only beyond 2^20 tiles): a grid sized to the resident set, as k_rows_tile's is, has to guess how
         // many waves fit a CU, and a guess one too high leaves 256 workgroups to run their share of the tiles alone at the end
-        const long grid = std::min<long>((rows + 63) / 64, 1L << 20);
         const int vec_ok = (reinterpret_cast<size_t>(d_in) & 15) == 0;
-        launch(k_rowsq_tile, (unsigned)grid, 64, lds, d_in, rows, len, magic_div(len), vec_ok, lv.p, nq, qc, magic_div(qc), magic_div(tail), ends, d_out);
+        launch(k_rowsq_tile, grid_capped((rows + 63) / 64, (size_t)1 << 20), 64, lds, d_in, rows, len, magic_div(len), vec_ok, lv.p, nq, qc, magic_div(qc), magic_div(tail), ends, d_out);
         break;
     }
     case RQ_BLOCK: {

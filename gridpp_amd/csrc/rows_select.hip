@@ -432,13 +432,12 @@ void rows_quantile(const float* d_in, long rows, int len, const float* d_q, int 
     case RS_TILE: {
         const size_t lds = (size_t)64 * (len | 1) * sizeof(unsigned);
         const long waves_per_cu = std::max<long>(1, std::min<long>(16, (160 * 1024) / (long)lds));
-        const long grid = std::min<long>((rows + 63) / 64, 256 * waves_per_cu);
         const int vec_ok = (reinterpret_cast<size_t>(d_in) & 15) == 0;
-        launch(k_rows_tile, (unsigned)grid, 64, lds, d_in, rows, len, magic_div(len), vec_ok, d_q, q_per_row, d_out);
+        launch(k_rows_tile, grid_capped((rows + 63) / 64, 256 * waves_per_cu), 64, lds, d_in, rows, len, magic_div(len), vec_ok, d_q, q_per_row, d_out);
         break;
     }
     case RS_BLOCK:
-        launch(k_rows_block, (unsigned)std::min<long>(rows, 256 * 8), 256, 0, d_in, rows, len, d_q, q_per_row, d_out);
+        launch(k_rows_block, grid_capped(rows, 256 * 8), 256, 0, d_in, rows, len, d_q, q_per_row, d_out);
         break;
     case RS_SPLIT:
         rs_split(d_in, rows, len, d_q, q_per_row, d_out);

@@ -79,6 +79,14 @@ static const char* intern_override_value(const char* v) {
     override_values.emplace_back(new std::string(v));
     return override_values.back()->c_str();
 }
+std::atomic<unsigned> g_grid_cap{0};   // GPP_GRID_CAP as a number (common.h: grid_capped), 0 while it is not set or names no count >= 1
+static void grid_cap_from(const char* name, const char* value) {   // (called with the table's mutex held)
+    if(strcmp(name, "GPP_GRID_CAP") != 0) return;
+    char* end = nullptr;
+    const long long n = value ? strtoll(value, &end, 10) : 0;
+    const bool ok = value && end != value && *end == 0 && n >= 1;
+    g_grid_cap.store(ok ? (unsigned)std::min<long long>(n, 0xffffffffll) : 0u, std::memory_order_relaxed);
+}
 const char* path_override(const char* name) {
     std::lock_guard<std::mutex> lock(g_override_mutex);
     for(auto& kv : override_table()) if(kv.first == name) return kv.second;
@@ -92,6 +100,7 @@ extern "C" int gpp_set_path_override(const char* name, const char* value) {
     if(!name || strncmp(name, "GPP_", 4) != 0) invalid("override names start with GPP_");
     std::lock_guard<std::mutex> lock(g_override_mutex);
     auto& t = override_table();
+    grid_cap_from(name, value);
     for(size_t i = 0; i < t.size(); i++)
         if(t[i].first == name) {
             if(value) { if(strcmp(t[i].second, value) != 0) t[i].second = intern_override_value(value); }

@@ -35,8 +35,7 @@ void corr_launch(const gpp_structure* s, const float p1[7], const float* x, cons
                  const float* laf, int stride, long long n, int background, float* d_out) {
     const gpp_structure t = gpp_structure_at(s, p1[5], p1[6]);
     const DevStructure d = gpp_resolve_structure(&t);
-    const long long blocks = std::min((n + CORR_BLOCK - 1) / CORR_BLOCK, CORR_MAX_BLOCKS);
-    launch(k_structure_corr_many, (unsigned)blocks, CORR_BLOCK, 0, d, make_float4(p1[0], p1[1], p1[2], p1[3]), p1[4], x, y, z, elev, laf, stride, n, background, d_out);
+    launch(k_structure_corr_many, grid_capped(blocks_of(n, CORR_BLOCK), CORR_MAX_BLOCKS), CORR_BLOCK, 0, d, make_float4(p1[0], p1[1], p1[2], p1[3]), p1[4], x, y, z, elev, laf, stride, n, background, d_out);
 }
 
 }   // namespace

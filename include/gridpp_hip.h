@@ -82,7 +82,12 @@ int gpp_device_count(int* count);
 /* Path overrides: switches that select between implementations with identical results (the tests reach rarely taken paths with them, A/B
  * timings compare them).  The library reads NO environment variable: an override exists only after gpp_set_path_override(name, value)
  * (name = "GPP_...", value NULL clears it; process-wide).  gpp_active_overrides: the names that are set, comma separated, into buf (NUL
- * terminated); returns how many -- a benchmark must run with none.  No counterpart in the reference. */
+ * terminated); returns how many -- a benchmark must run with none.  No counterpart in the reference.
+ * GPP_GRID_CAP = n (n >= 1) is the one override that is no choice of a path: every kernel that walks its work with a grid stride is launched
+ * with at most n workgroups (beside its own cap, which stays), so that a small input sends each workgroup through its loop several times, as
+ * only a field far beyond the cap does otherwise.  A value below 1 or not a number has no effect (the name is still listed).  No result
+ * depends on it, except where a kernel adds inexact per-workgroup partial sums in grid order (the general path of gpp_fractions_skill_score:
+ * within that function's stated tolerance). */
 int gpp_set_path_override(const char* name, const char* value);
 int gpp_active_overrides(char* buf, int len);
 /* releases the library's large call-to-call device workspaces (kept otherwise for the next call) and the pool of staging buffers that the
