@@ -240,6 +240,12 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
+// Its sibling inside one wave: what single lanes wrote to LDS before it, every lane of the wave may read after it (the compiler reorders the accesses otherwise).
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // ---- point set ---------------------------------------------------------------
 struct gpp_obs_index;   // oi.hip: bin-sorted observation block

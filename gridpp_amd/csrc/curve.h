@@ -43,12 +43,12 @@ GPP_HD int upper_index(float x, const float* v, int n) {
 }
 
 // true where a bisection finds the indices of the two scans: every entry valid, the curve non-decreasing
-inline bool sorted_and_valid(const float* v, int n) {
+inline bool valid_and_sorted(const float* v, int n) {
     for(int i = 0; i < n; i++)
         if(!valid(v[i]) || (i > 0 && v[i] < v[i - 1])) return false;
     return true;
 }
-// The two scan indices of a sorted_and_valid curve for v[0] <= x <= v[n-1], by bisection: lb = first entry >= x, ub = first entry
+// The two scan indices of a valid_and_sorted curve for v[0] <= x <= v[n-1], by bisection: lb = first entry >= x, ub = first entry
 // > x.  Where an entry equals x the scans stop at the first (from the front) and the last (from the back) of them: lb and ub - 1;
 // otherwise at the neighbours of the gap: lb - 1 and lb.
 GPP_HD void sorted_indices(float x, const float* v, int n, int& i0, int& i1) {
@@ -80,7 +80,7 @@ GPP_HD float between(float x, int i0, int i1, int n, float x0, float x1, float y
     return y0 + (y1 - y0) * (x - x0) / (x1 - x0);
 }
 
-// util.cpp:377-414 (sizes already checked).  sorted: iX is sorted_and_valid
+// util.cpp:377-414 (sizes already checked).  sorted: iX is valid_and_sorted
 GPP_HD float interpolate(float x, const float* iX, const float* iY, int n, bool sorted) {
     if(!valid(x)) return NAN;
     if(n == 0) return NAN;
@@ -129,7 +129,7 @@ GPP_HD float extrapolate(float input, const float* curve_ref, const float* curve
     return nearestObs + slope * (input - nearestFcst);
 }
 
-// curve.cpp:6-77 (sizes already checked, C >= 1).  sorted: curve_fcst is sorted_and_valid
+// curve.cpp:6-77 (sizes already checked, C >= 1).  sorted: curve_fcst is valid_and_sorted
 GPP_HD float apply(float input, const float* curve_ref, const float* curve_fcst, int C, int policy_below, int policy_above, bool sorted,
                    bool* unknown) {
     if(input >= curve_fcst[0] && input <= curve_fcst[C - 1]) return interpolate(input, curve_fcst, curve_ref, C, sorted);

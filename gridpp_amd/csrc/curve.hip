@@ -214,7 +214,7 @@ void run_shared(const float* in, long long n, const float* cx, const float* cy, 
         GPP_HIP(hipMemcpyAsync(c.p, cx, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, stream()));
         GPP_HIP(hipMemcpyAsync(c.p + nc, cy, (size_t)nc * sizeof(float), hipMemcpyHostToDevice, stream()));
     }
-    const int sorted = curve::sorted_and_valid(cx, nc) ? 1 : 0;
+    const int sorted = curve::valid_and_sorted(cx, nc) ? 1 : 0;
     const bool lds = 2 * (long long)nc <= CURVE_LDS_FLOATS;
     const bool wide = (((uintptr_t)v.d | (uintptr_t)o.d) & 15) == 0;
     const long long n4 = wide ? n / 4 : 0;
@@ -311,7 +311,7 @@ extern "C" int gpp_apply_curve_scalar(float input, const float* curve_ref, int n
     check_curve_sizes(nc_ref, nc_fcst);
     if(!curve_ref || !curve_fcst || !out) invalid("curve / out is NULL");
     bool unknown = false;
-    const float y = curve::apply(input, curve_ref, curve_fcst, nc_ref, policy_below, policy_above, curve::sorted_and_valid(curve_fcst, nc_fcst),
+    const float y = curve::apply(input, curve_ref, curve_fcst, nc_ref, policy_below, policy_above, curve::valid_and_sorted(curve_fcst, nc_fcst),
                                  &unknown);
     if(unknown) invalid("Unknown extrapolation policy");   // curve.cpp:70-72: only where the input extrapolates with it
     *out = y;
@@ -326,7 +326,7 @@ extern "C" int gpp_interpolate_scalar(float x, const float* ix, int nc_x, const 
     if(nc_x != nc_y) invalid("Dimension mismatch. Cannot interpolate.");
     if(nc_x < 0) invalid("negative curve size");
     if(nc_x > 0 && (!ix || !iy)) invalid("curve is NULL");
-    *out = curve::interpolate(x, ix, iy, nc_x, curve::sorted_and_valid(ix, nc_x));
+    *out = curve::interpolate(x, ix, iy, nc_x, curve::valid_and_sorted(ix, nc_x));
     return GPP_OK;
     GPP_CATCH
 }

@@ -63,7 +63,7 @@ struct EnsiArgs {
 // member validity over the whole field (oi_ensi.cpp:187-201): flags[e] = 0 if any cell is invalid
 __global__ void k_ensi_member_flags(const float* __restrict__ bg, long n, int E, int* __restrict__ flags) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n && !d_valid(bg[i])) flags[(int)(i % E)] = 0;
+    if(i < n && !dev_valid(bg[i])) flags[(int)(i % E)] = 0;
 }
 // gYhat / gY (oi_ensi.cpp:166-178): row mean with calc_statistic(Mean) semantics over ALL members
 __global__ void k_ensi_obs_prep(const float* __restrict__ pbg, int S, int E, const int* __restrict__ validIdx, int nV,
@@ -72,12 +72,12 @@ __global__ void k_ensi_obs_prep(const float* __restrict__ pbg, int S, int E, con
     if(s >= S) return;
     const float* row = pbg + (long)s * E;
     float total = 0; int count = 0;
-    for(int e = 0; e < E; e++) { float v = row[e]; if(d_valid(v)) { total += v; count++; } }
+    for(int e = 0; e < E; e++) { float v = row[e]; if(dev_valid(v)) { total += v; count++; } }
     float mean = count > 0 ? total / (float)count : NAN;
     gYhat[s] = mean;
     for(int k = 0; k < nV; k++) {
         float v = row[validIdx[k]];
-        gY[(long)s * nV + k] = (d_valid(v) && d_valid(mean)) ? v - mean : v;
+        gY[(long)s * nV + k] = (dev_valid(v) && dev_valid(mean)) ? v - mean : v;
     }
 }
 // cells that found at least one usable observation (k_ensi_scan's meta: the count in the low byte): what the reference counts as
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(256) void k_ensi_big_ns(EnsiArgs a) {
         if(tid < 64) s_val[tid] = value;
         __syncthreads();
         float total = 0; int count = 0;
-        for(int k = 0; k < nV; ++k) { const float v = s_val[k]; if(d_valid(v)) { total += v; count++; } }
+        for(int k = 0; k < nV; ++k) { const float v = s_val[k]; if(dev_valid(v)) { total += v; count++; } }
         const float ensMean = total / (float)count;
         if(tid < nV) s_X[tid] = (double)value - (double)ensMean;
         __syncthreads();
@@ -758,7 +758,7 @@ __global__ __launch_bounds__(256) void k_ensi_huge(EnsiArgs a, const int* __rest
         __threadfence_block();
         __syncthreads();
         float total = 0; int cnt = 0;
-        for(int k = 0; k < nV; ++k) { const float v = (float)v_val[k]; if(d_valid(v)) { total += v; cnt++; } }
+        for(int k = 0; k < nV; ++k) { const float v = (float)v_val[k]; if(dev_valid(v)) { total += v; cnt++; } }
         const float ensMean = total / (float)cnt;
         for(int k = tid; k < nV; k += 256) v_X[k] = v_val[k] - (double)ensMean;
         __threadfence_block();
@@ -902,17 +902,15 @@ struct EnsiCall {
     void copy_background() {   // output = background (oi_ensi.cpp:146, oi_ensi_multi.cpp:375)
         f_bg.bind(background, (size_t)C * E, mem);
         f_out.bind(out, (size_t)C * E, mem);
-        hipLaunchKernelGGL(k_copy, dim3((unsigned)((nbg + 255) / 256)), dim3(256), 0, stream(), f_bg.d, nbg, f_out.d);
-        GPP_HIP(hipGetLastError());
+        launch(k_copy, blocks_of(nbg), 256, 0, f_bg.d, nbg, f_out.d);
     }
-    void finish_early() { f_out.finish(); GPP_HIP(hipStreamSynchronize(stream())); }   // the background is the answer
+    int finish_early() { return finish_call(f_out); }   // the background is the answer
     void index_obs() { bgrid->to_device(); ix = gpp_build_obs_index(points); }
     // members valid in every one of the fields (host list; E is small): oi_ensi.cpp:187-201, oi_ensi_multi.cpp:395-418
     void valid_members(std::initializer_list<Field> fields) {
         std::vector<int> flags(E, 1);
         ws.flags.upload(flags.data(), E);
-        for(const Field& f : fields)
-            hipLaunchKernelGGL(k_ensi_member_flags, dim3((unsigned)((f.n + 255) / 256)), dim3(256), 0, stream(), f.d, f.n, E, ws.flags.p);
+        for(const Field& f : fields) launch(k_ensi_member_flags, blocks_of(f.n), 256, 0, f.d, f.n, E, ws.flags.p);
         GPP_HIP(hipMemcpyAsync(flags.data(), ws.flags.p, sizeof(int) * E, hipMemcpyDeviceToHost, stream()));
         GPP_HIP(hipStreamSynchronize(stream()));
         for(int e = 0; e < E; e++) if(flags[e]) valid.push_back(e);
@@ -920,9 +918,8 @@ struct EnsiCall {
     }
     void pack_obs(const float* obs, const float* fourth) {   // oaux = (laf, obs, gYhat, fourth); pgeo: the usable observations
         ws.pgeo.get(S); ws.oaux.get(S);
-        hipLaunchKernelGGL(k_pack_obs, dim3((S + 255) / 256), dim3(256), 0, stream(), S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p,
-                           obs, fourth, (const float*)ws.gYhat.p, (const float*)nullptr, 0, ws.pgeo.p, ws.oaux.p);
-        GPP_HIP(hipGetLastError());
+        launch(k_pack_obs, blocks_of(S), 256, 0, S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p, obs, fourth, (const float*)ws.gYhat.p, (const float*)nullptr, 0,
+               ws.pgeo.p, ws.oaux.p, (float4*)nullptr, (unsigned long long*)nullptr, 0);   // (no sorted copy, no status block to clear)
     }
     void bind_scan() {   // the grid, the observation index, the structure and the members: what both sets of kernels read
         a.gx = bgrid->d_x.p; a.gy = bgrid->d_y.p; a.gz = bgrid->d_z.p; a.gelev = bgrid->d_elev.p; a.glaf = bgrid->d_laf.p;
@@ -962,7 +959,7 @@ struct EnsiCall {
     void prep_obs() {   // the perturbations of the valid members at the observations, the observation block, the status words
         ws.validIdx.upload(valid.data(), nV);
         ws.gYhat.get(S); ws.gY.get((size_t)S * nV);
-        hipLaunchKernelGGL(k_ensi_obs_prep, dim3((S + 127) / 128), dim3(128), 0, stream(), f_pbg.d, S, E, ws.validIdx.p, nV, ws.gYhat.p, ws.gY.p);
+        launch(k_ensi_obs_prep, blocks_of(S, 128), 128, 0, f_pbg.d, S, E, ws.validIdx.p, nV, ws.gYhat.p, ws.gY.p);
         pack_obs(f_obs.d, f_sig.d);   // (fourth: sigma; only the observation itself must be valid, oi_ensi.cpp:235)
         ws.err.get(1); ws.counters.get(NCOUNTERS);
         GPP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(int), stream()));
@@ -998,16 +995,13 @@ struct EnsiCall {
     // the scan, then the spectral side (k_ensi_pair: pairs of cells, warm-started along a tile) and the ensemble side in batches of tiles
     void run_tiles() {   // LAYOUT: in front of launch_members
         a.meta = ws.meta.get((size_t)a.ntiles * 64); a.hsigs = ws.hsigs.get((size_t)a.ntiles * 64);
-        if(a.s.st.fh) hipLaunchKernelGGL(k_ensi_scan<true>, dim3(a.ntiles), dim3(64), 0, stream(), a);
-        else hipLaunchKernelGGL(k_ensi_scan<false>, dim3(a.ntiles), dim3(64), 0, stream(), a);
-        GPP_HIP(hipGetLastError());
-        if(nV <= 1) hipLaunchKernelGGL(k_ensi_count_cells, dim3(256), dim3(256), 0, stream(), (const unsigned*)a.meta, (long)a.ntiles * 64, ws.counters.p + 72);
+        launch(a.s.st.fh ? k_ensi_scan<true> : k_ensi_scan<false>, a.ntiles, 64, 0, a);
+        if(nV <= 1) launch(k_ensi_count_cells, 256, 256, 0, (const unsigned*)a.meta, (long)a.ntiles * 64, ws.counters.p + 72);
         const int tcap = park_tiles();
         for(int t0 = 0; t0 < a.ntiles; t0 += tcap) {
             const int nt = std::min(tcap, a.ntiles - t0);
             a.tile0 = t0;
-            if(a.s.st.fh) hipLaunchKernelGGL(k_ensi_pair<true>, dim3(nt), dim3(64), 0, stream(), a);
-            else hipLaunchKernelGGL(k_ensi_pair<false>, dim3(nt), dim3(64), 0, stream(), a);
+            launch(a.s.st.fh ? k_ensi_pair<true> : k_ensi_pair<false>, nt, 64, 0, a);
             launch_members(nt);
         }
     }
@@ -1029,11 +1023,8 @@ struct EnsiCall {
     }
     void launch_members(const int nt) {   // the ensemble side, one wave per cell.  LAYOUT: behind run_tiles, in front of run_huge
         // (at most 64 valid members: the three-waves-per-SIMD form, ensi_members3.h; GPP_ENSI_MEMBERS2: the two-area kernel it replaced)
-        const dim3 grid((unsigned)nt * 64u), block(64);
-        if(a.nV <= 64 && !path_env("GPP_ENSI_MEMBERS2")) hipLaunchKernelGGL(k_ensi_members3, grid, block, 0, stream(), a);
-        else if(a.nV <= 64) hipLaunchKernelGGL(k_ensi_members<true>, grid, block, 0, stream(), a);
-        else hipLaunchKernelGGL(k_ensi_members<false>, grid, block, 0, stream(), a);
-        GPP_HIP(hipGetLastError());
+        const Kernel form = a.nV <= 64 ? (!path_env("GPP_ENSI_MEMBERS2") ? k_ensi_members3 : k_ensi_members<true>) : k_ensi_members<false>;
+        launch(form, (unsigned)nt * 64u, 64, 0, a);
     }
     void run_huge(const int* list, const int* count, const int nitems) {   // the general kernel, keys + E x E matrices in HBM.  LAYOUT: in front of launch_big_ns
         const size_t mat = 2 * (size_t)nV * nV + 5 * (size_t)nV;
@@ -1042,9 +1033,7 @@ struct EnsiCall {
         a.huge_kcap = hs.kcap;
         a.huge_keys = ws.huge_keys.get((size_t)hs.nwg * hs.kcap);
         a.huge_mat = ws.huge_mat.get((size_t)hs.nwg * mat);
-        if(a.s.st.fh) hipLaunchKernelGGL(k_ensi_huge<true>, dim3(hs.nwg), dim3(256), 0, stream(), a, list, count);
-        else hipLaunchKernelGGL(k_ensi_huge<false>, dim3(hs.nwg), dim3(256), 0, stream(), a, list, count);
-        GPP_HIP(hipGetLastError());
+        launch(a.s.st.fh ? k_ensi_huge<true> : k_ensi_huge<false>, hs.nwg, 256, 0, a, list, count);
     }
     void launch_big_ns(const int nbig) {   // one member per lane; forms[not FULL][not SPATIAL], FULL: 49..64 valid members.  LAYOUT: the order of `forms`
         static constexpr Kernel forms[2][2] = {{k_ensi_big_ns<true, true>, k_ensi_big_ns<false, true>}, {k_ensi_big_ns<true, false>, k_ensi_big_ns<false, false>}};
@@ -1054,8 +1043,7 @@ struct EnsiCall {
         std::call_once(ns_once, [] {
             for(const auto& row : forms) for(const Kernel k : row) GPP_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NS_LDS));
         });
-        hipLaunchKernelGGL(forms[nV > 48 ? 0 : 1][a.s.st.fh ? 0 : 1], dim3(nwg), dim3(256), NS_LDS, stream(), a);
-        GPP_HIP(hipGetLastError());
+        launch(forms[nV > 48 ? 0 : 1][a.s.st.fh ? 0 : 1], nwg, 256, NS_LDS, a);
     }
     void run_big() {   // the cells with more than 32 usable observations
         int nbig = 0;
@@ -1105,8 +1093,8 @@ struct EnsiCall {
         if(variant == 1 && nV > 4096) runtime("optimal_interpolation_ensi_multi_ebe: more than 4096 valid ensemble members are not supported on the GPU path");
         ws.validIdx.upload(valid.data(), nV);
         ws.gYhat.get(S); ws.gY.get((size_t)S * nV); ws.gYm.get((size_t)S * nV); ws.obs0.get(S);
-        hipLaunchKernelGGL(k_multi_obs_prep, dim3((S + 127) / 128), dim3(128), 0, stream(), variant, f_pbg.d, corr ? f_pbgc.d : f_pbg.d, f_obs.d, S, E,
-                           (const int*)ws.validIdx.p, nV, ws.gY.p, ws.gYm.p, ws.gYhat.p, ws.obs0.p);
+        launch(k_multi_obs_prep, blocks_of(S, 128), 128, 0, variant, f_pbg.d, corr ? f_pbgc.d : f_pbg.d, f_obs.d, S, E, (const int*)ws.validIdx.p, nV, ws.gY.p, ws.gYm.p,
+               ws.gYhat.p, ws.obs0.p);
         pack_obs(ws.obs0.p, f_sig.d);   // (obs[.][0] / obs and pratio: an observation is usable when that first value is valid, :480)
         ws.err.get(1);
         GPP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(int), stream()));
@@ -1122,8 +1110,7 @@ struct EnsiCall {
     }
     int launch_multi() {   // returns the grid points beyond the LDS areas of k_ensi_multi
         static constexpr void (*forms[3])(MultiArgs) = {k_ensi_multi<1>, k_ensi_multi<2>, k_ensi_multi<3>};
-        hipLaunchKernelGGL(forms[variant - 1], dim3(multi_wgs()), dim3(256), 0, stream(), ma);
-        GPP_HIP(hipGetLastError());
+        launch(forms[variant - 1], multi_wgs(), 256, 0, ma);
         int nhuge = 0;
         GPP_HIP(hipMemcpyAsync(&nhuge, ws.big_count.p + 1, sizeof(int), hipMemcpyDeviceToHost, stream()));
         GPP_HIP(hipStreamSynchronize(stream()));
@@ -1139,8 +1126,7 @@ struct EnsiCall {
         a.huge_kcap = hs.kcap; ma.huge_ncap = (int)ncap; ma.huge_stride = stride;
         a.huge_keys = ws.huge_keys.get((size_t)hs.nwg * hs.kcap);
         a.huge_mat = ws.huge_mat.get((size_t)hs.nwg * stride);
-        hipLaunchKernelGGL(forms[variant - 1], dim3(hs.nwg), dim3(256), 0, stream(), ma, all ? nullptr : a.huge_list, all ? nullptr : a.big_count + 1);
-        GPP_HIP(hipGetLastError());
+        launch(forms[variant - 1], hs.nwg, 256, 0, ma, all ? nullptr : a.huge_list, all ? nullptr : a.big_count + 1);
     }
 };
 }
@@ -1157,10 +1143,10 @@ extern "C" int gpp_optimal_interpolation_ensi(gpp_points* bgrid, const float* ba
     g_ensi_stats = gpp_ensi_stats{(long long)c.C, 0, 0, 0.0f};
     if(c.C == 0 || c.E == 0) return GPP_OK;
     c.copy_background();
-    if(c.S == 0) { c.finish_early(); return GPP_OK; }    // oi_ensi.cpp:135-137
+    if(c.S == 0) return c.finish_early();    // oi_ensi.cpp:135-137
     c.stage_obs(obs, sigmas, background_at_points);
     c.valid_members({{c.f_bg.d, c.nbg}});
-    if(c.nV == 0) { c.finish_early(); return GPP_OK; }
+    if(c.nV == 0) return c.finish_early();
     c.prep_obs();
     c.plan_tiles();
     c.bind_scan();
@@ -1198,10 +1184,10 @@ extern "C" int gpp_optimal_interpolation_ensi_multi(int variant, gpp_points* bgr
     g_ensi_ms = 0;
     if(c.C == 0 || c.E == 0) return GPP_OK;
     c.copy_background();
-    if(c.S == 0) { c.finish_early(); return GPP_OK; }    // oi_ensi_multi.cpp:361-363
+    if(c.S == 0) return c.finish_early();    // oi_ensi_multi.cpp:361-363
     c.stage_multi(bratios, background_corr, pobs, pratios, pbackground, pbackground_corr);
     c.multi_valid_members();
-    if(c.nV == 0) { c.finish_early(); return GPP_OK; }   // :419-420
+    if(c.nV == 0) return c.finish_early();   // :419-420
     c.prep_multi_obs();
     c.fill_multi_args();
     c.big_lists();

@@ -26,12 +26,12 @@ struct MultiArgs {
 // calc_statistic(Mean) / (Std) of row[0..n) through an accessor (util.cpp:22-75: sequential float accumulation)
 template <class F> __device__ __forceinline__ float seq_mean_f(const int n, F at) {
     float total = 0; int count = 0;
-    for(int i = 0; i < n; ++i) { const float v = at(i); if(d_valid(v)) { total += v; count++; } }
+    for(int i = 0; i < n; ++i) { const float v = at(i); if(dev_valid(v)) { total += v; count++; } }
     return count > 0 ? total / (float)count : NAN;
 }
 template <class F> __device__ __forceinline__ float seq_std_f(const int n, F at) {
     float total = 0, total2 = 0, K = NAN; int count = 0;
-    for(int i = 0; i < n; ++i) { const float v = at(i); if(d_valid(v)) { if(!d_valid(K)) K = v; const float d = v - K; total += d; total2 += d * d; count++; } }
+    for(int i = 0; i < n; ++i) { const float v = at(i); if(dev_valid(v)) { if(!dev_valid(K)) K = v; const float d = v - K; total += d; total2 += d * d; count++; } }
     if(count == 0) return NAN;
     const float mean = total / (float)count, mean2 = total2 / (float)count;
     float var = mean2 - mean * mean;
@@ -50,14 +50,14 @@ __global__ void k_multi_obs_prep(const int variant, const float* __restrict__ pb
     if(variant == 3) {
         const float* row = pbg + (long)s * E;
         const float mean = seq_mean_f(nV, [&](int k) { return row[validIdx[k]]; });
-        for(int k = 0; k < nV; ++k) gYm[(long)s * nV + k] = d_valid(mean) ? row[validIdx[k]] - mean : 0.0f;
+        for(int k = 0; k < nV; ++k) gYm[(long)s * nV + k] = dev_valid(mean) ? row[validIdx[k]] - mean : 0.0f;
         gYhat[s] = mean;
     }
     if(variant != 2) {
         const float* row = pbgc + (long)s * E;
         const float mean = seq_mean_f(nV, [&](int k) { return row[validIdx[k]]; });
         const float sd = seq_std_f(nV, [&](int k) { return row[validIdx[k]]; });
-        const bool ok = d_valid(mean) && d_valid(sd) && sd > 0.0013f;
+        const bool ok = dev_valid(mean) && dev_valid(sd) && sd > 0.0013f;
         const float const_fact = (float)(1.0 / sqrt((double)(nV - 1)));
         for(int k = 0; k < nV; ++k) {
             float z = 0.0f;
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void k_ensi_multi(MultiArgs ma) {
                 }
                 __syncthreads();
                 const float mean = s_ms[0], sd = s_ms[1];
-                const bool ok = d_valid(mean) && d_valid(sd) && sd > 0.0013f;
+                const bool ok = dev_valid(mean) && dev_valid(sd) && sd > 0.0013f;
                 for(int k = tid; k < nV; k += 256) xL[k] = ok ? 1.0 / sqrt((double)(nV - 1)) * (double)(rowc[a.validIdx[k]] - mean) / (double)sd : 0.0;   // :531-541
                 __syncthreads();
             }
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256) void k_ensi_multi_huge(MultiArgs ma, const int
                 }
                 __syncthreads();
                 const float mean = s_st[0], sd = s_st[1];
-                const bool ok = d_valid(mean) && d_valid(sd) && sd > 0.0013f;
+                const bool ok = dev_valid(mean) && dev_valid(sd) && sd > 0.0013f;
                 for(int k = tid; k < nV; k += 256) xL[k] = ok ? 1.0 / sqrt((double)(nV - 1)) * (double)(rowc[a.validIdx[k]] - mean) / (double)sd : 0.0;   // :531-541
                 __threadfence_block();
                 __syncthreads();

@@ -38,7 +38,7 @@ constexpr int LDC_LDS_MAX = 512;   // pairs per cell the LDS path takes: 2 x 512
 // the bits of a non-negative float as a sort key (-0 -> +0)
 __device__ __forceinline__ unsigned key_bits(float v) { return __float_as_uint(v == 0.0f ? 0.0f : v); }
 __device__ __forceinline__ bool ldc_kept(float o, float b) {   // :99-102
-    return d_valid(o) && d_valid(b) && !(o < 0) && !(b < 0);
+    return dev_valid(o) && dev_valid(b) && !(o < 0) && !(b < 0);
 }
 
 // Kept pairs per cell, and the result of every cell that needs no curve: out = background (:70) where the background is not
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_ldc_count(IxView ix, float R, const flo
     const float b = background[y];
     float r = b;
     int c = 0;
-    if(d_valid(b)) {
+    if(dev_valid(b)) {
         visit_radius(ix, px[y], py[y], pz[y], R, true, [&](int, int orig, float) {
             for(int t = 0; t < nT; ++t) c += ldc_kept(pobs[(size_t)t * nS + orig], pbg[(size_t)t * nS + orig]) ? 1 : 0;
         });

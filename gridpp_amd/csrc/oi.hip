@@ -98,8 +98,7 @@ static gpp_obs_index* build_obs_index_device(gpp_points* pts) {
     // stable sort of the point indices by bin (index order inside a bin, like the host build)
     DevBuf<int> bin, sbin, iota, order;
     bin.get(S); sbin.get(S); iota.get(S); order.get(S);
-    hipLaunchKernelGGL(k_ix_bins, dim3((S + 255) / 256), dim3(256), 0, stream(), dax[a], dax[b], S, ix->amin, ix->bmin, ix->inv_s, nbx, nby, bin.p, iota.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_ix_bins, blocks_of(S), 256, 0, dax[a], dax[b], S, ix->amin, ix->bmin, ix->inv_s, nbx, nby, bin.p, iota.p);
     int bits = 1;
     while((1ll << bits) < nbins) bits++;
     size_t sb = 0;
@@ -108,11 +107,10 @@ static gpp_obs_index* build_obs_index_device(gpp_points* pts) {
     stmp.get(sb);
     GPP_HIP(rocprim::radix_sort_pairs((void*)stmp.p, sb, bin.p, sbin.p, iota.p, order.p, (size_t)S, 0u, (unsigned)bits, stream()));
     ix->d_bin_start.get(nbins + 1);
-    hipLaunchKernelGGL(k_ix_starts, dim3((nbins + 1 + 255) / 256), dim3(256), 0, stream(), sbin.p, S, nbins, ix->d_bin_start.p);
+    launch(k_ix_starts, blocks_of(nbins + 1), 256, 0, sbin.p, S, nbins, ix->d_bin_start.p);
     ix->d_sgeo.get(S); ix->d_smeta.get(S); ix->d_pos.get(S); ix->d_ogeo.get(S); ix->d_olaf.get(S);
-    hipLaunchKernelGGL(k_ix_gather, dim3((S + 255) / 256), dim3(256), 0, stream(), order.p, S, pts->d_x.p, pts->d_y.p, pts->d_z.p, pts->d_elev.p, pts->d_laf.p,
-                       ix->d_sgeo.p, ix->d_smeta.p, ix->d_pos.p, ix->d_ogeo.p, ix->d_olaf.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_ix_gather, blocks_of(S), 256, 0, order.p, S, pts->d_x.p, pts->d_y.p, pts->d_z.p, pts->d_elev.p, pts->d_laf.p,
+           ix->d_sgeo.p, ix->d_smeta.p, ix->d_pos.p, ix->d_ogeo.p, ix->d_olaf.p);
     GPP_HIP(hipStreamSynchronize(stream()));
     pts->obs_index = ix.release();
     return pts->obs_index;
@@ -260,9 +258,7 @@ __device__ __forceinline__ void oi_solve_pair(const OiArgs& a, const int lane, c
     // obs and background at the observations for the obs - background row (lane 30 of the half): obs rides in column
     // position 30 of every matrix column, the background in row 30 of the staging area
     if(hl < nh) { colbuf[hl][base + 30] = o1.y; colbuf[30][base + hl] = o1.z; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     double row[30];
     const bool used = hl < nh || hl >= 30;
 #pragma unroll
@@ -304,9 +300,7 @@ __device__ __forceinline__ void oi_solve_pair(const OiArgs& a, const int lane, c
         if(hl == 30) colL[base + p] = row[p];           // L^-1 (obs - background)
     }
     // (one lane writes, the others read: without the fences the compiler orders the two sides per thread -- readers first)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 #pragma unroll
     for(int p = 0; p < 30; ++p) {
         const double tp = colL[base + p];
@@ -370,7 +364,7 @@ __global__ __launch_bounds__(256, (N <= 32 ? 2 : 1)) void k_oi(OiArgs a) {
         bg = a.bg[cell];
         if(a.bvar) bvar = a.bvar[cell];
     }
-    const bool active = cell >= 0 && d_valid(bg);   // oi.cpp:223
+    const bool active = cell >= 0 && dev_valid(bg);   // oi.cpp:223
     float res_out = bg, res_var = bvar;              // oi.cpp:198-199
     bool parked = false;                             // this cell's selection went to k_oi_pairs
     unsigned long long (*keys)[64] = s_keys[wid];
@@ -548,9 +542,7 @@ __global__ __launch_bounds__(256, (N <= 32 ? 2 : 1)) void k_oi(OiArgs a) {
                         // the cells of the group beyond the G rows that fit beside the matrix: z is theirs as well -- every such cell, in its
                         // own lane, adds corr_background(itself, obs j) z_j over the n observations (one pass for all of them instead of
                         // another factorisation per 31 cells)
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        wave_lds_sync();
                         double incx = 0.0;
                         for(int j = 0; j < n; ++j) {
                             const float xj = readlane_f(o0.x, j), yj = readlane_f(o0.y, j), zj_ = readlane_f(o0.z, j);
@@ -751,9 +743,7 @@ __global__ __launch_bounds__(256, (N <= 32 ? 2 : 1)) void k_oi(OiArgs a) {
                 else solve_group(la, __builtin_amdgcn_readlane(cnt, la), 1ull << la, 1, 0ull);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (results were written by single lanes: see solve_pair)
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();   // (results were written by single lanes: see solve_pair)
         if(cnt > 0) { res_out = s_res[wid][0][lane]; res_var = s_res[wid][1][lane]; }
         if(wave_ballot(bad) != 0ull && lane == 0) atomicOr(a.err, ERR_SINGULAR);
         if(lane == 0 && a.counters) {
@@ -814,9 +804,7 @@ __global__ __launch_bounds__(256, PLAIN ? 4 : 3) void k_oi_pairs(OiArgs a) {   /
                              [&](const int i, const int) { return mine[i]; }, s_cb[wid], s_col[wid], s_res[wid], a.gx[ch], a.gy[ch], a.gz[ch],
                              a.gelev[ch], a.glaf[ch], a.bg[ch], a.bvar ? a.bvar[ch] : 1.0f, bad);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (results were written by single lanes: see oi_solve_pair)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();   // (results were written by single lanes: see oi_solve_pair)
     if(n > 0) {
         a.out[cell] = s_res[wid][0][lane];
         if(a.out_var) a.out_var[cell] = s_res[wid][1][lane];
@@ -1408,8 +1396,7 @@ void gpp_bind_field(DevStructure& d, const gpp_structure* s, gpp_points* bgrid, 
                     if(f->grid->type != pts->type) invalid("the structure function's grid and the background must have the same coordinate type");
                     idx = field_indices(f, pts, tmpi);
                 }
-                hipLaunchKernelGGL(k_gather_scale, dim3((m + 255) / 256), dim3(256), 0, stream(), f ? src_c : (const float*)nullptr, idx, value, m, out + (part ? C : 0));
-                GPP_HIP(hipGetLastError());
+                launch(k_gather_scale, blocks_of(m), 256, 0, f ? src_c : (const float*)nullptr, idx, value, m, out + (part ? C : 0));
                 GPP_HIP(hipStreamSynchronize(stream()));   // tmpi is reused by the next lookup
             }
         };
@@ -1539,9 +1526,7 @@ extern "C" int gpp_structure_corr(const gpp_structure* s, const float p1[7], con
     DevStructure d = gpp_resolve_structure(&t);
     DevBuf<float> out;
     out.get(1);
-    hipLaunchKernelGGL(k_structure_corr, dim3(1), dim3(1), 0, stream(), d, make_float4(p1[0], p1[1], p1[2], p1[3]), p1[4],
-                       make_float4(p2[0], p2[1], p2[2], p2[3]), p2[4], background, out.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_structure_corr, 1, 1, 0, d, make_float4(p1[0], p1[1], p1[2], p1[3]), p1[4], make_float4(p2[0], p2[1], p2[2], p2[3]), p2[4], background, out.p);
     GPP_HIP(hipMemcpyAsync(rho, out.p, sizeof(float), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));
     return GPP_OK;
@@ -1602,26 +1587,28 @@ struct OiCall {
 
     // ================================================= launch helpers =================================================
     void launch_pack(hipStream_t on) {   // the observation block of this call (also clears the status block)
-        hipLaunchKernelGGL(k_pack_obs, dim3((S + 255) / 256), dim3(256), 0, on, S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p,
-                           f_obs.d, f_ov.d, f_pbg.d, f_bvp.d, 1, pgeo_b->p, oaux_b->p, saux_b->p, status_b->p, (int)SB);
-        GPP_HIP(hipGetLastError());
+        launch_on(on, k_pack_obs, blocks_of(S), 256, 0, S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p,
+                  f_obs.d, f_ov.d, f_pbg.d, f_bvp.d, 1, pgeo_b->p, oaux_b->p, saux_b->p, status_b->p, (int)SB);
     }
     void launch_k_oi(const bool lu, hipStream_t on) {   // k_oi over a.nrun tiles (all, or the fallback list of k_oi_union)
-        const dim3 grid((a.nrun + 3) / 4), block(256);
-        if(spatial) {   // (plain: three Barnes factors with per-point scales -- the straight-line correlation code takes them per lane)
-            if(N == 32) { if(plain) hipLaunchKernelGGL((k_oi<32, true, true, true>), grid, block, 0, on, a); else hipLaunchKernelGGL((k_oi<32, true, false, true>), grid, block, 0, on, a); }
-            else hipLaunchKernelGGL((k_oi<62, true, false, true>), grid, block, 0, on, a);
-        }
-        else if(N == 32) {
-            if(lu) hipLaunchKernelGGL((k_oi<32, true, false, false>), grid, block, 0, on, a);
-            else if(plain) hipLaunchKernelGGL((k_oi<32, false, true, false>), grid, block, 0, on, a);
-            else hipLaunchKernelGGL((k_oi<32, false, false, false>), grid, block, 0, on, a);
-        }
-        else {
-            if(lu) hipLaunchKernelGGL((k_oi<62, true, false, false>), grid, block, 0, on, a);
-            else hipLaunchKernelGGL((k_oi<62, false, false, false>), grid, block, 0, on, a);
-        }
-        GPP_HIP(hipGetLastError());
+        // k_oi<N, LU, PLAIN, SPATIAL> by [not spatial][N != 32][not lu][not plain].  A spatially varying structure always takes the pivoted LU (plain there: three
+        // Barnes factors with per-point scales -- the straight-line correlation code takes them per lane); PLAIN exists for the 32-row tile only, and not beside the
+        // scalar LU.  LAYOUT: the instantiations are laid out in the code object in the order the table names them first, hence the negated indices.
+        //   spatial  N   lu   plain ->  k_oi<...>
+        //   yes      32  any  no        <32, true,  false, true>
+        //   yes      32  any  yes       <32, true,  true,  true>
+        //   yes      62  any  any       <62, true,  false, true>
+        //   no       32  no   no        <32, false, false, false>
+        //   no       32  no   yes       <32, false, true,  false>
+        //   no       32  yes  any       <32, true,  false, false>
+        //   no       62  no   any       <62, false, false, false>
+        //   no       62  yes  any       <62, true,  false, false>
+        static constexpr void (*forms[2][2][2][2])(OiArgs) = {
+            {{{k_oi<32, true, true, true>, k_oi<32, true, false, true>}, {k_oi<32, true, true, true>, k_oi<32, true, false, true>}},
+             {{k_oi<62, true, false, true>, k_oi<62, true, false, true>}, {k_oi<62, true, false, true>, k_oi<62, true, false, true>}}},
+            {{{k_oi<32, true, false, false>, k_oi<32, true, false, false>}, {k_oi<32, false, true, false>, k_oi<32, false, false, false>}},
+             {{k_oi<62, true, false, false>, k_oi<62, true, false, false>}, {k_oi<62, false, false, false>, k_oi<62, false, false, false>}}}};
+        launch_on(on, forms[!spatial][N != 32][!lu][!plain], (a.nrun + 3) / 4, 256, 0, a);
     }
     // Cholesky path with the 32-row tile: the cells whose observation set no other cell of their work item shares (all of them on
     // rough terrain with elevation-dependent rho) are parked by k_oi and solved by k_oi_pairs at twice the occupancy (128 B of
@@ -1632,10 +1619,7 @@ struct OiCall {
         if(clear) GPP_HIP(hipMemsetAsync(a.pair_n, 0, (size_t)C * sizeof(int), on));
     }
     void launch_pairs(hipStream_t on) {
-        const dim3 grid((a.ntiles + 3) / 4), block(256);
-        if(plain) hipLaunchKernelGGL(k_oi_pairs<true>, grid, block, 0, on, a);
-        else hipLaunchKernelGGL(k_oi_pairs<false>, grid, block, 0, on, a);
-        GPP_HIP(hipGetLastError());
+        launch_on(on, plain ? k_oi_pairs<true> : k_oi_pairs<false>, (a.ntiles + 3) / 4, 256, 0, a);
         a.pair_sel = nullptr; a.pair_n = nullptr;
     }
     void fetch() {   // the whole status block in one copy
@@ -1656,9 +1640,7 @@ struct OiCall {
         a.huge_kcap = hs.kcap; a.huge_ncap = (int)ncap;
         a.huge_keys = ws.huge_keys.get((size_t)hs.nwg * hs.kcap);
         a.huge_mat = ws.huge_mat.get((size_t)hs.nwg * ncap * (ncap + 2));
-        if(spatial) hipLaunchKernelGGL(k_oi_huge<true>, dim3(hs.nwg), dim3(256), 0, stream(), a, d_list, d_count);
-        else hipLaunchKernelGGL(k_oi_huge<false>, dim3(hs.nwg), dim3(256), 0, stream(), a, d_list, d_count);
-        GPP_HIP(hipGetLastError());
+        launch(spatial ? k_oi_huge<true> : k_oi_huge<false>, hs.nwg, 256, 0, a, d_list, d_count);
     }
     void launch_union(const long items, const bool list, hipStream_t on) {   // the scalar tile kernel, one wave per work item
         const long nb = (items + WPB - 1) / WPB;
@@ -1667,19 +1649,17 @@ struct OiCall {
         if(N != 32 && max_points <= 48 && !path_env("GPP_OI_NO_UNION48")) gpp_launch_union48(a, grid.x, plain, list, on);
         else if(N != 32) gpp_launch_union64(a, grid.x, plain, list, on);
         // (round 6: the first pass of the 32-column form shares one factorisation between the two tiles of a pair)
-        else if(!list && pair_tiles) {
-            const dim3 pgrid((unsigned)std::min<long>(union_pair_count(a), 0x7fffffffL)), pblock(128);
-            if(plain) hipLaunchKernelGGL(k_oi_union_pair<true>, pgrid, pblock, 0, on, a); else hipLaunchKernelGGL(k_oi_union_pair<false>, pgrid, pblock, 0, on, a);
+        else if(!list && pair_tiles)
+            launch_on(on, plain ? k_oi_union_pair<true> : k_oi_union_pair<false>, (unsigned)std::min<long>(union_pair_count(a), 0x7fffffffL), 128, 0, a);
+        else {
+            const auto form = plain ? (list ? k_oi_union<true, true, 32> : k_oi_union<true, false, 32>) : (list ? k_oi_union<false, true, 32> : k_oi_union<false, false, 32>);
+            // (the first pass of the plain form is persistent: a grid that fills the chip, every wave strides over the tiles)
+            launch_on(on, form, plain && !list && UnionCfg<32>::persistent<true>() ? dim3(union_persist_grid<k_oi_union<true, false, 32>>(block.x, nb)) : grid, block, 0, a);
         }
-        // (the first pass is persistent: a grid that fills the chip, every wave strides over the tiles)
-        else if(plain) { if(list) hipLaunchKernelGGL((k_oi_union<true, true, 32>), grid, block, 0, on, a); else hipLaunchKernelGGL((k_oi_union<true, false, 32>), UnionCfg<32>::persistent<true>() ? dim3(union_persist_grid<k_oi_union<true, false, 32>>(block.x, nb)) : grid, block, 0, on, a); }
-        else { if(list) hipLaunchKernelGGL((k_oi_union<false, true, 32>), grid, block, 0, on, a); else hipLaunchKernelGGL((k_oi_union<false, false, 32>), grid, block, 0, on, a); }
-        GPP_HIP(hipGetLastError());
     }
 
     void launch_union_sp(hipStream_t on) {   // the first pass of a spatially varying Barnes structure: one LU per tile, two tiles per workgroup
-        hipLaunchKernelGGL(k_oi_union_sp<0>, dim3((unsigned)((a.ntiles + 1) / 2)), dim3(128), 0, on, a);
-        GPP_HIP(hipGetLastError());
+        launch_on(on, k_oi_union_sp<0>, (unsigned)((a.ntiles + 1) / 2), 128, 0, a);
     }
 
     // ================================================= the list passes =================================================
@@ -1691,8 +1671,7 @@ struct OiCall {
         a.in_list = in; a.in_count = in_count; a.out_list = out_l; a.out_count = out_count; a.level = level;
         if(!spatial) { launch_union(items, true, on); return; }
         const long nb = (items + UnionCfg<32>::WPB - 1) / UnionCfg<32>::WPB;
-        hipLaunchKernelGGL((k_oi_union<true, true, 32, true>), dim3((unsigned)std::min<long>(nb, 0x7fffffffL)), dim3(64 * UnionCfg<32>::WPB), 0, on, a);
-        GPP_HIP(hipGetLastError());
+        launch_on(on, k_oi_union<true, true, 32, true>, (unsigned)std::min<long>(nb, 0x7fffffffL), 64 * UnionCfg<32>::WPB, 0, a);
     }
     // k_oi over the 4-cell items the list passes left (grid-stride over fb_list3 with a grid of nrun tiles); `run` false: only the arguments
     void leftover_to_k_oi(const int nrun, const bool run, hipStream_t on) {
@@ -1931,8 +1910,7 @@ struct OiCall {
                 if(!band_f64) { GPP_HIP(hipMemcpyAsync(const_cast<float*>(dst) + off, src + off, cnt * sizeof(float), hipMemcpyHostToDevice, sUp)); return; }
                 // (the rounding of the reference's PyArray_CastToType, swig/vector.i:42-55, on the device: k_stage_f64)
                 GPP_HIP(hipMemcpyAsync(wide.p + off, reinterpret_cast<const double*>(src) + off, cnt * sizeof(double), hipMemcpyHostToDevice, sUp));
-                hipLaunchKernelGGL(k_stage_f64, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, sUp, (const double*)(wide.p + off), cnt, const_cast<float*>(dst) + off);
-                GPP_HIP(hipGetLastError());
+                launch_on(sUp, k_stage_f64, blocks_of(cnt), 256, 0, (const double*)(wide.p + off), cnt, const_cast<float*>(dst) + off);
             };
             up(background, f_bg.d, wide_bg);
             if(bvariance) up(bvariance, f_bvar.d, wide_bv);
@@ -2139,8 +2117,7 @@ struct OiCall {
         else n_add = std::min(overlap_new, a.ntiles - memo.nlist);
         if(n_add > 0) {
             GPP_HIP(hipMemcpyAsync(memo.list.p + memo.nlist, ws.fb_list.p, (size_t)n_add * sizeof(int), hipMemcpyDeviceToDevice, stream()));
-            hipLaunchKernelGGL(k_flag_tiles, dim3((n_add + 255) / 256), dim3(256), 0, stream(), (const int*)(memo.list.p + memo.nlist), n_add, a.ntiles, memo.flags.p);
-            GPP_HIP(hipGetLastError());
+            launch(k_flag_tiles, blocks_of(n_add), 256, 0, (const int*)(memo.list.p + memo.nlist), n_add, a.ntiles, memo.flags.p);
             memo.nlist += n_add;
             ws.h_status[SB] = (unsigned long long)memo.nlist;      // (pinned: one word behind the mirror of the status block)
             GPP_HIP(hipMemcpyAsync(memo.count.p, ws.h_status + SB, sizeof(int), hipMemcpyHostToDevice, stream()));
@@ -2161,8 +2138,7 @@ struct OiCall {
         a.big_mat = ws.big_mat.get((size_t)nwg * (BIG_N + 2) * BIG_N);
         ws.huge_list.get((size_t)nbig);
         a.huge_list = ws.huge_list.p; a.huge_count = d_huge_count;
-        hipLaunchKernelGGL(k_oi_big, dim3(nwg), dim3(256), 0, stream(), a);
-        GPP_HIP(hipGetLastError());
+        launch(k_oi_big, nwg, 256, 0, a);
         mark_and_fetch();
         const int nhuge = h_ints[5];
         if(nhuge > 0) {   // beyond BIG_N observations / BIG_CAND candidates
@@ -2197,9 +2173,7 @@ struct OiCall {
             }
             float* const d_pv = f_var.d ? d_patch + (size_t)np * 64 : nullptr;
             int* const d_ids = reinterpret_cast<int*>(d_patch + (size_t)np * 64 * (f_var.d ? 2 : 1));
-            hipLaunchKernelGGL(k_gather_tiles, dim3(np), dim3(64), 0, stream(), patch_l0, patch_n0, patch_l1, patch_n1, a.ny, a.nx, a.tiles_x, a.wshift,
-                               (const float*)f_out.d, (const float*)f_var.d, d_patch, d_pv, d_ids);
-            GPP_HIP(hipGetLastError());
+            launch(k_gather_tiles, np, 64, 0, patch_l0, patch_n0, patch_l1, patch_n1, a.ny, a.nx, a.tiles_x, a.wshift, (const float*)f_out.d, (const float*)f_var.d, d_patch, d_pv, d_ids);
             GPP_HIP(hipMemcpyAsync(ws.h_patch, d_patch, words * sizeof(float), hipMemcpyDeviceToHost, stream()));
         }
         GPP_HIP(hipStreamSynchronize(stream()));

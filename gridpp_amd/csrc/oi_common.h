@@ -59,7 +59,6 @@ inline HugeScratch huge_scratch(const int S, const size_t mat_bytes_per_wg, cons
 // -------------------------------------------------------------------------------------------
 // device helpers
 // -------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool d_valid(float v) { return !isnan(v) && !isinf(v); }
 
 // src/api/structure.cpp:26-34
 // exp(x) for x <= 0, accurate to < 1 ulp(double) (the result is only used rounded to float32, where the reference's
@@ -219,7 +218,7 @@ __device__ __forceinline__ double d_exp_nonpos(double x) {
 __device__ __forceinline__ float d_div_by(float dist, double rlen) { return (float)((double)dist * rlen); }
 // d_barnes_rho for a valid, non-zero length, without divergent branches.  Same values for every valid dist.  A NaN dist gives exp(-112.5) = 0
 // (fminf drops the NaN) -- what the reference returns for !is_valid(dist) (structure.cpp:28-29) -- and not NaN: callers that need to
-// know about a missing coordinate test d_valid() themselves (d_barnes_corr_flat does for the elevation / laf factors).  The exponential
+// know about a missing coordinate test dev_valid() themselves (d_barnes_corr_flat does for the elevation / laf factors).  The exponential
 // goes down to exp(-112.5) here (tests/test_exp_table.py checks [-112.5, -110] too; d_exp_half_neg returns d_exp_core's doubles).
 __device__ __forceinline__ float d_barnes_rho_flat(float dist, double rlen) {
     // (|v| cut at 15: exp(-112.5) = 1e-49 is 0 in float32 like everything below exp(-103.98) -- one float32 minimum instead of a double
@@ -228,8 +227,8 @@ __device__ __forceinline__ float d_barnes_rho_flat(float dist, double rlen) {
     return (float)d_exp_half_neg((double)v * (double)v);   // (v^2 is exact in double)
 }
 __device__ __forceinline__ float d_barnes_rho(float dist, float length) {
-    if(!d_valid(length) || length == 0) return 1.0f;
-    if(!d_valid(dist)) return 0.0f;
+    if(!dev_valid(length) || length == 0) return 1.0f;
+    if(!dev_valid(dist)) return 0.0f;
     float v = dist / length;
     double e = -0.5 * (double)v * (double)v;
     return (float)d_exp_nonpos(e);
@@ -239,8 +238,8 @@ __device__ __forceinline__ float d_barnes_rho(float dist, float length) {
 // thirty double constants in vector registers for the whole kernel (gfx950 has no 64-bit literals) -- what pushed the 62-row pivoted-LU
 // forms of k_oi into the accumulation registers; the table form has five.  Same accuracy class (< 1 ulp of the double, rounded to float32).
 __device__ __forceinline__ float d_barnes_rho_tab(float dist, float length) {
-    if(!d_valid(length) || length == 0) return 1.0f;
-    if(!d_valid(dist)) return 0.0f;
+    if(!dev_valid(length) || length == 0) return 1.0f;
+    if(!dev_valid(dist)) return 0.0f;
     const float v = dist / length;
     const double e = -0.5 * (double)v * (double)v;
     const float r = (float)d_exp_core(fmax(e, -110.0));
@@ -280,8 +279,8 @@ __device__ __forceinline__ float d_barnes_corr(float x1, float y1, float z1, flo
     float hdist = d_chord(x1, y1, z1, x2, y2, z2);
     if(hdist > R) return 0.0f;
     float rho = d_barnes_rho(hdist, h);
-    if(d_valid(e1) && d_valid(e2)) rho *= d_barnes_rho(e1 - e2, v);
-    if(d_valid(l1) && d_valid(l2)) rho *= d_barnes_rho(l1 - l2, w);
+    if(dev_valid(e1) && dev_valid(e2)) rho *= d_barnes_rho(e1 - e2, v);
+    if(dev_valid(l1) && dev_valid(l2)) rho *= d_barnes_rho(l1 - l2, w);
     return rho;
 }
 // ---- generic structure functions (src/api/structure.cpp:26-86,90-138,287-944), scalar forms -------------------
@@ -313,14 +312,14 @@ template <bool TAB>
 __device__ __forceinline__ float d_rho_x(const int kind, const float dist, const float length) {
     if(kind == SK_BARNES) return TAB ? d_barnes_rho_tab(dist, length) : d_barnes_rho(dist, length);
     if(kind == SK_LINEAR) {                                     // structure.cpp:76-86 (length = min_corr)
-        if(!d_valid(length) || length < 0) return 1.0f;
-        if(!d_valid(dist)) return 0.0f;
+        if(!dev_valid(length) || length < 0) return 1.0f;
+        if(!dev_valid(dist)) return 0.0f;
         float absdiff = fabsf(dist);
         if(absdiff > 1) absdiff = 1;
         return 1.0f - (1.0f - length) * absdiff;
     }
-    if(!d_valid(length) || length == 0) return 1.0f;
-    if(!d_valid(dist)) return 0.0f;
+    if(!dev_valid(length) || length == 0) return 1.0f;
+    if(!dev_valid(dist)) return 0.0f;
     if(kind == SK_CRESSMAN) {                                   // :35-44
         if(dist >= length) return 0.0f;
         return (length * length - dist * dist) / (length * length + dist * dist);
@@ -347,8 +346,8 @@ __device__ __forceinline__ float d_corr_x(const DevStructure& s, float x1, float
     if(background && s.cv && hdist <= s.cv_dist) return 0.0f;   // structure.cpp:918-925
     if(s.kh != SK_CRESSMAN && hdist > s.R) return 0.0f;         // :216-217 (Cressman has no cut, :300-312)
     float rho = d_rho_x<TAB>(s.kh, hdist, s.h);
-    if(d_valid(e1) && d_valid(e2)) rho *= d_rho_x<TAB>(s.kv, e1 - e2, s.v);
-    if(d_valid(l1) && d_valid(l2)) rho *= d_rho_x<TAB>(s.kw, l1 - l2, s.w);
+    if(dev_valid(e1) && dev_valid(e2)) rho *= d_rho_x<TAB>(s.kv, e1 - e2, s.v);
+    if(dev_valid(l1) && dev_valid(l2)) rho *= d_rho_x<TAB>(s.kw, l1 - l2, s.w);
     return rho;
 }
 __device__ __forceinline__ float d_corr(const DevStructure& s, float x1, float y1, float z1, float e1, float l1,
@@ -496,7 +495,7 @@ static __global__ void k_pack_obs(int S, const float4* __restrict__ sgeo, const 
     int p = pos[o];
     if(saux) saux[p] = make_float4(olaf[o], ob, pb, ratio);
     float4 g = sgeo[p];
-    bool ok = d_valid(ob) && (!need_pbg || d_valid(pb));
+    bool ok = dev_valid(ob) && (!need_pbg || dev_valid(pb));
     if(!ok) g.x = NAN;   // fails the box test of the radius query -> never a candidate
     pgeo[p] = g;
 }
@@ -507,17 +506,17 @@ static __global__ void k_pack_obs(int S, const float4* __restrict__ sgeo, const 
 // invalid elevation / laf on either side deselects its factor).  The reciprocals are loop invariants of the calling kernels.
 __device__ __forceinline__ float d_barnes_corr_flat(float x1, float y1, float z1, float e1, float l1, float x2, float y2, float z2, float e2,
                                                     float l2, float h, float v, float w, float R) {
-    const bool hh = d_valid(h) && h != 0.0f, hv = d_valid(v) && v != 0.0f, hw = d_valid(w) && w != 0.0f;
+    const bool hh = dev_valid(h) && h != 0.0f, hv = dev_valid(v) && v != 0.0f, hw = dev_valid(w) && w != 0.0f;
     const float hdist = d_chord(x1, y1, z1, x2, y2, z2);
     float rho = 1.0f;
     if(hh) rho = d_barnes_rho_flat(hdist, 1.0 / (double)h);
     if(hv) {
         const float f = d_barnes_rho_flat(e1 - e2, 1.0 / (double)v);
-        rho = (d_valid(e1) && d_valid(e2)) ? rho * f : rho;
+        rho = (dev_valid(e1) && dev_valid(e2)) ? rho * f : rho;
     }
     if(hw) {
         const float f = d_barnes_rho_flat(l1 - l2, 1.0 / (double)w);
-        rho = (d_valid(l1) && d_valid(l2)) ? rho * f : rho;
+        rho = (dev_valid(l1) && dev_valid(l2)) ? rho * f : rho;
     }
     return hdist > R ? 0.0f : rho;
 }
@@ -566,12 +565,12 @@ __device__ __forceinline__ int scan_tile(const ScanArgs& a, const DevStructure& 
     const float R = st.R;
     const int K = a.K;
     // scalar Barnes structure (PLAIN): which factors are enabled, and the reciprocals of their scales
-    const bool p_hh = d_valid(st.h) && st.h != 0.0f, p_hv = d_valid(st.v) && st.v != 0.0f, p_hw = d_valid(st.w) && st.w != 0.0f;
+    const bool p_hh = dev_valid(st.h) && st.h != 0.0f, p_hv = dev_valid(st.v) && st.v != 0.0f, p_hw = dev_valid(st.w) && st.w != 0.0f;
     const double p_rh = p_hh ? 1.0 / (double)st.h : 0.0, p_rv = p_hv ? 1.0 / (double)st.v : 0.0, p_rw = p_hw ? 1.0 / (double)st.w : 0.0;
     const bool bounded = a.max_points > 0 && a.max_points <= N;
     const float h2 = st.h * st.h;
     // h / v and h / w for the combined pruning test (0: factor disabled, or a ratio float32 cannot hold)
-    const float p_sv = (p_hh && p_hv && d_valid(st.h / st.v)) ? st.h / st.v : 0.0f, p_sw = (p_hh && p_hw && d_valid(st.h / st.w)) ? st.h / st.w : 0.0f;
+    const float p_sv = (p_hh && p_hv && dev_valid(st.h / st.v)) ? st.h / st.v : 0.0f, p_sw = (p_hh && p_hw && dev_valid(st.h / st.w)) ? st.h / st.w : 0.0f;
     const bool prune = bounded && (PLAIN || st.kh == SK_BARNES);   // rho <= rho_h(d) with the closed-form inverse of the Barnes kernel
     float pa = a.axis_a == 0 ? gx : (a.axis_a == 1 ? gy : gz);
     float pb = a.axis_b == 1 ? gy : (a.axis_b == 2 ? gz : gx);
@@ -632,8 +631,8 @@ __device__ __forceinline__ int scan_tile(const ScanArgs& a, const DevStructure& 
                         const float oe = readlane_f(rec.w, c), ol = readlane_f(met.x, c);
                         const float te = (ge - oe) * p_sv, tl = (gl - ol) * p_sw;
                         float q = d2;
-                        q = (p_sv != 0.0f && d_valid(ge) && d_valid(oe)) ? q + te * te : q;
-                        q = (p_sw != 0.0f && d_valid(gl) && d_valid(ol)) ? q + tl * tl : q;
+                        q = (p_sv != 0.0f && dev_valid(ge) && dev_valid(oe)) ? q + te * te : q;
+                        q = (p_sw != 0.0f && dev_valid(gl) && dev_valid(ol)) ? q + tl * tl : q;
                         pass = pass && q <= thrq * 1.0001f + 1e-4f * h2;
                     }
                 }
@@ -660,13 +659,13 @@ __device__ __forceinline__ int scan_tile(const ScanArgs& a, const DevStructure& 
                         float rho;
                         if constexpr(PLAIN) {   // straight-line code: the three exp chains interleave (same values as d_barnes_rho)
                             rho = p_hh ? d_barnes_rho_flat(dist, p_rh) : 1.0f;
-                            if(p_hv) { const float f = d_barnes_rho_flat(ge - oe, p_rv); rho = (d_valid(ge) && d_valid(oe)) ? rho * f : rho; }
-                            if(p_hw) { const float f = d_barnes_rho_flat(gl - ol, p_rw); rho = (d_valid(gl) && d_valid(ol)) ? rho * f : rho; }
+                            if(p_hv) { const float f = d_barnes_rho_flat(ge - oe, p_rv); rho = (dev_valid(ge) && dev_valid(oe)) ? rho * f : rho; }
+                            if(p_hw) { const float f = d_barnes_rho_flat(gl - ol, p_rw); rho = (dev_valid(gl) && dev_valid(ol)) ? rho * f : rho; }
                         }
                         else {
                             rho = (st.cv && dist <= st.cv_dist) ? 0.0f : d_rho_x<TAB>(st.kh, dist, st.h);   // corr_background
-                            if(d_valid(ge) && d_valid(oe)) rho *= d_rho_x<TAB>(st.kv, ge - oe, st.v);
-                            if(d_valid(gl) && d_valid(ol)) rho *= d_rho_x<TAB>(st.kw, gl - ol, st.w);
+                            if(dev_valid(ge) && dev_valid(oe)) rho *= d_rho_x<TAB>(st.kv, ge - oe, st.v);
+                            if(dev_valid(gl) && dev_valid(ol)) rho *= d_rho_x<TAB>(st.kw, gl - ol, st.w);
                         }
                         const bool ins_ = rho > 0.0f && (cnt < K || (((unsigned long long)__float_as_uint(rho) << 32) | 0xffffffffull) > wkey);
                         if(a.scan_stats && wave_ballot(ins_) != 0ull) nins++;
@@ -765,13 +764,13 @@ __device__ __forceinline__ int scan_tile(const ScanArgs& a, const DevStructure& 
                         float rho;
                         if constexpr(PLAIN) {   // straight-line code: the three exp chains interleave (same values as d_barnes_rho)
                             rho = p_hh ? d_barnes_rho_flat(dist, p_rh) : 1.0f;
-                            if(p_hv) { const float f = d_barnes_rho_flat(ge - oe, p_rv); rho = (d_valid(ge) && d_valid(oe)) ? rho * f : rho; }
-                            if(p_hw) { const float f = d_barnes_rho_flat(gl - ol, p_rw); rho = (d_valid(gl) && d_valid(ol)) ? rho * f : rho; }
+                            if(p_hv) { const float f = d_barnes_rho_flat(ge - oe, p_rv); rho = (dev_valid(ge) && dev_valid(oe)) ? rho * f : rho; }
+                            if(p_hw) { const float f = d_barnes_rho_flat(gl - ol, p_rw); rho = (dev_valid(gl) && dev_valid(ol)) ? rho * f : rho; }
                         }
                         else {
                             rho = (st.cv && dist <= st.cv_dist) ? 0.0f : d_rho_x<TAB>(st.kh, dist, st.h);   // corr_background
-                            if(d_valid(ge) && d_valid(oe)) rho *= d_rho_x<TAB>(st.kv, ge - oe, st.v);
-                            if(d_valid(gl) && d_valid(ol)) rho *= d_rho_x<TAB>(st.kw, gl - ol, st.w);
+                            if(dev_valid(ge) && dev_valid(oe)) rho *= d_rho_x<TAB>(st.kv, ge - oe, st.v);
+                            if(dev_valid(gl) && dev_valid(ol)) rho *= d_rho_x<TAB>(st.kw, gl - ol, st.w);
                         }
                         if(rho > 0.0f) truncated = true;
                     }

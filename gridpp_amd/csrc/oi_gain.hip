@@ -79,9 +79,7 @@ __global__ __launch_bounds__(64) void k_oi_gain_build(GainBuildArgs a) {
         }
         if(s < cnt) srt[r][lane] = ks;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     unsigned (*origs)[64] = reinterpret_cast<unsigned (*)[64]>(&s_a[0][0]);
     float (*rho)[64] = reinterpret_cast<float (*)[64]>(&s_a[N / 2][0]);
     for(int s = 0; s < maxc; ++s) {
@@ -91,9 +89,7 @@ __global__ __launch_bounds__(64) void k_oi_gain_build(GainBuildArgs a) {
             rho[s][lane] = __uint_as_float((unsigned)(k >> 32));
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     const size_t pbase = (size_t)tile * a.m.K * 64 + lane;
     for(int s = 0; s < a.m.K; ++s) {
@@ -128,9 +124,7 @@ __global__ __launch_bounds__(64) void k_oi_gain_build(GainBuildArgs a) {
             if(lane == p) v += (double)o1.w;
             M[p][lane] = lane < n ? v : 0.0;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         // In-place Gauss-Jordan.  Step k takes the unused row with the largest |entry| in column k (the lowest lane on a tie) as its pivot row
         // p_k, and slot k of every row then holds column p_k of the accumulated row operations E: at the end E (P + R) has its ones at
         // (p_k, k), i.e. (P + R)^-1[k][p_j] = slot j of lane p_k.  The other rows take the UNSCALED pivot row with the multiplier entry / pivot,
@@ -148,9 +142,7 @@ __global__ __launch_bounds__(64) void k_oi_gain_build(GainBuildArgs a) {
             if(lane == p) mystep = k;
             if(lane == k) mypiv = p;
             M[k][lane] = lane == p ? 1.0 : 0.0;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             // (slot j of the pivot row is read by every lane in the instruction before the pivot lane overwrites it, and no other slot is
             //  touched in between: the slots are independent, and unrolled their LDS round trips overlap -- at one wave per SIMD nothing else hides them)
             for(int j0 = 0; j0 < n; j0 += 6) {
@@ -161,21 +153,15 @@ __global__ __launch_bounds__(64) void k_oi_gain_build(GainBuildArgs a) {
                 for(int u = 0; u < 6; ++u)
                     if(j0 + u < n) M[j0 + u][lane] = lane == p ? pr[u] * rp : __builtin_fma(-f, pr[u], mine[u]);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
         // the rows into the order of their steps: M[j][k] = (P + R)^-1[k][p_j]
         for(int j = 0; j < n; ++j) {
             const double v = M[j][lane];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             if(lane < n && mystep >= 0) M[j][mystep] = v;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         // w = g (P + R)^-1 of every cell of the group (a cell per lane; g is the rho of its keys, oi.cpp:250), a = w . g
         double asum = 0.0;
         for(int j = 0; j < n; ++j) {
@@ -203,7 +189,7 @@ __global__ void k_oi_gain_innovation(const float* __restrict__ pobs, const int p
     const int s = (int)(i / E), e = (int)(i - (long long)s * E);
     const float ob = pobs[per_field ? i : s], pb = pbg[i];
     d[i] = (double)ob - (double)pb;
-    if(usable[s] && !(d_valid(ob) && d_valid(pb))) atomicMin(flag + e, s);
+    if(usable[s] && !(dev_valid(ob) && dev_valid(pb))) atomicMin(flag + e, s);
 }
 
 // the clamp of oi.cpp:318-334 on the float32 increment
@@ -229,7 +215,7 @@ __global__ __launch_bounds__(256) void k_oi_gain_apply(const GainMap m, const in
     for(int e = 0; e < E; ++e) {
         const float b = bg[(size_t)cell * E + e];
         float res = b;
-        if(n > 0 && d_valid(b)) {   // oi.cpp:223
+        if(n > 0 && dev_valid(b)) {   // oi.cpp:223
             double acc = 0.0;
             float maxInc = -INFINITY, minInc = INFINITY;
             for(int k = 0; k < n; ++k) {
@@ -297,7 +283,7 @@ __global__ __launch_bounds__(256) void k_oi_gain_apply_wide(const GainMap m, con
                 }
                 float increment = (float)acc;
                 if(!EXTRAP) increment = gain_clamp(increment, maxInc, minInc);
-                const float res = (n > 0 && d_valid(b)) ? b + increment : b;
+                const float res = (n > 0 && dev_valid(b)) ? b + increment : b;
                 if(e0 + lane < E) out[(size_t)cell * E + e] = res;
             }
             cell = cell_next; b = b_next;
@@ -401,9 +387,8 @@ extern "C" int gpp_oi_gain_create(gpp_points* bgrid, gpp_points* points, const f
     d_ob.upload(ob.data(), S); d_ratio.upload(pratios, S);
     pgeo.get(S); oaux.get(S); status.get(2);
     GPP_HIP(hipMemsetAsync(status.p, 0, 2 * sizeof(int), stream()));
-    hipLaunchKernelGGL(k_pack_obs, dim3((S + 255) / 256), dim3(256), 0, stream(), S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p, d_ob.p, d_ratio.p,
-                       (const float*)nullptr, (const float*)nullptr, 0, pgeo.p, oaux.p, (float4*)nullptr, (unsigned long long*)nullptr, 0);
-    GPP_HIP(hipGetLastError());
+    launch(k_pack_obs, blocks_of(S), 256, 0, S, ix->d_sgeo.p, ix->d_pos.p, ix->d_olaf.p, d_ob.p, d_ratio.p,
+           (const float*)nullptr, (const float*)nullptr, 0, pgeo.p, oaux.p, (float4*)nullptr, (unsigned long long*)nullptr, 0);
     GainBuildArgs a = GainBuildArgs();
     const int N = max_points <= 32 ? 32 : 62;
     gpp_scan_geometry(a.s, ix, S, max_points, N);
@@ -415,10 +400,8 @@ extern "C" int gpp_oi_gain_create(gpp_points* bgrid, gpp_points* points, const f
     a.ogeo = ix->d_ogeo.p; a.oaux = oaux.p;
     a.idx = g->idx.p; a.w = g->w.p; a.a = g->a.p; a.cnt = g->cnt.p; a.status = status.p;
     const bool plain = a.s.st.kh == GPP_SK_BARNES && a.s.st.kv == GPP_SK_BARNES && a.s.st.kw == GPP_SK_BARNES && !a.s.st.cv;
-    const dim3 grid((unsigned)m.ntiles), block(64);
-    if(N == 32) { if(plain) hipLaunchKernelGGL((k_oi_gain_build<32, true>), grid, block, 0, stream(), a); else hipLaunchKernelGGL((k_oi_gain_build<32, false>), grid, block, 0, stream(), a); }
-    else { if(plain) hipLaunchKernelGGL((k_oi_gain_build<62, true>), grid, block, 0, stream(), a); else hipLaunchKernelGGL((k_oi_gain_build<62, false>), grid, block, 0, stream(), a); }
-    GPP_HIP(hipGetLastError());
+    static constexpr void (*forms[2][2])(GainBuildArgs) = {{k_oi_gain_build<32, true>, k_oi_gain_build<32, false>}, {k_oi_gain_build<62, true>, k_oi_gain_build<62, false>}};
+    launch(forms[N != 32][plain ? 0 : 1], (unsigned)m.ntiles, 64, 0, a);
     int h_status[2] = {0, 0};
     GPP_HIP(hipMemcpyAsync(h_status, status.p, sizeof(h_status), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));
@@ -467,17 +450,13 @@ extern "C" int gpp_oi_gain_apply(gpp_oi_gain* gain, const float* background, int
     f_out.bind(out, n, mem);
     if(S == 0) {
         GPP_HIP(hipMemcpyAsync(f_out.d, f_bg.d, n * sizeof(float), hipMemcpyDeviceToDevice, stream()));
-        f_out.finish();
-        GPP_HIP(hipStreamSynchronize(stream()));
-        return GPP_OK;
+        return finish_call(f_out);
     }
     f_obs.bind(pobs, pobs_per_field ? (size_t)S * ne : (size_t)S, mem);
     f_pbg.bind(pbackground, (size_t)S * ne, mem);
     gain->d.get((size_t)S * ne); gain->flag.get(ne);
     GPP_HIP(hipMemsetAsync(gain->flag.p, 0x7f, (size_t)ne * sizeof(int), stream()));
-    hipLaunchKernelGGL(k_oi_gain_innovation, dim3((unsigned)(((size_t)S * ne + 255) / 256)), dim3(256), 0, stream(), f_obs.d, pobs_per_field ? 1 : 0,
-                       f_pbg.d, (const unsigned char*)gain->usable.p, S, ne, gain->d.p, gain->flag.p);
-    GPP_HIP(hipGetLastError());
+    launch(k_oi_gain_innovation, blocks_of((size_t)S * ne), 256, 0, f_obs.d, pobs_per_field ? 1 : 0, f_pbg.d, (const unsigned char*)gain->usable.p, S, ne, gain->d.p, gain->flag.p);
     std::vector<int> flag(ne);
     GPP_HIP(hipMemcpyAsync(flag.data(), gain->flag.p, (size_t)ne * sizeof(int), hipMemcpyDeviceToHost, stream()));
     GPP_HIP(hipStreamSynchronize(stream()));
@@ -486,22 +465,14 @@ extern "C" int gpp_oi_gain_apply(gpp_oi_gain* gain, const float* background, int
             invalid("optimal_interpolation_gain: pobs or pbackground is invalid at usable station " + std::to_string(flag[e]) + " of field " +
                     std::to_string(e) + " (mark the station unusable when the gain is built)");
     if(ne >= APPLY_WIDE_MIN_FIELDS) {
-        const dim3 grid((unsigned)gain->m.ntiles), block(256);
         const size_t lds = (size_t)gain->m.K * 64 * (sizeof(double) + sizeof(int)) + 64 * sizeof(int);
-        if(allow_extrapolation)
-            hipLaunchKernelGGL(k_oi_gain_apply_wide<true>, grid, block, lds, stream(), gain->m, (const int*)gain->idx.p, (const double*)gain->w.p,
-                               (const unsigned char*)gain->cnt.p, f_bg.d, (const double*)gain->d.p, ne, f_out.d);
-        else
-            hipLaunchKernelGGL(k_oi_gain_apply_wide<false>, grid, block, lds, stream(), gain->m, (const int*)gain->idx.p, (const double*)gain->w.p,
-                               (const unsigned char*)gain->cnt.p, f_bg.d, (const double*)gain->d.p, ne, f_out.d);
+        launch(allow_extrapolation ? k_oi_gain_apply_wide<true> : k_oi_gain_apply_wide<false>, (unsigned)gain->m.ntiles, 256, lds, gain->m, (const int*)gain->idx.p,
+               (const double*)gain->w.p, (const unsigned char*)gain->cnt.p, f_bg.d, (const double*)gain->d.p, ne, f_out.d);
     }
     else
-        hipLaunchKernelGGL(k_oi_gain_apply, dim3((unsigned)((gain->m.ntiles + 3) / 4)), dim3(256), 0, stream(), gain->m, (const int*)gain->idx.p,
-                           (const double*)gain->w.p, (const unsigned char*)gain->cnt.p, f_bg.d, (const double*)gain->d.p, ne, allow_extrapolation ? 1 : 0, f_out.d);
-    GPP_HIP(hipGetLastError());
-    f_out.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+        launch(k_oi_gain_apply, (gain->m.ntiles + 3) / 4, 256, 0, gain->m, (const int*)gain->idx.p, (const double*)gain->w.p, (const unsigned char*)gain->cnt.p,
+               f_bg.d, (const double*)gain->d.p, ne, allow_extrapolation ? 1 : 0, f_out.d);
+    return finish_call(f_out);
     GPP_CATCH
 }
 
@@ -517,12 +488,8 @@ extern "C" int gpp_oi_gain_variance(gpp_oi_gain* gain, const float* bvariance, f
     OutField f_out;
     f_bv.bind(bvariance, C, mem);
     f_out.bind(out, C, mem);
-    hipLaunchKernelGGL(k_oi_gain_variance, dim3((unsigned)((gain->m.ntiles + 3) / 4)), dim3(256), 0, stream(), gain->m, (const double*)gain->a.p,
-                       (const unsigned char*)gain->cnt.p, f_bv.d, f_out.d);
-    GPP_HIP(hipGetLastError());
-    f_out.finish();
-    GPP_HIP(hipStreamSynchronize(stream()));
-    return GPP_OK;
+    launch(k_oi_gain_variance, (gain->m.ntiles + 3) / 4, 256, 0, gain->m, (const double*)gain->a.p, (const unsigned char*)gain->cnt.p, f_bv.d, f_out.d);
+    return finish_call(f_out);
     GPP_CATCH
 }
 
@@ -538,9 +505,7 @@ extern "C" int gpp_oi_gain_selection(gpp_oi_gain* gain, int* counts, int* indice
     int* dc = counts ? (dev ? counts : t_counts.get(C)) : nullptr;
     int* di = indices ? (dev ? indices : t_indices.get(C * K)) : nullptr;
     double* dw = weights ? (dev ? weights : t_weights.get(C * K)) : nullptr;
-    hipLaunchKernelGGL(k_oi_gain_unpack, dim3((unsigned)((gain->m.ntiles + 3) / 4)), dim3(256), 0, stream(), gain->m, (const int*)gain->idx.p,
-                       (const double*)gain->w.p, (const unsigned char*)gain->cnt.p, dc, di, dw);
-    GPP_HIP(hipGetLastError());
+    launch(k_oi_gain_unpack, (gain->m.ntiles + 3) / 4, 256, 0, gain->m, (const int*)gain->idx.p, (const double*)gain->w.p, (const unsigned char*)gain->cnt.p, dc, di, dw);
     if(!dev) {
         if(counts) GPP_HIP(hipMemcpyAsync(counts, dc, C * sizeof(int), hipMemcpyDeviceToHost, stream()));
         if(indices) GPP_HIP(hipMemcpyAsync(indices, di, C * K * sizeof(int), hipMemcpyDeviceToHost, stream()));

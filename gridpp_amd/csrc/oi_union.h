@@ -258,7 +258,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         bg = a.bg[cell];
         if(a.bvar) bvar = a.bvar[cell];
     }
-    const bool active = cell >= 0 && d_valid(bg);   // oi.cpp:223
+    const bool active = cell >= 0 && dev_valid(bg);   // oi.cpp:223
     // (a copy whose scales the optimiser cannot see through when the item runs inside the tile loop of the persistent first pass: their
     //  reciprocals, squares and pruning constants are otherwise invariants of that loop, kept in a dozen vector registers)
     DevStructure st = a.s.st;
@@ -283,12 +283,12 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
     // evaluated for all 64 cells).  A cell without elevation takes the factor 1: then there is no extent.
     float emin_t = -INFINITY, emax_t = INFINITY, lmin_t = -INFINITY, lmax_t = INFINITY, kv2 = 0.0f, kw2 = 0.0f;
     if constexpr(PLAIN && !SP) {   // (SP: the ratios differ from cell to cell; the horizontal prune alone)
-        if(d_valid(st.v) && st.v != 0.0f && d_valid(st.h) && st.h != 0.0f) {
-            emin_t = wave_min(active ? (d_valid(ge) ? ge : -INFINITY) : INFINITY); emax_t = wave_max(active ? (d_valid(ge) ? ge : INFINITY) : -INFINITY);
+        if(dev_valid(st.v) && st.v != 0.0f && dev_valid(st.h) && st.h != 0.0f) {
+            emin_t = wave_min(active ? (dev_valid(ge) ? ge : -INFINITY) : INFINITY); emax_t = wave_max(active ? (dev_valid(ge) ? ge : INFINITY) : -INFINITY);
             kv2 = (st.h / st.v) * (st.h / st.v) * 0.9999f;
         }
-        if(d_valid(st.w) && st.w != 0.0f && d_valid(st.h) && st.h != 0.0f) {
-            lmin_t = wave_min(active ? (d_valid(gl) ? gl : -INFINITY) : INFINITY); lmax_t = wave_max(active ? (d_valid(gl) ? gl : INFINITY) : -INFINITY);
+        if(dev_valid(st.w) && st.w != 0.0f && dev_valid(st.h) && st.h != 0.0f) {
+            lmin_t = wave_min(active ? (dev_valid(gl) ? gl : -INFINITY) : INFINITY); lmax_t = wave_max(active ? (dev_valid(gl) ? gl : INFINITY) : -INFINITY);
             kw2 = (st.h / st.w) * (st.h / st.w) * 0.9999f;
         }
     }
@@ -394,7 +394,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         // the candidates `mask` of one chunk of 64 records (lane c holds record c: rec, met, sorted position posv)
         // rho(cell, candidate c of the chunk) as corr_background gives it, 0 when the candidate is not usable for this cell.
         // PLAIN: straight-line code (selects instead of branches) so that two candidates evaluated back to back interleave.
-        const bool hv = d_valid(st.v) && st.v != 0.0f, hw = d_valid(st.w) && st.w != 0.0f, hh = d_valid(st.h) && st.h != 0.0f;
+        const bool hv = dev_valid(st.v) && st.v != 0.0f, hw = dev_valid(st.w) && st.w != 0.0f, hh = dev_valid(st.h) && st.h != 0.0f;
         const double rh = hh ? 1.0 / (double)st.h : 0.0, rv_ = hv ? 1.0 / (double)st.v : 0.0, rw_ = hw ? 1.0 / (double)st.w : 0.0;
         // (SP: the scales are this lane's; the tests around the vertical / laf factors stay wave-uniform -- "some cell has one")
         const bool hvu = SP ? wave_ballot(hv) != 0ull : hv, hwu = SP ? wave_ballot(hw) != 0ull : hw;
@@ -416,19 +416,19 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 rho = hh ? d_barnes_rho_flat(dist, rh) : 1.0f;
                 if(hvu) {
                     const float oe = readlane_f(rec.w, c);
-                    if(d_valid(oe)) { const float f = d_barnes_rho_flat(ge - oe, rv_); rho = (hv && d_valid(ge)) ? rho * f : rho; }
+                    if(dev_valid(oe)) { const float f = d_barnes_rho_flat(ge - oe, rv_); rho = (hv && dev_valid(ge)) ? rho * f : rho; }
                 }
                 if(hwu) {
                     const float ol = readlane_f(met.x, c);
-                    if(d_valid(ol)) { const float f = d_barnes_rho_flat(gl - ol, rw_); rho = (hw && d_valid(gl)) ? rho * f : rho; }
+                    if(dev_valid(ol)) { const float f = d_barnes_rho_flat(gl - ol, rw_); rho = (hw && dev_valid(gl)) ? rho * f : rho; }
                 }
                 rho = ok ? rho : 0.0f;
             }
             else if(ok) {
                 const float oe = readlane_f(rec.w, c), ol = readlane_f(met.x, c);
                 rho = (st.cv && dist <= st.cv_dist) ? 0.0f : d_rho(st.kh, dist, st.h);   // corr_background
-                if(d_valid(ge) && d_valid(oe)) rho *= d_rho(st.kv, ge - oe, st.v);
-                if(d_valid(gl) && d_valid(ol)) rho *= d_rho(st.kw, gl - ol, st.w);
+                if(dev_valid(ge) && dev_valid(oe)) rho *= d_rho(st.kv, ge - oe, st.v);
+                if(dev_valid(gl) && dev_valid(ol)) rho *= d_rho(st.kw, gl - ol, st.w);
             }
             return rho;
         };
@@ -474,16 +474,16 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
 #pragma unroll
                 for(int q = 0; q < EV; ++q) {
                     const float oe = readlane_f(rec.w, cc[q]);
-                    const float f = d_barnes_rho_flat(d_valid(oe) ? ge - oe : 0.0f, rv_);
-                    rho[q] = (hv && d_valid(oe) && d_valid(ge)) ? rho[q] * f : rho[q];
+                    const float f = d_barnes_rho_flat(dev_valid(oe) ? ge - oe : 0.0f, rv_);
+                    rho[q] = (hv && dev_valid(oe) && dev_valid(ge)) ? rho[q] * f : rho[q];
                 }
             }
             if(hwu) {
 #pragma unroll
                 for(int q = 0; q < EV; ++q) {
                     const float ol = readlane_f(met.x, cc[q]);
-                    const float f = d_barnes_rho_flat(d_valid(ol) ? gl - ol : 0.0f, rw_);
-                    rho[q] = (hw && d_valid(ol) && d_valid(gl)) ? rho[q] * f : rho[q];
+                    const float f = d_barnes_rho_flat(dev_valid(ol) ? gl - ol : 0.0f, rw_);
+                    rho[q] = (hw && dev_valid(ol) && dev_valid(gl)) ? rho[q] * f : rho[q];
                 }
             }
 #pragma unroll
@@ -881,9 +881,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
     if constexpr(PAIR) {
         if(partner) {
             PairLds& P = *PP;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             if(lane < U_WCAP) P.pos[pw][lane] = (((coreM | extM) >> lane) & 1ull) ? L.wpos[lane] : -1;
             if(lane == 0) { P.core[pw] = coreM; P.state[pw] = fb ? 2 : (upd == 0ull ? 1 : 0); }
             UPROF(11);  // (classification of the own slots, publishing)
@@ -1036,16 +1034,14 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             if(lane < u) {
                 const int fi = su.obs_idx[oorig];
                 const float h_i = su.fh[fi], v_i = su.fv[fi], w_i = su.fw[fi];
-                rsc[lane] = (d_valid(h_i) && h_i != 0.0f) ? 1.0 / (double)h_i : 0.0;
-                rsc[40 + lane] = (d_valid(v_i) && v_i != 0.0f) ? 1.0 / (double)v_i : 0.0;
-                rsc[80 + lane] = (d_valid(w_i) && w_i != 0.0f) ? 1.0 / (double)w_i : 0.0;
+                rsc[lane] = (dev_valid(h_i) && h_i != 0.0f) ? 1.0 / (double)h_i : 0.0;
+                rsc[40 + lane] = (dev_valid(v_i) && v_i != 0.0f) ? 1.0 / (double)v_i : 0.0;
+                rsc[80 + lane] = (dev_valid(w_i) && w_i != 0.0f) ? 1.0 / (double)w_i : 0.0;
                 rR[lane] = su.fR[fi];
                 L.orec[lane] = o0; L.olaf[lane] = o1.x;
             }
             const bool anyv = wave_ballot(lane < u && rsc[40 + (lane < u ? lane : 0)] != 0.0) != 0ull, anyw = wave_ballot(lane < u && rsc[80 + (lane < u ? lane : 0)] != 0.0) != 0ull;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             // P(i, p) = corr(observation i, observation p) with the scales AT OBSERVATION i (oi.cpp:304-312, structure.cpp:188-214): every entry of
             // the u x u matrix, one per lane and pass
             const int nent = u * u;
@@ -1055,14 +1051,12 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 const float4 ri = L.orec[i], rp = L.orec[pcol];
                 const float hd = d_chord(ri.x, ri.y, ri.z, rp.x, rp.y, rp.z);
                 float cv = d_barnes_rho_flat(hd, rsc[i]);
-                if(anyv) { const float f = d_barnes_rho_flat((d_valid(ri.w) && d_valid(rp.w)) ? ri.w - rp.w : 0.0f, rsc[40 + i]); cv = (d_valid(ri.w) && d_valid(rp.w)) ? cv * f : cv; }
-                if(anyw) { const float li = L.olaf[i], lp = L.olaf[pcol]; const float f = d_barnes_rho_flat((d_valid(li) && d_valid(lp)) ? li - lp : 0.0f, rsc[80 + i]); cv = (d_valid(li) && d_valid(lp)) ? cv * f : cv; }
+                if(anyv) { const float f = d_barnes_rho_flat((dev_valid(ri.w) && dev_valid(rp.w)) ? ri.w - rp.w : 0.0f, rsc[40 + i]); cv = (dev_valid(ri.w) && dev_valid(rp.w)) ? cv * f : cv; }
+                if(anyw) { const float li = L.olaf[i], lp = L.olaf[pcol]; const float f = d_barnes_rho_flat((dev_valid(li) && dev_valid(lp)) ? li - lp : 0.0f, rsc[80 + i]); cv = (dev_valid(li) && dev_valid(lp)) ? cv * f : cv; }
                 cv = hd > rR[i] ? 0.0f : cv;
                 if(e0 + lane < nent) colbuf[pcol * U_MAXU + i] = cv;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             UPROF(7);   // P build
             // rows in lanes: the 32 register columns, the late columns 32 .. 39 (as they are: substituted behind the elimination), obs - background
             double row[NC];
@@ -1076,9 +1070,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
 #pragma unroll
             for(int b = 0; b < 8; ++b) lt[b] = (32 + b < u && lane < u) ? colbuf[(32 + b) * U_MAXU + lane] : 0.0f;
             const double dcol = lane < u ? (double)o1.y - (double)o1.z : 0.0;                                           // lObs - lY
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             auto rcp_nr = [](const double x) { double r = __builtin_amdgcn_rcp(x); r = r * (2.0 - x * r); r = r * (2.0 - x * r); return r; };
             {
                 int co = 0;
@@ -1095,9 +1087,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                         }
                         const double mlt = lane > j ? row[j] * rp : 0.0;     // (rows >= u hold zeros)
                         if(lane > j) row[j] = mlt;
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        wave_lds_sync();
                         const double* const q = sv + co - j;
 #pragma unroll
                         for(int p = j + 1; p < NC; ++p) row[p] = __builtin_fma(-mlt, q[p], row[p]);     // (p >= u: registers nobody reads)
@@ -1139,9 +1129,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 maxInc = wave_max(lane < c ? dpf : -INFINITY);
                 minInc = wave_min(lane < c ? dpf : INFINITY);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             UPROF(9);   // export
             // ---- per cell: t = U^-T g by sweeping the rows of U (row j updates every later entry at once; the entries of this cell's own extras
             //      ride along: they end as g_X - B_col^T t_C), then the LU of the cell's own block of the Schur complement
@@ -1219,7 +1207,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
 #define GPP_UNION_PB 1     // (measured: 3 entries side by side 7.1 k clocks per tile, one at a time 7.2 k -- the same, for eight more registers)
 #endif
         constexpr int PB = PLAIN ? GPP_UNION_PB : 1;
-        const bool hh = d_valid(st.h) && st.h != 0.0f, hv = d_valid(st.v) && st.v != 0.0f, hw = d_valid(st.w) && st.w != 0.0f;
+        const bool hh = dev_valid(st.h) && st.h != 0.0f, hv = dev_valid(st.v) && st.v != 0.0f, hw = dev_valid(st.w) && st.w != 0.0f;
         const double rh = hh ? 1.0 / (double)st.h : 0.0, rv_ = hv ? 1.0 / (double)st.v : 0.0, rw_ = hw ? 1.0 / (double)st.w : 0.0;
         for(int e0 = 0; e0 < ntri; e0 += 64 * PB) {
             int ti[PB], tp[PB];
@@ -1247,11 +1235,11 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 }
                 if(hv) {
 #pragma unroll
-                    for(int q = 0; q < PB; ++q) { const float f = d_barnes_rho_flat(ri[q].w - rp[q].w, rv_); cv[q] = (d_valid(ri[q].w) && d_valid(rp[q].w)) ? cv[q] * f : cv[q]; }
+                    for(int q = 0; q < PB; ++q) { const float f = d_barnes_rho_flat(ri[q].w - rp[q].w, rv_); cv[q] = (dev_valid(ri[q].w) && dev_valid(rp[q].w)) ? cv[q] * f : cv[q]; }
                 }
                 if(hw) {
 #pragma unroll
-                    for(int q = 0; q < PB; ++q) { const float f = d_barnes_rho_flat(li[q] - lp[q], rw_); cv[q] = (d_valid(li[q]) && d_valid(lp[q])) ? cv[q] * f : cv[q]; }
+                    for(int q = 0; q < PB; ++q) { const float f = d_barnes_rho_flat(li[q] - lp[q], rw_); cv[q] = (dev_valid(li[q]) && dev_valid(lp[q])) ? cv[q] * f : cv[q]; }
                 }
 #pragma unroll
                 for(int q = 0; q < PB; ++q) cv[q] = hd[q] > st.R ? 0.0f : cv[q];
@@ -1269,9 +1257,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         //  address addition, 122 of the elimination's ~1 200 vector instructions -- makes the scheduler keep more reads in flight: 168 registers
         //  and 20 bytes of scratch instead of 150 and none.  Left as it was.)
         if(lane < u) colL[lane] = (double)o1.y - (double)o1.z;                                             // lObs - lY
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         UPROF(7);   // P build
         // SPLIT (round 11): a row lives in TWO lanes.  Lower half -- columns 0 .. 17 -- of row i in lane i (i < u <= 40), of the obs - background
         // row in lane 63, as before; upper half -- columns 18 .. 31 -- of rows 18 .. 39 in lanes 40 .. 61 and of the obs - background row in lane
@@ -1386,9 +1372,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             }
         }
         if(u > 32 && !GPP_DBG(a, 16)) {   // Schur complement / d' of the late columns: entry - (row of B or L_C^-1 d) . (row p of B)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
 #pragma unroll
             for(int b = 0; b < 8; ++b) {
                 const int p = 32 + b;
@@ -1548,9 +1532,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         if(U_MAXU > NC && ue > NC && !GPP_DBG(a, 16)) {   // Schur complement / d' of the late columns: entry - (row of B or L_C^-1 d) . (row p of B)
             // (row p of B has just been exported: it comes back as LDS broadcasts, one read per two multiply-adds, instead of a
             //  v_readlane pair per multiply-add; columns c.. of the padded row are multiplied by zeros)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
 #pragma unroll
             for(int b = 0; b < 8; ++b) {
                 const int p = NC + b;
@@ -1636,9 +1618,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                 bad = false;
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         }   // solver
         if constexpr(PAIR) {
             if(paired) {

@@ -2,14 +2,6 @@
 #include "oi_union.h"
 
 void gpp_launch_union64(const OiArgs& a, const unsigned nblocks, const bool plain, const bool list, hipStream_t stream) {
-    constexpr int T = 64 * UnionCfg<64>::WPB;
-    const dim3 grid(nblocks), block(T);
-    if(plain) {
-        if(list) hipLaunchKernelGGL((k_oi_union<true, true, 64>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k_oi_union<true, false, 64>), grid, block, 0, stream, a);
-    }
-    else {
-        if(list) hipLaunchKernelGGL((k_oi_union<false, true, 64>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((k_oi_union<false, false, 64>), grid, block, 0, stream, a);
-    }
+    static constexpr void (*forms[2][2])(OiArgs) = {{k_oi_union<true, true, 64>, k_oi_union<true, false, 64>}, {k_oi_union<false, true, 64>, k_oi_union<false, false, 64>}};   // forms[not plain][not list]
+    gpp::launch_on(stream, forms[plain ? 0 : 1][list ? 0 : 1], nblocks, 64 * UnionCfg<64>::WPB, 0, a);
 }

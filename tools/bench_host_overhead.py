@@ -1,4 +1,4 @@
-"""Host overhead of an entry point: the per-call wall time of three tiny device-resident calls where everything is overhead, this tree against
+"""Host overhead of an entry point: the per-call wall time of six tiny device-resident calls where everything is overhead, this tree against
 a checkout of the parent commit (the launch helper adds one hipGetLastError per launch on the good path).
 
     python tools/bench_host_overhead.py --parent-tree DIR [--rounds 5] [--calls 2000] [--jsonl FILE]
@@ -6,6 +6,9 @@ a checkout of the parent commit (the launch helper adds one hipGe
   calc_crps      64 rows x 8 members       (one launch)
   neighbourhood  Mean, halfwidth 1, 16 x 16 (one launch)
   fill_missing   16 x 16                    (five launches)
+  oi             optimal_interpolation, 16 x 16 grid, 8 observations, max_points 4 (the OiCall path: pack, tile kernel, list passes)
+  oi_ensi        optimal_interpolation_ensi on the same geometry, 4 members         (the EnsiCall path: scan, pair, members)
+  oi_gain_apply  OiGain.apply with one field, the gain built once on that geometry  (two launches)
 
 Each is timed twice: `abi` is the extern "C" entry called through ctypes with device pointers and a preallocated result, `api` the Python wrapper a
 user calls.  A call ends in the library's own stream synchronise, so the host clock around it is the whole call.  A measurement is a warm-up of 200
@@ -28,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def measure(tree, calls):
     sys.path.insert(0, os.path.abspath(tree))
     import ctypes as C
+    import numpy as np
     import torch
     import gridpp_amd as gridpp
     from gridpp_amd import _capi
@@ -41,16 +45,33 @@ def measure(tree, calls):
     holes = plane.clone()
     holes[3:6, 4:9] = float("nan")
     o64, o256 = torch.empty(64, device=dev), torch.empty((16, 16), device=dev)
+    # the OI family: a 16 x 16 grid over one degree, 8 observations inside it, every cell within reach of some of them
+    lats, lons = np.meshgrid(np.linspace(60.0, 61.0, 16), np.linspace(10.0, 11.0, 16), indexing="ij")
+    rng = np.random.default_rng(11)
+    grid, points = gridpp.Grid(lats, lons), gridpp.Points(rng.uniform(60.0, 61.0, 8), rng.uniform(10.0, 11.0, 8))
+    structure = gridpp.BarnesStructure(50000)
+    pobs, pratios, pbg = (torch.rand((8,), generator=gen, device=dev) for _ in range(3))
+    psigmas = pratios + 0.5
+    cube, pcube = torch.rand((16, 16, 4), generator=gen, device=dev), torch.rand((8, 4), generator=gen, device=dev)
+    ocube = torch.empty((16, 16, 4), device=dev)
+    gain = gridpp.optimal_interpolation_gain(grid, points, pratios.cpu().numpy(), structure, 4)
     lib = _capi.lib()
     p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.byref(structure._s)
     DEVICE = 1   # GPP_MEM_DEVICE
     cases = {
         "calc_crps_abi": lambda: lib.gpp_calc_crps(p(ens), p(ref), 64, 8, p(o64), DEVICE),
         "neighbourhood_abi": lambda: lib.gpp_neighbourhood(p(plane), 16, 16, 1, 0, 1, gridpp.Mean, p(o256), DEVICE),
         "fill_missing_abi": lambda: lib.gpp_fill_missing(p(holes), 16, 16, p(o256), DEVICE),
+        "oi_abi": lambda: lib.gpp_optimal_interpolation_full(grid._h, p(plane), None, points._h, p(pobs), p(pratios), p(pbg), None, st, 4, 1, p(o256), None, DEVICE),
+        "oi_ensi_abi": lambda: lib.gpp_optimal_interpolation_ensi(grid._h, p(cube), 4, points._h, p(pobs), p(psigmas), p(pcube), st, 4, 1, p(ocube), DEVICE),
+        "oi_gain_apply_abi": lambda: lib.gpp_oi_gain_apply(gain._h, p(plane), 1, p(pobs), 0, p(pbg), 1, p(o256), DEVICE),
         "calc_crps_api": lambda: gridpp.calc_crps(ens, ref),
         "neighbourhood_api": lambda: gridpp.neighbourhood(plane, 1, gridpp.Mean),
         "fill_missing_api": lambda: gridpp.fill_missing(holes),
+        "oi_api": lambda: gridpp.optimal_interpolation(grid, plane, points, pobs, pratios, pbg, structure, 4),
+        "oi_ensi_api": lambda: gridpp.optimal_interpolation_ensi(grid, cube, points, pobs, psigmas, pcube, structure, 4),
+        "oi_gain_apply_api": lambda: gain.apply(plane, pobs, pbg),
     }
     out = {}
     for name, fn in cases.items():
