@@ -2224,7 +2224,7 @@ struct OiCall {
 #ifdef GPP_UNION_STATS
         fprintf(stderr, "[gpp] union: fallback reasons: slots %llu, union>40 %llu, extras>12 %llu, layout %llu, per-cell extras>6 %llu; per tile: insertions %.1f, evictions %.1f, candidates evaluated outside the bulk disc %.1f, records loaded in phase 2 %.1f\n",
                                 counters[4], counters[5], counters[6], counters[7], counters[8], counters[9] / (double)a.ntiles, counters[10] / (double)a.ntiles, counters[11] / (double)a.ntiles, counters[12] / (double)a.ntiles);
-        fprintf(stderr, "[gpp] union: tiles whose slot-ownership masks disagree with the slots: %llu\n", counters[13]);
+        fprintf(stderr, "[gpp] union: tiles whose slot-ownership masks disagree with the slots: %llu; tiles with a NaN in a slot: %llu\n", counters[13], counters[14]);
 #endif
         if(timing_env("GPP_SCAN_STATS")) { fprintf(stderr, "[gpp] wave-level insertions per tile histogram:"); for(int i = 0; i < 70; i++) fprintf(stderr, " %d:%llu", i, counters[4 + i]); fprintf(stderr, "\n"); }
     }

@@ -1,6 +1,7 @@
 // Shared by oi.hip and ensi.hip: observation index, Barnes device functions, the per-tile candidate scan.
 #pragma once
 #include "common.h"
+#include "oi_small.h"
 #include <algorithm>
 
 #pragma clang fp contract(off)
@@ -159,6 +160,8 @@ __device__ __forceinline__ double d_fma_sc(double a, double c, double b) {   // 
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(a), "s"(c), "v"(b));
     return o;
 }
+// (d_min_pos / d_min3_pos, the float32 minimum of operands that hold no NaN and no sign bit, and the generator of the
+//  triangle-index table live in oi_small.h, which the host compiler can include too)
 __device__ __forceinline__ unsigned d_and_or_sc(unsigned m, unsigned c, unsigned b) {   // (m & c) | b
     unsigned o;
     asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(o) : "v"(m), "s"(c), "v"(b));
@@ -261,6 +264,21 @@ __device__ __forceinline__ float d_sqrt_cr(const float x) {
     const float rm = __builtin_fmaf(-sm, s, x), rp = __builtin_fmaf(-sp, s, x);
     float r = (0.0f >= rm) ? sm : s;
     r = (0.0f < rp) ? sp : r;
+    return r;
+}
+// The same for two arguments at once, on a two-element vector (round 12): element q is d_sqrt_cr(x[q]), operation for operation; written on
+// the vector so that the two residual multiply-adds pack (v_pk_fma_f32) without moving halves between register pairs.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 d_sqrt_cr2(const f32x2 x) {
+    f32x2 s;
+    s.x = __builtin_amdgcn_sqrtf(x.x); s.y = __builtin_amdgcn_sqrtf(x.y);
+    f32x2 sm, sp;
+    sm.x = __int_as_float(__float_as_int(s.x) - 1); sm.y = __int_as_float(__float_as_int(s.y) - 1);
+    sp.x = __int_as_float(__float_as_int(s.x) + 1); sp.y = __int_as_float(__float_as_int(s.y) + 1);
+    const f32x2 rm = __builtin_elementwise_fma(-sm, s, x), rp = __builtin_elementwise_fma(-sp, s, x);
+    f32x2 r;
+    r.x = (0.0f >= rm.x) ? sm.x : s.x; r.y = (0.0f >= rm.y) ? sm.y : s.y;
+    r.x = (0.0f < rp.x) ? sp.x : r.x; r.y = (0.0f < rp.y) ? sp.y : r.y;
     return r;
 }
 // v_sqrt_f32 as it is (within one ulp): for the quantities that only bound the work (tile radii, ring limits, row extents -- all padded)

@@ -97,6 +97,17 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long mask, int m) {
 #define UPROF(i) do { } while(0)
 #endif
 
+// Round 12 (profiles/oi_union_selection_ab.txt), each with its own switch so that an item can be built against the same tree without it:
+#ifndef GPP_UNION_MINNN
+#define GPP_UNION_MINNN 1    // worst_slot: minima without NaN handling (d_min_pos, d_min3_pos) instead of fminf
+#endif
+#ifndef GPP_UNION_CHORD2
+#define GPP_UNION_CHORD2 1   // bulk evaluations: the two side-by-side chords on two-element vectors, lane half q = candidate q (see chord_n)
+#endif
+#ifndef GPP_UNION_TRITAB
+#define GPP_UNION_TRITAB 1   // P build: (row, column) of a triangle entry from c_tri_tab instead of a square root and two corrections
+#endif
+static __device__ const TriTab c_tri_tab = make_tri_tab();   // (oi_small.h; defined here and not there: oi_common.h also goes into ensi.hip, which has no use for it)
 // Two sizes of the kernel.  NC = 32: max_points <= 32, 32 register columns (+ 8 late columns kept in LDS), four waves per
 // workgroup.  NC = 64: max_points 33..62, 64 register columns, two waves per workgroup (46 KB of LDS) at one wave per SIMD.
 template <int NC> struct UnionCfg;
@@ -318,6 +329,16 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
     // minima of groups of eight slots, then the eight values of the group that holds the minimum, read again from LDS (its index is
     // the lane's own): ~70 instructions.  One flat pass (compare, select, count for each of the 40 slots, each triple with a wait
     // state behind the compare) was 180, and a tile runs this 5.5 times (once behind the bulk disc, once per eviction).
+    //
+    // Round 12.  The minima are integer minima of the bit patterns (d_min3_pos, d_min_pos in oi_small.h): a slot holds a positive number
+    // or +inf, never a NaN -- every store is `cond ? rho : INFINITY` with cond implying rho > 0 (want, ok) or a certified item (rho a normal
+    // positive number) -- so fminf's quieting of every loaded operand (30 v_max_f32 v, v, v per call) changed no bit.  (GPP_UNION_STATS
+    // counts the tiles that hold a NaN slot at classification in counters[14].)
+    // Also built in round 12 and taken out: the group minima kept in registers between the calls (a store into the wave-uniform slot s
+    // lowers gm[s >> 3], an eviction re-reads only the group of the slot the lane cleared).  16 LDS reads fewer per eviction, but writing
+    // one of five registers chosen at run time is a compare and a select for each of them, twice per eviction: with the four-instruction
+    // group minimum above the sum of the instruction counts went UP by 21 per tile (vector + 40, scalar + 25, LDS - 45) for 0.03 ms,
+    // inside the spread -- profiles/oi_union_selection_ab.txt.
     auto worst_slot = [&](float& r0, int& s0, bool& multi) {
         constexpr int NG = U_WCAP / 8;
         float gm[NG];
@@ -326,11 +347,24 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             float v[8];
 #pragma unroll
             for(int j = 0; j < 8; ++j) v[j] = L.rho[8 * g + j][lane];
+#if GPP_UNION_MINNN
+            gm[g] = d_min_pos(d_min3_pos(v[3], v[4], v[5]), d_min3_pos(v[6], v[7], d_min3_pos(v[0], v[1], v[2])));
+#else
             gm[g] = fminf(fminf(fminf(v[0], v[1]), fminf(v[2], v[3])), fminf(fminf(v[4], v[5]), fminf(v[6], v[7])));
+#endif
         }
         r0 = gm[0];
+#if GPP_UNION_MINNN
+        {
+            int g = 1;
+#pragma unroll
+            for(; g + 1 < NG; g += 2) r0 = d_min3_pos(r0, gm[g], gm[g + 1]);
+            if(g < NG) r0 = d_min_pos(r0, gm[g]);
+        }
+#else
 #pragma unroll
         for(int g = 1; g < NG; ++g) r0 = fminf(r0, gm[g]);
+#endif
         int gs = 0, ng = 0;
 #pragma unroll
         for(int g = 0; g < NG; ++g) { const bool eq = gm[g] == r0; gs = eq ? g : gs; ng += eq ? 1 : 0; }
@@ -381,6 +415,18 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         // once every cell of the wave has its max_points -- inside the largest budget with the elevation / laf distance to the tile's extent added
         const bool eprune = PLAIN && (kv2 != 0.0f || kw2 != 0.0f);   // (wave-uniform; flat ground pays nothing for the extent)
         auto wave_bud2 = [&]() { return eprune ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wave_max(bud2)))) : INFINITY; };
+        // Round 12, site by site, why the other fminf / fmaxf of union_item were NOT converted like worst_slot's (d_min_pos needs operands without a
+        // NaN AND without a sign bit; the bare float instruction as an inline statement lost its A/B, see oi_small.h):
+        //   keep (here):  dz and dl take a record's / the tile's elevation and land fraction, NaN where there is none -- fmaxf DROPS that NaN
+        //                 ("no distance"): dropping it is the point.  sd's operand is signed (sqrt(pd) - rad < 0 inside the tile's radius).
+        //   wave_lim2:    holds no fminf / fmaxf of its own -- wave_max is the DPP reduction (v_max_f32_dpp drops a NaN by itself, nothing is
+        //                 quieted in front of it), and thr2 is never a NaN (thr2_R, -1, or fminf(thr2_R, bud2), which drops the NaN bud2 of an
+        //                 invalid h: again the point of that fminf).
+        //   far:          its operands can be NaN (inf - inf when no lane of the wave is active) and the test is written so that a NaN fails the
+        //                 certificate; once per record lane and item.  Stays.
+        //   maxInc / minInc (the clamp, three sites below): de = obs - background is signed, so the integer form does not apply; whether it can
+        //                 be a NaN was not analysed (the host drops stations with an invalid observation, but the difference is taken here).
+        //                 At most twelve extras per cell and only without extrapolation.  Stays.
         auto keep = [&](const float pd, const float4& rec, const float2& met, const float lim2, const float B2) {
             bool k = pd <= lim2;
             if(eprune && B2 < INFINITY) {
@@ -442,18 +488,42 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
                           //  with three waves per SIMD the scan is bound by instruction issue, not by the chains -- and costs 24 registers)
 #endif
         constexpr int EV = GPP_UNION_EV;
+        // d2 and the chord of EV candidates to this cell.  Round 12, EV = 2: on explicit two-element vectors, element q = candidate q from the
+        // subtraction to the residuals of the root -- left to itself the compiler packs DIFFERENT coordinates of the two candidates into one
+        // register pair and moves halves around before the sum of squares (three v_mov_b32 per pair of candidates).  The same float32
+        // operations in the same order (no contraction): d2 and dist keep their bits.
+        auto chord_n = [&](const float4& rec, const int (&cc)[EV], float (&d2)[EV], float (&dist)[EV]) {
+            if constexpr(EV == 2 && GPP_UNION_CHORD2 != 0) {
+                f32x2 ox, oy, oz;
+                ox.x = readlane_f(rec.x, cc[0]); ox.y = readlane_f(rec.x, cc[EV - 1]);
+                oy.x = readlane_f(rec.y, cc[0]); oy.y = readlane_f(rec.y, cc[EV - 1]);
+                oz.x = readlane_f(rec.z, cc[0]); oz.y = readlane_f(rec.z, cc[EV - 1]);
+                const f32x2 dx = ox - gx, dy = oy - gy, dz = oz - gz;
+                f32x2 q2 = dx * dx + dy * dy;
+                q2 = q2 + dz * dz;
+                const f32x2 r = d_sqrt_cr2(q2);
+                d2[0] = q2.x; d2[EV - 1] = q2.y; dist[0] = r.x; dist[EV - 1] = r.y;
+            }
+            else {
+#pragma unroll
+                for(int q = 0; q < EV; ++q) {
+                    const float ox = readlane_f(rec.x, cc[q]), oy = readlane_f(rec.y, cc[q]), oz = readlane_f(rec.z, cc[q]);
+                    const float dx = ox - gx, dy = oy - gy, dz = oz - gz;
+                    float t = dx * dx + dy * dy;
+                    t = t + dz * dz;
+                    d2[q] = t;
+                    dist[q] = d_sqrt_cr(t);
+                }
+            }
+        };
         auto eval_n = [&](const float4& rec, const float2& met, const int (&cc)[EV], float (&rho)[EV]) {
-            float dist[EV];
+            float dist[EV], d2[EV];
             bool ok[EV];
             unsigned long long anynear = 0ull;   // (wave-uniform: the lanes' compare masks, combined and tested by scalar instructions)
+            chord_n(rec, cc, d2, dist);
 #pragma unroll
             for(int q = 0; q < EV; ++q) {
-                const float ox = readlane_f(rec.x, cc[q]), oy = readlane_f(rec.y, cc[q]), oz = readlane_f(rec.z, cc[q]);
-                const float dx = ox - gx, dy = oy - gy, dz = oz - gz;
-                float d2 = dx * dx + dy * dy;
-                d2 = d2 + dz * dz;
-                dist[q] = d_sqrt_cr(d2);
-                ok[q] = d2 <= thr2 && dist[q] <= R;
+                ok[q] = d2[q] <= thr2 && dist[q] <= R;
                 anynear |= wave_ballot(ok[q]) & wave_ballot(dist[q] > near_r);
             }
             if(anynear != 0ull) {   // (see eval: the strictly-inside box of the radius query, only for candidates within ulps of R)
@@ -494,15 +564,8 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         // bulk candidate -- ok is `active`, no candidate is near R, rho is a normal number -- so only the arithmetic the value needs is left.
         // The same helpers in the same order: every rho keeps its bits.
         auto eval_cert_n = [&](const float4& rec, const int (&cc)[EV], float (&rho)[EV]) {
-            float dist[EV];
-#pragma unroll
-            for(int q = 0; q < EV; ++q) {
-                const float ox = readlane_f(rec.x, cc[q]), oy = readlane_f(rec.y, cc[q]), oz = readlane_f(rec.z, cc[q]);
-                const float dx = ox - gx, dy = oy - gy, dz = oz - gz;
-                float d2 = dx * dx + dy * dy;
-                d2 = d2 + dz * dz;
-                dist[q] = d_sqrt_cr(d2);
-            }
+            float dist[EV], d2[EV];
+            chord_n(rec, cc, d2, dist);
 #pragma unroll
             for(int q = 0; q < EV; ++q) rho[q] = 1.0f;
             if(hh) {
@@ -872,6 +935,9 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             unsigned long long held = 0ull;
             for(int w = 0; w < U_WCAP; ++w) held |= (L.rho[w][lane] < INFINITY ? 1ull : 0ull) << w;
             if(wave_ballot(held != mine) != 0ull && lane == 0) atomicAdd(&a.counters[13], 1ull);
+            bool nan_slot = false;   // (counters[14]: tiles with a NaN in a slot -- the precondition of d_min_pos in worst_slot)
+            for(int w = 0; w < U_WCAP; ++w) { const float v = L.rho[w][lane]; nan_slot = nan_slot || v != v; }
+            if(wave_ballot(nan_slot) != 0ull && lane == 0) atomicAdd(&a.counters[14], 1ull);
         }
     }
     // row i of the shared factorisation = lane i: the slot of THIS wave that holds its observation (-1: no cell of this tile selected it;
@@ -976,6 +1042,26 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         if(solver && lane < u) {
             o0 = sa.pgeo[mypos];
             o1 = a.saux[mypos];
+        }
+        // (PLAIN P build: PB entries per lane and pass, their chains side by side -- chord, correctly rounded root and quotient, table exp: ~35
+        //  dependent operations each; the nine passes of a 33-row union one after the other were a wave waiting for itself, see eval_n)
+#ifndef GPP_UNION_PB
+#define GPP_UNION_PB 1     // (measured: 3 entries side by side 7.1 k clocks per tile, one at a time 7.2 k -- the same, for eight more registers)
+#endif
+        constexpr int PB = PLAIN ? GPP_UNION_PB : 1;
+        // Round 12: (row, column) of the triangle entries a lane builds come from c_tri_tab, one 16-bit load per entry, issued one pass
+        // ahead -- the first ones here, beside the record loads, so that no chain of the P build waits for memory.  (The number of passes
+        // is the union's: all loads in front of the first chain would need every pass unrolled.)  tri_next stays live across the gf build
+        // below, where the allocation peaks: checked in the build remarks -- 143 VGPRs for the first pass with and without it, no kernel
+        // of the three units moved (profiles/oi_union_selection_build_remarks.txt); nothing else guards it.
+        constexpr bool TRITAB = GPP_UNION_TRITAB != 0 && !SP;
+        static_assert(U_MAXU * (U_MAXU + 1) / 2 <= TRI_N, "the triangle table holds the largest union");
+        unsigned tri_next[PB] = {};
+        if constexpr(TRITAB) {
+            if(solver) {
+#pragma unroll
+                for(int q = 0; q < PB; ++q) tri_next[q] = c_tri_tab.v[min(64 * q + lane, u * (u + 1) / 2 - 1)];
+            }
         }
         const float dpf = (float)((double)o1.y - (double)o1.z);   // obs - background at the observation (oi.cpp:293)
         // this cell's rho for every row of the union (lG, oi.cpp:296); afterwards the rho slots are dead and the
@@ -1201,12 +1287,6 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         if(lane < u) { L.orec[lane] = o0; L.olaf[lane] = o1.x; }
         float* colbuf = reinterpret_cast<float*>(L.f.solve);   // [u][U_MAXU]
         const int ntri = u * (u + 1) / 2;
-        // (PLAIN: PB entries per lane and pass, their chains side by side -- chord, correctly rounded root and quotient, table exp: ~35 dependent
-        //  operations each; the nine passes of a 33-row union one after the other were a wave waiting for itself, see eval_n)
-#ifndef GPP_UNION_PB
-#define GPP_UNION_PB 1     // (measured: 3 entries side by side 7.1 k clocks per tile, one at a time 7.2 k -- the same, for eight more registers)
-#endif
-        constexpr int PB = PLAIN ? GPP_UNION_PB : 1;
         const bool hh = dev_valid(st.h) && st.h != 0.0f, hv = dev_valid(st.v) && st.v != 0.0f, hw = dev_valid(st.w) && st.w != 0.0f;
         const double rh = hh ? 1.0 / (double)st.h : 0.0, rv_ = hv ? 1.0 / (double)st.v : 0.0, rw_ = hw ? 1.0 / (double)st.w : 0.0;
         for(int e0 = 0; e0 < ntri; e0 += 64 * PB) {
@@ -1216,10 +1296,16 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
 #pragma unroll
             for(int q = 0; q < PB; ++q) {
                 const int e = min(e0 + 64 * q + lane, ntri - 1);
+                if constexpr(TRITAB) {
+                    ti[q] = (int)(tri_next[q] >> 8); tp[q] = (int)(tri_next[q] & 255u);
+                    tri_next[q] = c_tri_tab.v[min(e + 64 * PB, ntri - 1)];   // the next pass's (the last pass reads the tail entry again)
+                }
+                else {
                 int i = (int)((d_sqrt_raw(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);   // (the two tests below put an estimate one off right)
                 if(i * (i + 1) / 2 > e) i--;
                 if((i + 1) * (i + 2) / 2 <= e) i++;
                 ti[q] = i; tp[q] = e - i * (i + 1) / 2;
+                }
                 ri[q] = L.orec[ti[q]]; rp[q] = L.orec[tp[q]];
                 li[q] = L.olaf[ti[q]]; lp[q] = L.olaf[tp[q]];
             }
