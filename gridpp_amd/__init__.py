@@ -935,7 +935,8 @@ def oi_last_stats():
     s = _capi.gpp_oi_stats()
     check(lib().gpp_oi_last_stats(C.byref(s)))
     return dict(cells=s.cells, cells_updated=s.cells_updated, solves=s.solves, fallback_tiles=s.fallback_tiles, kernel_ms=s.kernel_ms,
-                union_kernel_ms=s.union_kernel_ms, fallback_subtiles=s.fallback_subtiles, big_cells=s.big_cells, bulk_certified=s.bulk_certified)
+                union_kernel_ms=s.union_kernel_ms, fallback_subtiles=s.fallback_subtiles, big_cells=s.big_cells, bulk_certified=s.bulk_certified,
+                pair_window=s.pair_window, pair_table_bytes=s.pair_table_bytes, pair_fallback_items=s.pair_fallback_items, pair_table_build_ms=s.pair_table_build_ms)
 
 
 def obs_index_axes(points):

@@ -33,7 +33,8 @@ class gpp_structure(C.Structure):
 class gpp_oi_stats(C.Structure):
     _fields_ = [("cells", C.c_longlong), ("cells_updated", C.c_longlong), ("solves", C.c_longlong),
                 ("fallback_tiles", C.c_longlong), ("kernel_ms", C.c_float), ("union_kernel_ms", C.c_float), ("fallback_subtiles", C.c_longlong), ("big_cells", C.c_longlong),
-                ("bulk_certified", C.c_longlong)]
+                ("bulk_certified", C.c_longlong), ("pair_window", C.c_int), ("pair_table_bytes", C.c_longlong),
+                ("pair_fallback_items", C.c_longlong), ("pair_table_build_ms", C.c_float)]
 
 
 class gpp_ensi_stats(C.Structure):

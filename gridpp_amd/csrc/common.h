@@ -273,6 +273,7 @@ struct gpp_points {
     bool host_fields = true;
     void ensure_host_fields();
     int tile_wshift = -1;            // gpp_tile_wshift's answer for this grid (computed once)
+    float tile_diam[7] = {-1, -1, -1, -1, -1, -1, -1};   // diagonal of a tile of each shape in the library's coordinates (oi.hip: pair_window_for; computed once)
     float lat_at(int i);             // single elements without materialising the vectors
     float lon_at(int i);
     bool elev_uniform = true, laf_uniform = true;   // every point has the same elevation / laf (or none has one)

@@ -26,6 +26,7 @@ void gpp_launch_union48(const OiArgs& a, unsigned nblocks, bool plain, bool list
 #include <cfloat>
 #include <algorithm>
 #include <memory>
+#include <chrono>
 
 #pragma clang fp contract(off)
 
@@ -1444,6 +1445,118 @@ void gpp_scan_geometry(ScanArgs& s, const gpp_obs_index* ix, const int S, const 
     s.K = kk;
 }
 
+// ---- the pair table of the observation index (oi_pair_table.h) ---------------------------------------------------------------------------
+// row descriptors and bin row of every sorted position.  bin_base[bin]: offset of the values of the bin's first observation (host prefix sum
+// over the bins); every observation of a bin has the same rows, hence the same number of values.
+__global__ void k_pair_desc(const int S, const int nbx, const int nby, const int W, const int* __restrict__ bin_start, const int* __restrict__ bin_base,
+                            int4* __restrict__ desc, int* __restrict__ brow) {
+    const int nbins = nbx * nby;
+    for(int p = blockIdx.x * blockDim.x + threadIdx.x; p < S; p += gridDim.x * blockDim.x) {
+        int lo = 0, hi = nbins - 1;      // the bin of sorted position p: the first one whose end lies behind p
+        while(lo < hi) { const int mid = (lo + hi) >> 1; if(bin_start[mid + 1] > p) hi = mid; else lo = mid + 1; }
+        const int by = lo / nbx, bx = lo - by * nbx;
+        const int xa = max(bx - W, 0), xb = min(bx + W, nbx - 1);
+        int per = 0;
+        for(int dy = -W; dy <= W; ++dy) { const int r = by + dy; if(r >= 0 && r < nby) per += bin_start[r * nbx + xb + 1] - bin_start[r * nbx + xa]; }
+        int off = bin_base[lo] + (p - bin_start[lo]) * per;
+        for(int dy = -W; dy <= W; ++dy) {
+            const int r = by + dy;
+            int first = 0, len = 0;
+            if(r >= 0 && r < nby) { first = bin_start[r * nbx + xa]; len = bin_start[r * nbx + xb + 1] - first; }
+            desc[(size_t)p * (2 * W + 1) + (dy + W)] = make_int4(first, len, off, 0);
+            off += len;
+        }
+        brow[p] = by;
+    }
+}
+// the values: one wave per observation a, its lanes over the observations of each row -- d_barnes_corr_flat, the helper of the P build itself
+__global__ void k_pair_values(const PairTabArgs t, const int S, const float4* __restrict__ sgeo, const float2* __restrict__ smeta,
+                              const float h, const float v, const float w, const float R, float* __restrict__ vals) {
+    d_exptab_fill();
+    __syncthreads();
+    const int lane = threadIdx.x & 63, nrow = 2 * t.W + 1;
+    for(int a = blockIdx.x * 4 + (threadIdx.x >> 6); a < S; a += gridDim.x * 4) {
+        const float4 ga = sgeo[a];
+        const float la = smeta[a].x;
+        for(int j = 0; j < nrow; ++j) {
+            const int4 d = t.desc[(size_t)a * nrow + j];
+            for(int k = lane; k < d.y; k += 64) {
+                const float4 gb = sgeo[d.x + k];
+                const float lb = smeta[d.x + k].x;
+                vals[(size_t)d.z + k] = d_barnes_corr_flat(ga.x, ga.y, ga.z, ga.w, la, gb.x, gb.y, gb.z, gb.w, lb, h, v, w, R);
+            }
+        }
+    }
+}
+// The table of `ix` for the scalar Barnes structure `st` and a window of W_asked bins: the cached one when its key matches, else built here, on
+// the library stream (which has run it when this returns: the list passes of a call may read it from another stream).  The window shrinks until
+// the table fits GPP_PAIR_TABLE_CAP; no window >= 1 that fits, or a failed allocation, leaves W == 0 -- callers then evaluate, it is no error.
+// build_ms: the time of a build (0 when the cached table was used).
+static const gpp_pair_table& pair_table_for(gpp_obs_index* ix, const DevStructure& st, const int W_asked, float* build_ms) {
+    gpp_pair_table& t = ix->pair;
+    *build_ms = 0.0f;
+    const float key[4] = {st.h, st.v, st.w, st.R}, have[4] = {t.h, t.v, t.w, t.R};
+    if(t.built && t.kh == st.kh && t.kv == st.kv && t.kw == st.kw && t.W_asked == W_asked && memcmp(key, have, sizeof(key)) == 0) return t;
+    // (another key: whatever still reads the old table -- a deferred call's kernels on any stream -- finishes first)
+    if(t.built) GPP_HIP(hipDeviceSynchronize());
+    const auto t0 = std::chrono::steady_clock::now();
+    t.built = true; t.kh = st.kh; t.kv = st.kv; t.kw = st.kw; t.W_asked = W_asked; t.h = st.h; t.v = st.v; t.w = st.w; t.R = st.R;
+    t.W = 0; t.bytes = 0; t.ndesc = 0; t.nvals = 0;
+    const int S = ix->S, nbx = ix->nbx, nby = ix->nby, nbins = nbx * nby;
+    int W = std::min(W_asked, std::max(nbx, nby));   // (a wider window holds nothing more)
+    if(S <= 0 || W < 1 || (size_t)S * (sizeof(float) + 3 * sizeof(int4) + sizeof(int)) > GPP_PAIR_TABLE_CAP) return t;
+    std::vector<int> bs((size_t)nbins + 1), base((size_t)nbins);
+    GPP_HIP(hipMemcpyAsync(bs.data(), ix->d_bin_start.p, bs.size() * sizeof(int), hipMemcpyDeviceToHost, stream()));
+    GPP_HIP(hipStreamSynchronize(stream()));
+    size_t nvals = 0;
+    for(; W >= 1; --W) {
+        nvals = 0;
+        for(int by = 0; by < nby; ++by)
+            for(int bx = 0; bx < nbx; ++bx) {
+                const int bin = by * nbx + bx, n = bs[bin + 1] - bs[bin];
+                base[bin] = (int)std::min<size_t>(nvals, 0x7fffffff);
+                if(n == 0) continue;
+                const int xa = std::max(bx - W, 0), xb = std::min(bx + W, nbx - 1);
+                size_t per = 0;
+                for(int r = std::max(by - W, 0); r <= std::min(by + W, nby - 1); ++r) per += (size_t)(bs[r * nbx + xb + 1] - bs[r * nbx + xa]);
+                nvals += (size_t)n * per;
+            }
+        if(nvals * sizeof(float) + (size_t)S * (2 * W + 1) * sizeof(int4) + (size_t)S * sizeof(int) <= GPP_PAIR_TABLE_CAP) break;
+    }
+    if(W < 1) return t;
+    const size_t ndesc = (size_t)S * (2 * W + 1);
+    try {
+        t.d_desc.get(ndesc); t.d_vals.get(nvals); t.d_brow.get(S);
+        t.d_bin_base.upload(base.data(), base.size());
+    }
+    catch(const gpp::Error&) {   // no room for it: no table
+        (void)hipGetLastError();
+        t.d_desc.release(); t.d_vals.release(); t.d_brow.release(); t.d_bin_base.release();
+        return t;
+    }
+    t.W = W; t.ndesc = (unsigned)ndesc; t.nvals = (unsigned)nvals;
+    t.bytes = nvals * sizeof(float) + ndesc * sizeof(int4) + (size_t)S * sizeof(int);
+    launch(k_pair_desc, grid_capped(blocks_of(S), 4096), 256, 0, S, nbx, nby, W, (const int*)ix->d_bin_start.p, (const int*)t.d_bin_base.p, t.d_desc.p, t.d_brow.p);
+    launch(k_pair_values, grid_capped(blocks_of(S, 4), 16384), 256, 0, t.args(), S, (const float4*)ix->d_sgeo.p, (const float2*)ix->d_smeta.p, st.h, st.v, st.w, st.R, t.d_vals.p);
+    GPP_HIP(hipStreamSynchronize(stream()));
+    *build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return t;
+}
+// the window a call needs: two members of one union are each within the selection radius (gpp_scan_geometry's estimate: 1.5 r_k) of one tile
+static int pair_window_for(const ScanArgs& s, gpp_points* g, const int wshift) {
+    if(g->ny < 2 || g->nx < 2) return 0;
+    if(g->tile_diam[wshift] < 0.0f) {   // metric size of a cell from the corner points, as gpp_tile_wshift takes it
+        const float la[3] = {g->lat_at(0), g->lat_at(1), g->lat_at(g->nx)}, lo[3] = {g->lon_at(0), g->lon_at(1), g->lon_at(g->nx)};
+        float x[3], y[3], z[3];
+        if(gpp_convert_coordinates(la, lo, 3, g->type, x, y, z) != GPP_OK) return 0;
+        auto dist = [&](int i) { return std::sqrt((double)(x[i] - x[0]) * (x[i] - x[0]) + (double)(y[i] - y[0]) * (y[i] - y[0]) + (double)(z[i] - z[0]) * (z[i] - z[0])); };
+        const double ex = (1 << wshift) * dist(1), ey = (64 >> wshift) * dist(2);
+        g->tile_diam[wshift] = (float)std::sqrt(ex * ex + ey * ey);
+    }
+    const double w = (2.0 * (double)s.ring_r0 + (double)g->tile_diam[wshift]) * (double)s.inv_s;
+    return w < 1e6 ? (int)std::ceil(w) : 0;   // (also NaN: no table)
+}
+
 extern "C" int gpp_field_create(gpp_points* grid, const float* h, const float* v, const float* w, int kind, float min_rho, gpp_field** out) {
     GPP_TRY
     if(!grid || !out || !h || !v || !w) invalid("NULL argument");
@@ -1854,6 +1967,19 @@ struct OiCall {
             if(async_slot < 0) steady = false;
         }
     }
+    // Round 13: the PLAIN forms of k_oi_union (scalar Barnes structure, symmetric P) take the pair correlations of P from the table kept with the
+    // observation index; it is built here, ahead of the first pass, when the index holds none for this structure and window.  Only on 2-D tiled
+    // grids (the window comes from the tile's diagonal).  GPP_OI_NO_PAIR_TABLE: none is built or used; GPP_OI_PAIR_WINDOW=n: a window of n bins.
+    void bind_pair_table() {
+        a.pt = PairTabArgs();
+        if(!use_union || use_lu || !plain || spatial || !a.tiled2d || path_env("GPP_OI_NO_PAIR_TABLE")) return;
+        const int W = path_env("GPP_OI_PAIR_WINDOW") ? atoi(path_env("GPP_OI_PAIR_WINDOW")) : pair_window_for(a.s, bgrid, a.wshift);
+        if(W < 1) return;
+        const gpp_pair_table& t = pair_table_for(ix, a.s.st, W, &g_stats.pair_table_build_ms);
+        if(t.W < 1) return;
+        a.pt = t.args();
+        g_stats.pair_window = t.W; g_stats.pair_table_bytes = (long long)t.bytes;
+    }
     // The workspace of this call -- the slot's observation block and status block -- is bound HERE, behind the decision whether the call is deferred:
     // a call that is not completes the deferred calls of the thread first, and one of those may need its synchronous re-run, i.e. a nested
     // oi_full_impl that flips the slot, reallocates the slot buffers for its own observation count and overwrites the statistics.
@@ -1864,6 +1990,7 @@ struct OiCall {
             g_stats = gpp_oi_stats();      // (a re-run inside the drain left its own)
             g_stats.cells = C;
         }
+        bind_pair_table();
         wsl = ws.slot ^= 1;
         pgeo_b = &ws.pgeo_s[wsl]; oaux_b = &ws.oaux_s[wsl]; saux_b = &ws.saux_s[wsl]; status_b = &ws.status_s[wsl];
         pgeo_b->get(S); oaux_b->get(S); saux_b->get(S); status_b->get(SB);
@@ -2206,6 +2333,7 @@ struct OiCall {
         g_stats.union_kernel_ms = 0;
         if(ran_union || (ran_sp && !sp_failed)) GPP_HIP(hipEventElapsedTime(&g_stats.union_kernel_ms, ws.e0, ws.eu));
         g_stats.cells_updated = 0; g_stats.solves = 0; g_stats.bulk_certified = 0;
+        g_stats.pair_fallback_items = (long long)counters[0];
         // (the factorisation counter carries two sums: low word the factorisations, high word the items whose bulk disc was certified -- oi_union.h)
         for(int k = 0; k < GPP_NSLOT; k++) {
             g_stats.cells_updated += (long long)counters[80 + 2 * k];
@@ -2311,6 +2439,7 @@ static int complete_pending(PendingOi& pc) {
         pc.stats.union_kernel_ms = pc.stats.kernel_ms;   // (the first pass is what stream A ran between the two timestamps; the list passes ran beside the call before)
         pc.stats.cells_updated = 0; pc.stats.solves = 0; pc.stats.bulk_certified = 0;
         const unsigned long long* const c = sl.h + 8;
+        pc.stats.pair_fallback_items = (long long)c[0];
         for(int k = 0; k < GPP_NSLOT; k++) {
             pc.stats.cells_updated += (long long)c[80 + 2 * k];
             pc.stats.solves += (long long)(c[81 + 2 * k] & 0xffffffffull); pc.stats.bulk_certified += (long long)(c[81 + 2 * k] >> 32);

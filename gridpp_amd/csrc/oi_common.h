@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "oi_small.h"
+#include "oi_pair_table.h"
 #include <algorithm>
 
 #pragma clang fp contract(off)
@@ -22,6 +23,7 @@ struct gpp_obs_index {
     DevBuf<float2> d_smeta;    // sorted: laf, orig (int bits)
     DevBuf<float4> d_ogeo;     // original order: x,y,z,elev
     DevBuf<float> d_olaf;      // original order: laf
+    gpp_pair_table pair;       // rho of the observation pairs of one scalar Barnes structure (oi_pair_table.h), built by the first call that needs it
 };
 
 gpp_obs_index* gpp_build_obs_index(gpp_points* pts);   // oi.hip

@@ -29,6 +29,7 @@ struct OiArgs {
     const float4* oaux;      // original order: laf, obs, pbg, ratio
     const float4* saux;      // the same records at the sorted positions (k_oi_union: one dependent load less per tile)
     int S, allow_extrap;
+    PairTabArgs pt;          // pair correlations of P from the index's table (k_oi_union, PLAIN forms; W == 0: none, every entry is evaluated)
     int* err;                // bit0: list overflow (needs the large-n path), bit1: singular / not SPD
     unsigned long long* counters;   // [80 + 2 k], [81 + 2 k]: cells updated, factorisations -- spread over GPP_NSLOT slots (k = block
                                     // index mod GPP_NSLOT): a quarter of a million atomics on ONE address would serialise in the L2
@@ -106,6 +107,15 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long mask, int m) {
 #endif
 #ifndef GPP_UNION_TRITAB
 #define GPP_UNION_TRITAB 1   // P build: (row, column) of a triangle entry from c_tri_tab instead of a square root and two corrections
+#endif
+#ifndef GPP_UNION_PAIRTAB
+#define GPP_UNION_PAIRTAB 1  // round 13 (profiles/oi_pair_table_ab.txt).  P build of the PLAIN forms: the entries from the pair table of the observation index, GPP_UNION_PTCH passes at a time
+#endif
+#ifndef GPP_UNION_PTCH
+#define GPP_UNION_PTCH 3
+#endif
+#ifndef GPP_UNION_PTPRE
+#define GPP_UNION_PTPRE 1
 #endif
 static __device__ const TriTab c_tri_tab = make_tri_tab();   // (oi_small.h; defined here and not there: oi_common.h also goes into ensi.hip, which has no use for it)
 // Two sizes of the kernel.  NC = 32: max_points <= 32, 32 register columns (+ 8 late columns kept in LDS), four waves per
@@ -1038,10 +1048,24 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         }
         int oorig = 0;     // SP: the observation (original order) of this row -- its scales are looked up there
         if constexpr(SP) oorig = L.worig[myslot];
+        // Round 13: with the pair table of the observation index (oi_pair_table.h) the P build below looks its entries up.  A row lane takes
+        // its bin row and the base of its row descriptors here, beside the record loads; the x, y, z, elevation record is then needed by the
+        // fallback alone (a work item with an entry the table does not hold redoes its P build by evaluation) and is loaded there.
+        constexpr bool PTAB = GPP_UNION_PAIRTAB != 0 && PLAIN && !SP && !PAIR;
+        const bool ptab = PTAB && a.pt.W > 0;   // (wave-uniform)
+        int pt_a = 0, pt_r = 0;
         float4 o0 = make_float4(0, 0, 0, NAN), o1 = make_float4(NAN, 0, 0, 0);
         if(solver && lane < u) {
-            o0 = sa.pgeo[mypos];
+            if(!ptab) o0 = sa.pgeo[mypos];
             o1 = a.saux[mypos];
+            if constexpr(PTAB) { if(ptab) { pt_r = a.pt.brow[mypos]; pt_a = mypos * (2 * a.pt.W + 1); } }
+        }
+        unsigned pt_t[GPP_UNION_PTCH] = {};   // (GPP_UNION_PTPRE: the triangle-table entries of the first group of passes, issued here like tri_next below)
+        if constexpr(PTAB && GPP_UNION_PTPRE != 0) {
+            if(ptab && solver) {
+#pragma unroll
+                for(int q = 0; q < GPP_UNION_PTCH; ++q) pt_t[q] = c_tri_tab.v[min(64 * q + lane, u * (u + 1) / 2 - 1)];
+            }
         }
         // (PLAIN P build: PB entries per lane and pass, their chains side by side -- chord, correctly rounded root and quotient, table exp: ~35
         //  dependent operations each; the nine passes of a 33-row union one after the other were a wave waiting for itself, see eval_n)
@@ -1284,9 +1308,78 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
         else {
         if(solver) {
         // lower triangle of P (oi.cpp:304-312), one entry per lane and pass: entry e = i (i + 1) / 2 + p, p <= i
-        if(lane < u) { L.orec[lane] = o0; L.olaf[lane] = o1.x; }
         float* colbuf = reinterpret_cast<float*>(L.f.solve);   // [u][U_MAXU]
         const int ntri = u * (u + 1) / 2;
+        // Round 13: the entries from the pair table.  For entry (i, p) the lane fetches row i's descriptor base and bin row and row p's sorted
+        // position and bin row across the lanes (ds_bpermute; no LDS array), loads the descriptor of row p's bin row in row i's window and then
+        // the value, both addresses clamped into the table.  The two gathers depend on each other, so the passes go GPP_UNION_PTCH at a time: the
+        // descriptors of the NEXT group (and the triangle-table entries of the one behind it) are issued before this group's descriptors are
+        // waited for, and a group's values are stored one group late, behind the next group's value loads.  The only thing the form carries out
+        // of the loop is `miss`: some lane's pair is not in the table -- then the item runs the loop below as if there were no table (counted).
+        bool direct = true;    // (wave-uniform) this item evaluates its entries
+        if constexpr(PTAB) {
+            if(ptab) {
+                constexpr int CH = GPP_UNION_PTCH;
+                const PairTabArgs& pt = a.pt;
+                const int npass = (ntri + 63) >> 6;
+                auto tri_of = [&](const int pass) { return (unsigned)c_tri_tab.v[min(64 * pass + lane, ntri - 1)]; };
+                unsigned tn[CH];          // triangle-table entries of the group whose descriptors are issued next
+                int4 dn[CH]; int pn[CH], en[CH];   // the group whose descriptors are in flight: descriptor, row p's sorted position, place in colbuf
+                bool miss = false;
+                auto issue_desc = [&]() {
+#pragma unroll
+                    for(int q = 0; q < CH; ++q) {
+                        const int ti = (int)(tn[q] >> 8), tp = (int)(tn[q] & 255u);
+                        const int ai = __builtin_amdgcn_ds_bpermute(ti << 2, pt_a), ri = __builtin_amdgcn_ds_bpermute(ti << 2, pt_r);
+                        const int rp = __builtin_amdgcn_ds_bpermute(tp << 2, pt_r);
+                        pn[q] = __builtin_amdgcn_ds_bpermute(tp << 2, mypos);
+                        bool in;
+                        dn[q] = pt.desc[d_pair_desc_index(pt, ai, ri, rp, in)];
+                        miss |= !in;                 // (a lane past the triangle repeats its last entry: a pair of this union like any other)
+                        en[q] = tp * U_MAXU + ti;
+                    }
+                };
+#pragma unroll
+                for(int q = 0; q < CH; ++q) tn[q] = GPP_UNION_PTPRE != 0 ? pt_t[q] : tri_of(q);
+                issue_desc();
+#pragma unroll
+                for(int q = 0; q < CH; ++q) tn[q] = tri_of(CH + q);
+                float vprev[CH]; int eprev[CH];
+                for(int p0 = 0; p0 < npass; p0 += CH) {
+                    int4 dc[CH]; int pc[CH], ec[CH];
+#pragma unroll
+                    for(int q = 0; q < CH; ++q) { dc[q] = dn[q]; pc[q] = pn[q]; ec[q] = en[q]; }
+                    if(p0 + CH < npass) {
+                        issue_desc();
+#pragma unroll
+                        for(int q = 0; q < CH; ++q) tn[q] = tri_of(p0 + 2 * CH + q);
+                    }
+                    float vc[CH];
+#pragma unroll
+                    for(int q = 0; q < CH; ++q) {
+                        bool hit;
+                        const unsigned vi = d_pair_value_index(pt, dc[q], pc[q], hit);
+                        miss |= !hit;
+                        vc[q] = pt.vals[vi];
+                    }
+                    if(p0 > 0) {
+#pragma unroll
+                        for(int q = 0; q < CH; ++q) colbuf[eprev[q]] = vprev[q];
+                    }
+#pragma unroll
+                    for(int q = 0; q < CH; ++q) { vprev[q] = vc[q]; eprev[q] = ec[q]; }
+                }
+#pragma unroll
+                for(int q = 0; q < CH; ++q) colbuf[eprev[q]] = vprev[q];
+                direct = wave_ballot(miss) != 0ull;
+                if(direct) {
+                    if(lane == 0 && a.counters) atomicAdd(&a.counters[0], 1ull);   // (gpp_oi_stats::pair_fallback_items)
+                    if(lane < u) o0 = sa.pgeo[mypos];
+                }
+            }
+        }
+        if(direct) {
+        if(lane < u) { L.orec[lane] = o0; L.olaf[lane] = o1.x; }
         const bool hh = dev_valid(st.h) && st.h != 0.0f, hv = dev_valid(st.v) && st.v != 0.0f, hw = dev_valid(st.w) && st.w != 0.0f;
         const double rh = hh ? 1.0 / (double)st.h : 0.0, rv_ = hv ? 1.0 / (double)st.v : 0.0, rw_ = hw ? 1.0 / (double)st.w : 0.0;
         for(int e0 = 0; e0 < ntri; e0 += 64 * PB) {
@@ -1336,6 +1429,7 @@ __device__ __forceinline__ void union_item(const OiArgs& a, int tile, int sub, c
             }
 #pragma unroll
             for(int q = 0; q < PB; ++q) if(e0 + 64 * q + lane < ntri) colbuf[tp[q] * U_MAXU + ti[q]] = cv[q];
+        }
         }
         // obs - background of every row (oi.cpp:293) for the row of lane 63: through the (still free) column staging area
         double* const colL = L.f.solve + (U_SOLVE - 64);   // free until the export (the P staging and 1/diag live below it)

@@ -725,6 +725,14 @@ typedef struct gpp_oi_stats {
     long long big_cells;      /* grid points with more than 62 usable observations (done by k_oi_big) */
     long long bulk_certified; /* of `solves`: work items of k_oi_union whose bulk disc was certified (every per-candidate test decided once per item);
                                * 0 under GPP_OI_NO_BULK_CERT, with elevation / land-fraction factors, and on k_oi_union_pair / k_oi_union_sp */
+    /* The pair table of the observation set (csrc/oi_pair_table.h): for a scalar Barnes structure on a 2-D grid, k_oi_union takes the pair
+     * correlations of P from a table kept with the Points handle, built by the first call with that structure and window.  It is a cache: a
+     * work item that meets a pair the table does not hold evaluates its P as without it.  Path overrides: GPP_OI_NO_PAIR_TABLE (none is built
+     * or used), GPP_OI_PAIR_WINDOW = n (a window of n bins instead of the estimate).  The result depends on neither. */
+    int pair_window;          /* half-width of the table's window in bins of the observation index; 0: no table was used */
+    long long pair_table_bytes;    /* its size; at most 128 MiB (the window shrinks to fit) */
+    long long pair_fallback_items; /* work items of k_oi_union that redid their P build by evaluation */
+    float pair_table_build_ms;     /* host time of the build inside this call; 0 when the cached table was used */
 } gpp_oi_stats;
 int gpp_oi_last_stats(gpp_oi_stats* stats);
 /* diagnostics: the two coordinate axes (0 = x, 1 = y, 2 = z; the two of largest extent) on which the observation index of `points` is binned --
